@@ -10,7 +10,10 @@ per-GPU work is fixed ("weak").  `--config c4` is BASELINE configs[3] instead: s
 N ("strong"); `--config c5` is configs[4] (mesh scene, depth 12).  The scene is resident in HBM (a scene handle, created before the
 timed region); a step passes the camera and the parameters; outputs stay in HBM.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the headline: Msamples/s,
+ms_per_step and the roofline of the timed steps.  `--full` adds every other leg below (stress, organisations, estimators,
+cpu_baseline, other precision, configs, end_to_end, scene_build, tiles_of_8_gpus), each in runs of its own after the timed steps;
+without it those keys are null.  `--dump-outputs DIR` writes the frame the last timed step rendered to DIR/hdr.npy (dump_outputs()).
   roofline      the dominant kernel (k_path: one launch per pass) against the HBM roofline: algorithmic bytes from the
                 device counters of the LAST TIMED step divided by that step's own kernel time (HIP events the library
                 records around every k_path launch on the render stream) — so avg_launch_ms * launches <= ms_per_step.
@@ -63,6 +66,28 @@ def kernel_source_hash():
     env = {k: v for k, v in os.environ.items() if k != "LD_PRELOAD" and not k.startswith(("ROCPROF", "ROCP_", "ROCPROFILER", "HSA_TOOLS"))}
     out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "julia-spira_amd", "csrc"), "build_id"], check=True, capture_output=True, text=True, env=env).stdout
     return out.strip().splitlines()[-1].strip()
+
+
+DUMP_BUDGET = 64 * 10**6     # --dump-outputs: bytes of array data at most; a larger frame is stored as a seeded sample of its pixels
+
+
+def dump_outputs(dirname, hdr):
+    """--dump-outputs DIR: what the timed path hands its caller — the planar HDR frame [3, H, W] of the last timed step, in the run's
+    precision — as DIR/hdr.npy.  A frame above DUMP_BUDGET keeps a fixed, seeded sample of its pixels: hdr.npy is then [3, k] and
+    DIR/hdr_pixels.npy holds their row-major pixel indices (float64, exact)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = np.ascontiguousarray(hdr)
+    pix_file = os.path.join(dirname, "hdr_pixels.npy")
+    if a.nbytes > DUMP_BUDGET:
+        npix = a.shape[1] * a.shape[2]
+        k = (DUMP_BUDGET - 4096) // (3 * a.itemsize + 8)        # (room for the two .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(npix, size=k, replace=False))
+        np.save(pix_file, idx.astype(np.float64))
+        a = a.reshape(3, npix)[:, idx]
+    elif os.path.exists(pix_file):
+        os.remove(pix_file)
+    np.save(os.path.join(dirname, "hdr.npy"), a)
 
 
 def metric_string(W, H, spp, depth):
@@ -207,6 +232,8 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the stress scene and the other kernel organisations")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true", help="all ranks use GPU 0 and the gloo backend (not a measurement)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline (N=1 only; the --no-* options still apply)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the frame of the last timed step to DIR/hdr.npy")
     args = ap.parse_args()
     if args.first_call_probe:
         return first_call_probe(args.first_call_probe)
@@ -368,21 +395,24 @@ def main():
     result = None
     if rank == 0:
         assert bool(torch.isfinite(img).all()), "non-finite pixels"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img.cpu().numpy())
+        full = args.full and world == 1           # every leg below runs only on request (N=1 only), after the timed steps and the dump
         if args.kernel == "wavefront":
             roof = roofline_record(c_timed, args.prec, args.kernel, scene_name + ("_ext" if ext_flags else ""), pmc_shape, src_hash)
-        elif args.kernel == "bounce":
+        elif args.kernel == "bounce" and args.full:     # (a profiled render of its own)
             roof = side_run(scene_name, "bounce", args.prec, reps=1)[2]
         else:
             roof = None
         # ---- the same workload in the other precision (N=1 only; informational, never `value`)
         alt = None
-        if world == 1 and not args.no_alt_precision:
+        if full and not args.no_alt_precision:
             ap_ = "f32" if args.prec == "f64" else "f64"
             v, ms, aroof = side_run(scene_name, args.kernel, ap_)
             alt = {"dtype": ap_, "value": round(v, 3), "unit": "Msamples/s", "ms_per_step": round(ms, 3), "roofline": aroof}
         # ---- stress scene and the other kernel organisations (N=1 only; informational)
         stress, stress_mesh, extensions, orgs, estimators = None, None, None, None, None
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             if scene_name != "s3" and args.config != "c5":
                 v, ms, sroof = side_run("s3", args.kernel, args.prec)
                 stress = {"scene": "s3", "what": "the same frame with the scene inside a closed box: every path runs all max_depth segments (SURVEY 8d)",
@@ -424,7 +454,7 @@ def main():
         # ---- the other BASELINE configurations that fit one GPU (N=1 only): configs[3] = 1080p spp 256 depth 8 on S3 (4 passes of 64 sample slots; on
         # 8 GPUs every rank renders its 135-row share of this), configs[4] = the 81 920-triangle mesh scene S4 at depth 12 — both precisions each
         other_configs = None
-        if world == 1 and not args.no_extras and (W, H) == (1920, 1080):
+        if full and not args.no_extras and (W, H) == (1920, 1080):
             other_configs = {}
             for cname in ("c4", "c5"):
                 if cname == args.config:
@@ -439,7 +469,7 @@ def main():
         # ---- end to end through the host-buffer entry point (N=1 only; never `value`): scene arrays in, image out to host memory — validation,
         # upload, the same kernels, one device-to-host copy of the frame (SURVEY §8d asks for it beside the device-resident figure)
         end_to_end = None
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             hdr_host, _ = B.render(sc[0], sc[1], sc[2], sc[3], params, args.prec)      # warm-up (pageable host memory, like a caller's)
             t1 = time.perf_counter()
             for _ in range(3):
@@ -477,7 +507,7 @@ def main():
         # ---- scene build latency (N=1 only): the host BVH build + uploads of the configs[4] mesh, and the first call of a fresh process in the shape of the
         # reference's own test (tests/bunny-test.jl:37-60: 64x64, spp 1, depth 25 — one render of a new mesh); each precision in its own fresh process
         scene_build = None
-        if world == 1 and not args.no_extras:
+        if full and not args.no_extras:
             import subprocess
             scene_build = {"what": "fresh process per precision (bench.py --first-call-probe): first_call_ms = spira_render_* with host arrays on the 81 920-triangle scene at "
                                    "64x64 spp 1 depth 25, everything included (context, validation, hash, host BVH build on host_threads cores, uploads, first launches, frame back); "
@@ -492,7 +522,7 @@ def main():
         # ---- what a rank's render of an 8-GPU run costs (N=1 only, the headline shape): this GPU renders each of the 8 ranks' tiles of the weak-scaling
         # workload (spp 64 x 8 on rows r, r + 8, ...) in turn; the step of the 8-GPU run costs the slowest rank's render plus the exchange (not measurable here)
         tiles8 = None
-        if world == 1 and not args.no_extras and (W, H) == (1920, 1080) and cfg["scaling"] == "weak":
+        if full and not args.no_extras and (W, H) == (1920, 1080) and cfg["scaling"] == "weak":
             ms8 = []
             for r8 in range(8):
                 t8 = D.tile_params(H, 8, r8)
@@ -513,7 +543,7 @@ def main():
                               "frame_ms / slowest tile bounds the weak-scaling efficiency from the render side; the gather (6.2 MB per rank over xGMI) comes on top"}
         # ---- CPU baseline leg (rank 0, N=1 only): the oracle port on the host cores, bounded sample
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             import oracle_py as O
             ns, nm, nt = counts
             cores = min(O.max_threads(), host_cpu_share())     # the box's cgroup CPU share, not the host's core count

@@ -87,6 +87,27 @@ def test_bench_line_keys_are_declared():
         assert key in src, key
 
 
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the budget is written whole; a larger one as the same seeded pixel sample on every run, with the
+    indices of its pixels, within the budget."""
+    import numpy as np
+    hdr = np.random.default_rng(1).random((3, 60, 80))
+    bench.dump_outputs(str(tmp_path / "whole"), hdr)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["hdr.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "hdr.npy"), hdr)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096 + 32 * 1000)      # room for 1 000 pixels of 3 float64 values + a float64 index
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), hdr)
+    a, ia = np.load(tmp_path / "a" / "hdr.npy"), np.load(tmp_path / "a" / "hdr_pixels.npy")
+    assert a.shape == (3, 1000) and a.dtype == np.float64 and ia.dtype == np.float64 and len(set(ia)) == 1000
+    assert np.array_equal(a, np.load(tmp_path / "b" / "hdr.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "hdr_pixels.npy"))
+    assert np.array_equal(a, hdr.reshape(3, -1)[:, ia.astype(np.int64)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BUDGET
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 64 * 10**6)
+    bench.dump_outputs(str(tmp_path / "a"), hdr)         # a later whole frame leaves no stale index file behind
+    assert sorted(os.listdir(tmp_path / "a")) == ["hdr.npy"]
+
+
 def test_c4_tile_arithmetic_on_8_gpus():
     """bench.py --config c4 --gpus 8: interleaved rows give every rank 135 rows of 1080, and spp stays 256 in total."""
     sys.path.insert(0, os.path.join(ROOT, "julia-spira_amd"))

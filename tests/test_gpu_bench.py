@@ -21,7 +21,7 @@ def _bench(*args):
 
 
 def test_default_line_has_the_contract_keys_and_is_consistent():
-    d = _bench()                                         # the default workload: 1080p, spp 64, depth 8, Float64 (a few seconds on the device)
+    d = _bench("--full")                                 # the default workload: 1080p, spp 64, depth 8, Float64 (a few seconds on the device), every leg
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "end_to_end", "configs", "kernel_source_hash"):
         assert k in d, k
@@ -46,6 +46,28 @@ def test_default_line_has_the_contract_keys_and_is_consistent():
         assert scene in e["workload"] and "spp=%d depth=%d" % (spp, depth) in e["metric"]
         for pr in ("f64", "f32"):
             assert e[pr]["value"] > 0 and e[pr]["roofline"]["launches"] == spp // 64 and e[pr]["roofline"]["frac"] > 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_frame(tmp_path):
+    """Without --full the line carries the headline of the timed steps only (every other leg null); --steps sets the timed steps;
+    --dump-outputs writes the frame of the last timed step in the run's precision."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 8192, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["unit"] == "Msamples/s" and d["higher_is_better"] is True
+    assert d["metric"] == "Msamples/sec at 1920x1080 spp=64 depth=8; fraction of HBM roofline"
+    assert abs(d["value"] - d["config"]["samples_per_step"] / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 1e-3
+    assert 0 < d["roofline"]["frac"] < 1 and d["roofline"]["avg_launch_ms"] * d["roofline"]["launches"] <= d["ms_per_step"] * 1.05
+    for k in ("cpu_baseline", "end_to_end", "scene_build", "tiles_of_8_gpus", "configs", "other_precision", "stress", "stress_mesh", "extensions",
+              "organisations", "estimators"):
+        assert d[k] is None, k
+    assert sorted(os.listdir(tmp_path)) == ["hdr.npy"]
+    hdr = np.load(tmp_path / "hdr.npy")
+    assert hdr.shape == (3, 1080, 1920) and hdr.dtype == np.float64 and np.isfinite(hdr).all() and hdr.mean() > 0
 
 
 def test_config_c5_is_labelled_depth_12():
