@@ -1463,8 +1463,51 @@ template <class T> struct PathArgs {
                                      // its sub-chunks so that the k waves one fat wave takes over work on image blocks far apart (load balance)
     uint32_t *redo;                  // [NW] speculative division (SpecDiv above): the SPEC launch leaves 1 for a wave that has to be rendered again,
     uint32_t redo_only;              // the exact launch behind it (redo_only = 1) renders exactly those waves.  NULL / 0: one exact launch.
-    Stats *stats;                    // redo_only: counts the waves rendered again
+    Stats *stats;                    // redo_only: counts the waves rendered again; pixel-owning passes: every wave adds its counters
+    // Pixel-owning passes (Float64 sphere scenes without extensions, k_eff <= 64; NULL: sub-chunks dealt round-robin and k_resolve after the launch): wave w
+    // owns the pixels owned_pixel(w, NW, 0..63) and all k_eff slots of each, and ends by summing them into accum — k_resolve's statements, in the
+    // kernel.  Path e of the wave (e < 64 k_eff) is slot (e / RUN) % k_eff of pixel e % RUN of its run e / (RUN k_eff): a row of 64 lanes holds RUN
+    // adjacent pixels x 64 / RUN slots — camera rays nearly alike, and a radiance store writes 64 / RUN runs of RUN adjacent entries.  (64 slots x
+    // 1 pixel per row ran k_path 0.55 ms longer in Float64: every store scattered over 64 lines; 64 pixels x 1 slot lost the dense continuation.)
+    Pack4<T> *accum;
+    FastDiv fd_keff;
+    uint32_t k_eff;                  // slots of this pass (n_first / tile_pixels)
+    uint32_t accum_first;            // the first pass of a fresh render: the sums start at 0
 };
+
+// Pixel-owning passes: lane l of wave w owns pixel ((l / RUN) * nw + w) * RUN + l % RUN — 64 / RUN runs of RUN adjacent pixels, nw * RUN pixels
+// apart, so that a wave's cost is the mean of pixels all over the frame (contiguous blocks are all sky or all sphere: a long launch tail).
+// RUN = 4 measured best (S1 1080p; 2, 8 and 16 slower: docs/experiments.md §16).
+// A bijection of [0, 64 nw) onto itself; the host makes 64 nw >= tile_pixels.
+#ifndef SPIRA_RESOLVE_RUN
+#define SPIRA_RESOLVE_RUN 4
+#endif
+__device__ __forceinline__ uint32_t owned_pixel(uint32_t w, uint32_t nw, uint32_t l) {
+    constexpr uint32_t kRun = SPIRA_RESOLVE_RUN;
+    static_assert(64 % kRun == 0, "a run length divides the wave");
+    return ((l / kRun) * nw + w) * kRun + l % kRun;
+}
+
+// accum[p] (+)= the pixel's k_eff path radiances in sample order: `color = color + ray_color(...)` of examples/julia-raytracer.jl:401.
+// Eight independent 12/24-byte loads in flight per lane, then the adds in sample order (only the loads are batched).
+template <class T>
+__device__ __forceinline__ void resolve_pixel(Pack4<T> *accum, const Pack3<T> *L, uint32_t tile_pixels, uint32_t k_eff, bool first_pass, uint32_t p) {
+    Pack4<T> acc;
+    if (first_pass) { acc.x = 0; acc.y = 0; acc.z = 0; acc.w = 0; } else acc = accum[p];
+    uint32_t s = 0;
+    for (; s + 8 <= k_eff; s += 8) {
+        Pack3<T> l[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) l[k] = L[(size_t)(s + k) * tile_pixels + p];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { acc.x = acc.x + l[k].x; acc.y = acc.y + l[k].y; acc.z = acc.z + l[k].z; }
+    }
+    for (; s < k_eff; ++s) {
+        const Pack3<T> l = L[(size_t)s * tile_pixels + p];
+        acc.x = acc.x + l.x; acc.y = acc.y + l.y; acc.z = acc.z + l.z;
+    }
+    accum[p] = acc;
+}
 
 // queue word C.y: the path index (bit 31 = "L[q] already holds radiance") and, in Float64, the hit reference beside it
 __device__ __forceinline__ float pack_qref(uint32_t q, uint32_t, float) { return __uint_as_float(q); }
@@ -1565,7 +1608,9 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     uint32_t n_rmw = 0, n_store = 0, n_seg = 0, n_enq = 0, n_park = 0;   // (n_park: entries written to the mesh list, wave-uniform)
     uint32_t n_wtrips = 0, n_ltrips = 0;                         // trips of the traversal sessions' walk loop and the lanes walking in them (wave-uniform: scalar registers)
     uint32_t n_in = 0;                                           // packets waiting in this wave's region (rounds >= 1)
-    const uint32_t n_sub_first = (a.n_first + SUB - 1) / SUB;
+    const bool own = !BVH && !EXT && !TRI && sizeof(T) == 8 && a.accum != nullptr;      // a pixel-owning pass (PathArgs::accum)
+    const uint32_t n_own = own ? 64u * a.k_eff : 0u;             // its paths of this wave
+    const uint32_t n_sub_first = own ? (n_own + SUB - 1) / SUB : (a.n_first + SUB - 1) / SUB;
 
     // park a ray on the wave's mesh list (entry = 3 packets: {o, d.x} {d.y, d.z, beta.xy} {beta.z, closest so far, q, object so far + stage of the hit})
     auto park = [&](uint32_t slot_i, const Vec<T> o_, const Vec<T> d_, const Vec<T> beta_, T closest_, uint32_t q_, int prim_, uint32_t stage_hit) {
@@ -1593,7 +1638,8 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     // Mode 1: wave w*k + i works on the sub-chunks of "logical" wave i*(NW/k) + w, so that the k waves a fat wave of the second launch takes over
     // (w*k .. w*k+k-1: contiguous regions) cover image blocks NW/k sub-chunks apart — adjacent blocks see the mesh together or not at all, and
     // fat waves made of them ran 1.5x apart.  (Any bijection will do: the assignment only has to be a pure function of the wave index.)
-    const uint32_t first_sub = mesh_mode == 1u ? (wid % a.resume_k) * (NW / a.resume_k) + wid / a.resume_k : wid;
+    const uint32_t first_sub = own ? 0u : (mesh_mode == 1u ? (wid % a.resume_k) * (NW / a.resume_k) + wid / a.resume_k : wid);
+    const uint32_t sub_step = own ? 1u : NW;
     MESH_STAT(unsigned long long dbg_t0 = __builtin_readcyclecounter(); unsigned long long dbg_sess = 0, dbg_walk = 0; uint32_t dbg_ns = 0, dbg_ws = 0, dbg_ls = 0, dbg_rf = 0, dbg_rays = 0, dbg_rounds = 0, dbg_ws1 = 0, dbg_ls1 = 0, dbg_h[4] = {0, 0, 0, 0};)
     for (uint32_t round = 0; ; ++round) {
         MESH_STAT(++dbg_rounds;)
@@ -1603,10 +1649,10 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
         uint32_t *rout = a.qref[round & 1];
         const uint2 *kin = a.qkey[(round + 1) & 1];
         uint2 *kout = a.qkey[round & 1];
-        const uint32_t limit = first ? a.n_first : n_in;
+        const uint32_t limit = first ? (own ? n_own : a.n_first) : n_in;
         const uint32_t n_sub = first ? n_sub_first : (n_in + SUB - 1) / SUB;
         uint32_t fill = 0;
-        for (uint32_t sub = first ? first_sub : 0u; sub < n_sub; sub += first ? NW : 1u) {
+        for (uint32_t sub = first ? first_sub : 0u; sub < n_sub; sub += first ? sub_step : 1u) {
             Vec<T> o[R], beta[R];
             Pending<T> pend[R];                           // between trips pend[r].v holds the direction the hit was reached along
             ExtState<T> ex[R];                            // EXT instantiations only (dead otherwise)
@@ -1621,12 +1667,20 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                 pend[r].kind = kDead; pend[r].rough = 0; pend[r].v = mk<T>(0, 0, 0);
                 o[r] = mk<T>(0, 0, 0); beta[r] = mk<T>(1, 1, 1);
                 bool parked = false; T park_t = 0; int park_prim = -1;
-                if (idx < limit) {
+                uint32_t qf = idx;                                // round 0: the camera ray's path index
+                bool in = idx < limit;
+                if (own && first) {                               // pixel-owning pass: idx is the wave's path (PathArgs::accum)
+                    const uint32_t t = idx / SPIRA_RESOLVE_RUN, run = fastdiv(t, a.fd_keff);
+                    const uint32_t px = owned_pixel(wid, NW, run * SPIRA_RESOLVE_RUN + idx % SPIRA_RESOLVE_RUN);
+                    qf = (t - run * a.k_eff) * rc.tile_pixels + px;
+                    in = in && px < rc.tile_pixels;
+                }
+                if (in) {
                     if (first) {
                         uint32_t pixel, sample, pi, pj;
                         Vec<T> d;
-                        q[r] = idx;
-                        path_of<T>(rc, idx, a.pass, pi, pj, pixel, sample);
+                        q[r] = qf;
+                        path_of<T>(rc, qf, a.pass, pi, pj, pixel, sample);
                         if (kCarry) { ka[r] = mix32(rc.sA + pixel) ^ (sample << 8); kb[r] = mix32(rc.sB ^ pixel) + (sample << 8); }
                         camera_ray_lds<T>(rc, cam_lds, pix_div, pi, pj, pixel, sample, o[r], d, pol);
                         if (EXT) { ex[r].flags = rc.flags; if (rc.flags & kExtSpectral) beta[r] = ext_wavelength<T>(sc, rc.sA, rc.sB, pixel, sample, ex[r]); }
@@ -1643,7 +1697,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                         else if (prim < 0) {                      // the camera ray leaves the scene: sky, :365-366
                             const Vec<T> c = sky_term_x<T, EXT>(d, beta[r], &ex[r]);
                             Pack3<T> l; l.x = c.x; l.y = c.y; l.z = c.z;
-                            a.L[idx] = l;
+                            a.L[qf] = l;
                             ++n_store;
                         } else {
                             valid[r] = true;
@@ -2066,6 +2120,20 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     }
     for (int sft = 32; sft > 0; sft >>= 1) { n_rmw += __shfl_down(n_rmw, sft); n_seg += __shfl_down(n_seg, sft); n_store += __shfl_down(n_store, sft); }
     const bool again = SPEC && __any(outside_window<T>(pol));    // some quotient of this wave may not be the IEEE one: the exact launch redoes the wave
+    if (own && !again && !(SPEC && a.redo_only == 2u)) {        // (a wave rendered again resolves in the exact launch: accum is added to once)
+        // Every path of this wave's pixels has ended, and only this wave's lanes stored their radiance: as for the queue region above, waiting
+        // for the stores (workgroup-scope release) is all that takes on one CU — no other CU ever wrote these bytes.
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const uint32_t px = owned_pixel(wid, NW, lane);
+        if (px < rc.tile_pixels) resolve_pixel<T>(a.accum, a.L, rc.tile_pixels, a.k_eff, a.accum_first != 0, px);
+        // k_resolve's fold of the statistics rows, one wave instruction: lane i adds counter i (Stats' first four fields)
+        const uint32_t seg = __shfl(n_seg, 0), rmw = __shfl(n_rmw, 0), sto = __shfl(n_store, 0);
+        if (lane < 4) {
+            unsigned long long *f = lane == 0 ? &a.stats->segments : (lane == 1 ? &a.stats->rays_enqueued : (lane == 2 ? &a.stats->radiance_rmw : &a.stats->radiance_store));
+            atomicAdd(f, (unsigned long long)(lane == 0 ? seg : (lane == 1 ? n_enq : (lane == 2 ? rmw : sto))));
+        }
+    }
     MESH_STAT(if (lane == 0) { unsigned long long *g = g_mesh_dbg + (mesh_mode == 2u ? 16 : 0);
                                atomicAdd(&g[0], __builtin_readcyclecounter() - dbg_t0); atomicAdd(&g[1], dbg_sess); atomicAdd(&g[2], (unsigned long long)dbg_ns);
                                atomicAdd(&g[3], (unsigned long long)dbg_ws); atomicAdd(&g[4], (unsigned long long)dbg_ls); atomicAdd(&g[5], (unsigned long long)dbg_rf);
@@ -2753,25 +2821,8 @@ __global__ __launch_bounds__(64) void k_trace_variant(const BounceArgs<T> a, con
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_resolve(Pack4<T> *accum, const Pack3<T> *L, uint32_t tile_pixels, uint32_t k_eff, int first_pass,
                                                     const uint32_t *blk_stats, uint32_t n_rows, Stats *stats) {
-    for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < tile_pixels; p += gridDim.x * kBlock) {
-        Pack4<T> acc;
-        if (first_pass) { acc.x = 0; acc.y = 0; acc.z = 0; acc.w = 0; } else acc = accum[p];
-        // eight independent 12/24-byte loads in flight per lane, then the adds in sample order (the sum order is
-        // the reference's; only the loads are batched)
-        uint32_t s = 0;
-        for (; s + 8 <= k_eff; s += 8) {
-            Pack3<T> l[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) l[k] = L[(size_t)(s + k) * tile_pixels + p];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { acc.x = acc.x + l[k].x; acc.y = acc.y + l[k].y; acc.z = acc.z + l[k].z; }
-        }
-        for (; s < k_eff; ++s) {
-            const Pack3<T> l = L[(size_t)s * tile_pixels + p];
-            acc.x = acc.x + l.x; acc.y = acc.y + l.y; acc.z = acc.z + l.z;
-        }
-        accum[p] = acc;
-    }
+    for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < tile_pixels; p += gridDim.x * kBlock)
+        resolve_pixel<T>(accum, L, tile_pixels, k_eff, first_pass != 0, p);
     if (blockIdx.x == 0 && blk_stats) {
         __shared__ unsigned long long red[4];
         if (threadIdx.x < 4) red[threadIdx.x] = 0;

@@ -670,6 +670,12 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
     if (!bad && !covers(c.blkstats, a.blk_stats, nw * 4 * sizeof(uint32_t))) bad = "per-wave statistics";
     if (!bad && !covers(c.L, a.L, (uint64_t)a.n_first * sizeof(spira::Pack3<T>))) bad = "per-path radiance";
     if (!bad && !covers(c.stats, a.stats, sizeof(spira::Stats))) bad = "counters";
+    if (!bad && a.accum) {                  // pixel-owning pass: an instantiation that resolves, a wave for every pixel, every wave's paths in its region
+        const uint64_t tp = a.rc.tile_pixels;
+        if (!covers(c.accum, a.accum, tp * sizeof(spira::Pack4<T>)) || sizeof(T) != 8 || a.scene.n_triangles || mesh || (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) ||
+            a.k_eff == 0 || a.k_eff > 64 || (uint64_t)a.k_eff * tp != a.n_first || 64 * nw < tp || a.cap < 64ull * a.k_eff)
+            bad = "pixel-owning pass";
+    }
     if (bad) return fail(SPIRA_E_LIMIT, std::string("internal: a workspace is smaller than the launch needs (") + bad + ")");
     return 0;
 }
@@ -737,7 +743,20 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     const uint32_t max_blocks = (uint32_t)c.num_cus * env_u32("SPIRA_BLOCKS_PER_CU", blocks_per_cu);
     const uint32_t wpb = spira::kBlock / 64;
     const uint32_t sub = 64 * R;                                   // rays per wave sub-chunk
+    // pixel-owning passes (PathArgs::accum): each wave sums its own 64 pixels at its end instead of k_resolve streaming the whole of L after the
+    // launch — S1 Float64 -1.5 … -4.5 %.  Only where that was measured to pay: Float64 scenes of spheres alone, no extension, at most 64 slots per pass.
+    // In Float32 the end-of-wave sum costs k_path what k_resolve costs (S1 +0.30 / 0.29 ms); in the kernels with the LDS triangle scan or the
+    // extensions its code costs spilled registers (glass scene Float64 +15 %, S2 +4 %).  SPIRA_FUSED_RESOLVE=0: round-robin dealing + k_resolve (A/B, tests).
+    // (R = 2 too: the instantiation of SPIRA_R=1 is compiled with the triangle scan.)
+    const bool fused = persistent && sizeof(T) == 8 && R == 2 && nt_scene == 0 && (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) == 0 &&
+                       slots <= 64 && env_u32("SPIRA_FUSED_RESOLVE", 1) != 0;
     auto geometry = [&](uint64_t n_first, uint32_t &G, uint32_t &cap) {
+        if (fused) {                                                // one wave per 64 pixels; its region holds all its paths
+            const uint64_t k = n_first / tile_pixels;
+            G = (uint32_t)((tile_pixels + 64 * wpb - 1) / (64 * wpb));
+            cap = (uint32_t)((64 * k + sub - 1) / sub * sub);
+            return;
+        }
         const uint64_t n_sub = (n_first + sub - 1) / sub;
         G = (uint32_t)std::min<uint64_t>((n_sub + wpb - 1) / wpb, max_blocks);
         const uint64_t nw = (uint64_t)G * wpb;
@@ -995,6 +1014,10 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
                     while (k > 1 && (nw % k != 0 || nw / k < fat)) k >>= 1;
                     pa.resume_k = k; pa.resume_nw = nw;
                 }
+                if (fused) {
+                    pa.accum = (P4 *)c.accum.p; pa.k_eff = k_eff; pa.fd_keff = spira::fastdiv_make(k_eff);
+                    pa.accum_first = (pass == 0 && !progressive) ? 1u : 0u;
+                }
                 if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
                 HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
                 if (int rc = launch_path<T>(R, dim3(G), lds_a, st, pa, spec)) return rc;
@@ -1037,6 +1060,7 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
                     ++launches;
                 }
             }
+            if (fused) continue;      // the waves of the launch resolved their pixels and added their counters
             uint32_t rblocks = std::min<uint32_t>((uint32_t)((tile_pixels + spira::kBlock - 1) / spira::kBlock), max_blocks);
             hipLaunchKernelGGL((spira::k_resolve<T>), dim3(rblocks), dim3(spira::kBlock), 0, st, (P4 *)c.accum.p, (const spira::Pack3<T> *)c.L.p,
                                (uint32_t)tile_pixels, k_eff, (pass == 0 && !progressive) ? 1 : 0, mega ? (const uint32_t *)nullptr : (const uint32_t *)c.blkstats.p,
