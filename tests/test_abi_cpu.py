@@ -98,6 +98,28 @@ def test_the_translation_units_hold_the_kernels_they_are_built_for():
         assert flag in mk, flag
 
 
+def test_every_k_path_instantiation_has_a_case(binding):
+    """The k_path instantiations in libspira_hip.so (host stubs: _ZN5spira6k_pathI<d|f>L<i|b><value>E...E, no demangler needed) are exactly the
+    keys of tests/test_gpu_instantiations.py's KERNELS: a new template parameter or instantiation fails here until it gets a GPU case or a
+    reason why no render reaches it."""
+    from test_gpu_instantiations import KERNELS
+    blob = open(binding.LIB_PATH, "rb").read()
+    names = set(re.findall(rb"_ZN5spira6k_pathI[df](?:L[ib]\d+E)+E", blob))
+    found = set()
+    for n in names:
+        args = re.findall(rb"L([ib])(\d+)E", n)
+        found.add((chr(n[len(b"_ZN5spira6k_pathI")]),) + tuple(bool(int(v)) if t == b"b" else int(v) for t, v in args))
+    assert len(found) == len(names) == 64, sorted(found)
+    assert found == set(KERNELS), (sorted(found - set(KERNELS)), sorted(set(KERNELS) - found))
+    reachable = [k for k, v in KERNELS.items() if not isinstance(v, str)]
+    assert len(reachable) == 44
+    for k, v in KERNELS.items():
+        if isinstance(v, str):
+            assert v.startswith("unreachable: "), k
+        else:
+            assert v, k
+
+
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_camera_matches_oracle(binding, oracle, prec):
     rng = np.random.default_rng(1)

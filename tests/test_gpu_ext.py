@@ -45,7 +45,8 @@ def test_ext_geometry_and_image_match_oracle(gpu, oracle, ext, prec):
             assert np.array_equal(hdr, first) and seg == oseg
 
 
-def test_ext_bvh_mesh_and_tiling(gpu, oracle):
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_ext_bvh_mesh_and_tiling(gpu, oracle, prec):
     """A glass blob (1 280 triangles through the BVH) in spectral mode: oracle image, and an interleaved tiling reassembles bit for bit."""
     from spira_hip import distributed as D
     s = scenes.scene_s4(level=3)
@@ -53,13 +54,13 @@ def test_ext_bvh_mesh_and_tiling(gpu, oracle):
     ns, nm, nt = _counts(s)
     flags = gpu.EXT_DIELECTRIC | gpu.EXT_SPECTRAL | gpu.POST_NONE
     W, H = 128, 72
-    hdr, _ = gpu.render(*_args(s), gpu.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6), "f64")
+    hdr, _ = gpu.render(*_args(s), gpu.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6), prec)
     seg = gpu.counters()["segments"]
-    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6), "f64")
+    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6), prec)
     assert _close(hdr, ohdr)[0] == 0 and seg == oseg
-    tiles = [gpu.render(*_args(s), gpu.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6, **D.tile_params(H, 3, r, 4)), "f64")[0] for r in range(3)]
+    tiles = [gpu.render(*_args(s), gpu.make_params(W, H, 4, 10, ns, nm, nt, flags=flags, seed=6, **D.tile_params(H, 3, r, 4)), prec)[0] for r in range(3)]
     mr = D.max_rows(H, 3, 4)
-    padded = [np.concatenate([t, np.zeros((3, mr - t.shape[1], W))], axis=1) for t in tiles]
+    padded = [np.concatenate([t, np.zeros((3, mr - t.shape[1], W), dtype=t.dtype)], axis=1) for t in tiles]
     assert np.array_equal(D.assemble(padded, H, 3, 4), hdr)
 
 

@@ -17,6 +17,10 @@ from test_gpu_parity import _args, _close, _counts
 
 pytestmark = pytest.mark.gpu
 W, H = 1920, 1080
+EXT_SPECTRAL = 0x40000      # include/spira_hip.h; configs[4] with it = bench.py's c5_spectral leg
+# (precision, flags): the plain configuration keeps its ids, the spectral one is "spectral-<precision>"
+_C5 = [(pr, fl) for fl in (0, EXT_SPECTRAL) for pr in ("f32", "f64")]
+_C5_IDS = [pr if fl == 0 else "spectral-" + pr for pr, fl in _C5]
 
 
 def _slab_vs_oracle(gpu, oracle, s, spp, depth, seed, prec, tile, full):
@@ -69,33 +73,36 @@ def test_config4_full_size_stripe_matches_oracle(gpu, oracle, prec):
     _slab_vs_oracle(gpu, oracle, s, 256, 8, seed, prec, dict(row0=540, rows=4), full)
 
 
-@pytest.mark.parametrize("prec", ["f32", "f64"])
-def test_config5_full_size_spp64(gpu, prec):
-    """BASELINE configs[4] at its real size: 81 920 triangles, 1080p, spp 64, depth 12.  Wavefront == megakernel bit for bit,
-    the 8-way stripe tiling reassembles to the frame, every pixel finite and non-negative, segment bounds."""
+@pytest.mark.parametrize("prec,flags", _C5, ids=_C5_IDS)
+def test_config5_full_size_spp64(gpu, prec, flags):
+    """BASELINE configs[4] at its real size: 81 920 triangles, 1080p, spp 64, depth 12, without and with spectral transport (bench.py's
+    c5_spectral leg).  Wavefront == megakernel bit for bit, the 8-way stripe tiling reassembles to the frame, every pixel finite (and
+    non-negative in RGB transport), segment bounds."""
     s = scenes.scene_s4()
     ns, nm, nt = _counts(s)
     seed, spp, depth = scenes.seed_for(5), 64, 12
     assert nt == 81920
-    wf, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed), prec)
+    wf, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=flags), prec)
     c = gpu.counters()
     assert c["samples"] == W * H * spp and W * H * spp < c["segments"] <= W * H * spp * depth
-    mg, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=gpu.KERNEL_MEGA), prec)
+    mg, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=flags | gpu.KERNEL_MEGA), prec)
     assert np.array_equal(wf, mg) and gpu.counters()["segments"] == c["segments"]
     del mg
-    assert np.isfinite(wf).all() and wf.min() >= 0
+    # (a path of spectral transport carries one wavelength, whose sRGB colour can lie outside the gamut: the oracle's images have negative pixels too)
+    assert np.isfinite(wf).all() and (flags != 0 or wf.min() >= 0)
     tiles, seg = [], 0
     for r in range(8):
-        t, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, **D.tile_params(H, 8, r)), prec)
+        t, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=flags, **D.tile_params(H, 8, r)), prec)
         seg += gpu.counters()["segments"]
         tiles.append(t)
     assert np.array_equal(D.assemble(tiles, H, 8), wf) and seg == c["segments"]
 
 
-@pytest.mark.parametrize("prec", ["f32", "f64"])
-def test_config5_full_mesh_geometry_vs_linear_scan(gpu, oracle, prec):
+@pytest.mark.parametrize("prec,flags", _C5, ids=_C5_IDS)
+def test_config5_full_mesh_geometry_vs_linear_scan(gpu, oracle, prec, flags):
     """The 81 920-triangle tree against the oracle's linear scan over all 81 920 triangles (like the reference's
-    closest-hit loop, examples/julia-raytracer.jl:242-258): per-segment object, distance and direction, bit for bit."""
+    closest-hit loop, examples/julia-raytracer.jl:242-258): per-segment object, distance and direction, bit for bit
+    (spectral transport: the paths of hero wavelengths)."""
     s = scenes.scene_s4()
     ns, nm, nt = _counts(s)
     rng = np.random.default_rng(23)
@@ -104,8 +111,8 @@ def test_config5_full_mesh_geometry_vs_linear_scan(gpu, oracle, prec):
     ij_mesh = np.stack([rng.integers(875, 1046, n * 3 // 4), rng.integers(465, 613, n * 3 // 4)], axis=1)
     ij_any = np.stack([rng.integers(1, W + 1, n - len(ij_mesh)), rng.integers(1, H + 1, n - len(ij_mesh))], axis=1)
     ijs = np.concatenate([np.concatenate([ij_mesh, ij_any]), rng.integers(0, spp, (n, 1))], axis=1).astype(np.uint32)
-    prims, ts, dirs, rad = gpu.trace_paths(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed), ijs, prec)
-    po = oracle.make_params(W, H, spp, depth, ns, nm, nt, seed=seed)
+    prims, ts, dirs, rad = gpu.trace_paths(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=flags), ijs, prec)
+    po = oracle.make_params(W, H, spp, depth, ns, nm, nt, seed=seed, flags=flags)
     tri_hits = 0
     for k in range(n):
         cnt, oprims, ots, odirs, orad = oracle.trace_path(*_args(s), po, int(ijs[k, 0]), int(ijs[k, 1]), int(ijs[k, 2]), prec)
@@ -117,15 +124,16 @@ def test_config5_full_mesh_geometry_vs_linear_scan(gpu, oracle, prec):
     assert tri_hits > 800, tri_hits
 
 
-@pytest.mark.parametrize("prec", ["f32", "f64"])
-def test_config5_slab_matches_oracle_image(gpu, oracle, prec):
+@pytest.mark.parametrize("prec,flags", _C5, ids=_C5_IDS)
+def test_config5_slab_matches_oracle_image(gpu, oracle, prec, flags):
     """An 8-row slab through the 81 920-triangle mesh at 1080p, depth 12 (spp 2: the oracle tests every triangle for every
-    segment, ~5e9 triangle tests), GPU BVH vs the oracle's linear scan: image to tolerance, identical segment count."""
+    segment, ~5e9 triangle tests), GPU BVH vs the oracle's linear scan, without and with spectral transport: image to tolerance,
+    identical segment count."""
     s = scenes.scene_s4()
     ns, nm, nt = _counts(s)
     seed = scenes.seed_for(5)
     tile = dict(row0=536, rows=8)
-    part, _ = gpu.render(*_args(s), gpu.make_params(W, H, 2, 12, ns, nm, nt, seed=seed, **tile), prec)
+    part, _ = gpu.render(*_args(s), gpu.make_params(W, H, 2, 12, ns, nm, nt, seed=seed, flags=flags, **tile), prec)
     seg = gpu.counters()["segments"]
-    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, 2, 12, ns, nm, nt, seed=seed, **tile), prec)
+    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, 2, 12, ns, nm, nt, seed=seed, flags=flags, **tile), prec)
     assert _close(part, ohdr)[0] == 0 and seg == oseg

@@ -77,6 +77,42 @@ def test_fuzz_against_oracle(gpu, oracle):
         assert gpu.counters()["segments"] == oseg, (it, kind, prec, sem)
 
 
+def test_fuzz_k_path_knobs_against_oracle(gpu, oracle):
+    """The scenes and shapes of _case rendered by k_path with its knobs drawn on top: SPIRA_SPEC_DIV (0 off, 1 the predictor's choice, 2 every wave
+    rendered again, 3 forced on), SPIRA_R (1 or 2 rays per lane and sub-chunk), SPIRA_MESH_TWO_PASS and SPIRA_DEFER_MESH (one launch, traversal in
+    place), SPIRA_BLOCKS_PER_CU (1, 3, 32), with or without the extensions — the off-default instantiations of tests/test_gpu_instantiations.py's
+    table at random sizes.  Every case against the oracle; the seed fixes the cases (SPIRA_FUZZ_KNOB_SEED / SPIRA_FUZZ_KNOB_ITERS: one-off campaigns)."""
+    from test_gpu_specdiv import _Env
+    rng = np.random.default_rng(int(os.environ.get("SPIRA_FUZZ_KNOB_SEED", "20261016")))
+    for it in range(int(os.environ.get("SPIRA_FUZZ_KNOB_ITERS", "40"))):
+        kind, s, W, H, spp, depth = _case(rng)
+        ns, nm, nt = _counts(s)
+        prec = "f32" if rng.random() < 0.5 else "f64"
+        ext = 0
+        if rng.random() < 0.3:
+            ext = int(rng.choice([gpu.EXT_DIELECTRIC, gpu.EXT_SPECTRAL, gpu.EXT_DIELECTRIC | gpu.EXT_SPECTRAL]))
+            if ext & gpu.EXT_DIELECTRIC:
+                m = s["materials8"].copy()
+                glass = rng.random(len(m)) < 0.4
+                m[glass, 7] = -rng.uniform(1.05, 2.4, int(glass.sum())).astype(np.float32).astype(np.float64)
+                s = dict(s, materials8=m)
+        env = {"SPIRA_SPEC_DIV": int(rng.integers(0, 4)), "SPIRA_R": int(rng.integers(1, 3)), "SPIRA_MESH_TWO_PASS": int(rng.integers(0, 2)),
+               "SPIRA_DEFER_MESH": int(rng.random() < 0.75), "SPIRA_BLOCKS_PER_CU": int(rng.choice([1, 3, 32]))}
+        seed = int(rng.integers(0, 2 ** 40))
+        batch = int(rng.choice([0, 1, W * H * 2 + 3, 1 << 20]))
+        flags = gpu.KERNEL_WAVEFRONT | ext | gpu.POST_NONE
+        if os.environ.get("SPIRA_FUZZ_LOG"):      # one line per case BEFORE it runs (flushed): which case a crash of the process belongs to
+            with open(os.environ["SPIRA_FUZZ_LOG"], "a") as fh:
+                fh.write("knobs %d %s ns=%d nm=%d nt=%d %dx%d spp=%d depth=%d %s flags=%#x seed=%d batch=%d env=%s\n" % (it, kind, ns, nm, nt, W, H, spp, depth, prec, flags, seed, batch, env))
+        with _Env(**env):
+            hdr, _ = gpu.render(*_args(s), gpu.make_params(W, H, spp, depth, ns, nm, nt, flags=flags, seed=seed, batch_rays=batch), prec)
+            seg = gpu.counters()["segments"]
+        ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, spp, depth, ns, nm, nt, flags=flags, seed=seed), prec)
+        nbad, worst = _close(hdr, ohdr)
+        assert nbad == 0, (it, kind, W, H, spp, depth, prec, ext, env, batch, nbad, worst)
+        assert seg == oseg, (it, kind, prec, ext, env)
+
+
 def test_fuzz_api_sequences(gpu, oracle):
     """Seeded random SEQUENCES of C-ABI calls on one process: resident scene handles (single and multi-device form) created, used through
     every entry that takes one (host outputs, device outputs on a torch stream, the RCCL entry with one device) and destroyed in any order,

@@ -164,33 +164,81 @@ def test_scene_outside_the_window_is_rendered_again_and_matches_the_oracle(gpu, 
     assert _close(b, ohdr)[0] == 0 and oseg == seg
 
 
-@pytest.mark.parametrize("prec", ["f64", "f32"])
-def test_partial_redo(gpu, oracle, prec):
-    """Only SOME waves leave the window: a sphere far outside the ordinary range (radius 3e7 at a distance of 1e9 in Float32, 3e118 at
-    1e120 in Float64) straight ahead of the camera.  b*b of its test is beyond the window, but the fold only happens for rays whose
-    line meets it (:120) — the camera rays of a disc of ~27 pixels radius, and the odd scattered ray.  Forced on (the predictor would
-    decline this scene), the waves that own those rays are rendered again, the others are not; the image is the exact one."""
-    s = scenes.scene_s1()
-    ns, nm, nt = _counts(s)
+def _far_sphere(s, prec):
+    """s with one more sphere far outside the ordinary range straight ahead of its camera (radius 3e7 at 1e9 in Float32, 3e118 at 1e120 in Float64)."""
     cam = s["camera12"].astype(np.float64)
     view = cam[3:6] + 0.5 * cam[6:9] + 0.5 * cam[9:12] - cam[0:3]
     view /= np.linalg.norm(view)
     D, R = (1e9, 3e7) if prec == "f32" else (1e120, 3e118)
     far = cam[0:3] + view * D
-    sp = np.vstack([s["spheres5"].astype(np.float64), [[far[0], far[1], far[2], R, 1.0]]])
-    W, H, spp, depth = 320, 180, 8, 6
-    p = gpu.make_params(W, H, spp, depth, ns + 1, nm, nt, flags=gpu.POST_NONE, seed=9)
-    with _Env(SPIRA_SPEC_DIV=0):
-        ref, _ = gpu.render(sp, s["materials8"], None, s["camera12"], p, prec)
-    with _Env(SPIRA_SPEC_DIV=1):
-        dflt, _ = gpu.render(sp, s["materials8"], None, s["camera12"], p, prec)
-        assert gpu.counters()["redone_waves"] == 0                    # declined by the predictor
-    with _Env(SPIRA_SPEC_DIV=3):
-        got, _ = gpu.render(sp, s["materials8"], None, s["camera12"], p, prec)
-        c = gpu.counters()
+    return dict(s, spheres5=np.vstack([s["spheres5"].astype(np.float64), [[far[0], far[1], far[2], R, 1.0]]]))
+
+
+def _glass_mesh():
+    s = scenes.scene_s4(level=3)
+    s["materials8"] = s["materials8"].copy()
+    s["materials8"][2] = [0.9, 0.95, 1.0, 0, 0, 0, 0.0, -1.45]
+    return s
+
+
+_REDO_CASES = [(sc, pr) for sc in ("s1", "mesh", "mesh_glass") for pr in ("f64", "f32")]
+
+
+@pytest.mark.parametrize("scene,prec", _REDO_CASES, ids=[pr if sc == "s1" else "%s-%s" % (sc, pr) for sc, pr in _REDO_CASES])
+def test_partial_redo(gpu, oracle, scene, prec):
+    """Only SOME waves leave the window: a sphere far outside the ordinary range (radius 3e7 at a distance of 1e9 in Float32, 3e118 at
+    1e120 in Float64) straight ahead of the camera.  b*b of its test is beyond the window, but the fold only happens for rays whose
+    line meets it (:120) — the camera rays of a disc of ~27 pixels radius, and the odd scattered ray.  Forced on (the predictor would
+    decline this scene), the waves that own those rays are rendered again, the others are not; the image is the exact one.
+    The mesh scenes (1 280 triangles through the BVH, without and with glass + spectral transport): the parking waves that are rendered again
+    and those that are not leave their mesh lists to the fat-wave launch together — every mode the same bits, segments and parked rays."""
+    s, flags = {"s1": (scenes.scene_s1(), 0), "mesh": (scenes.scene_s4(level=3), 0),
+                "mesh_glass": (_glass_mesh(), gpu.EXT_DIELECTRIC | gpu.EXT_SPECTRAL)}[scene]
+    s = _far_sphere(s, prec)
+    ns, nm, nt = _counts(s)
+    W, H, spp, depth = (320, 180, 8, 6) if scene == "s1" else (160, 90, 4, 8)
+    p = gpu.make_params(W, H, spp, depth, ns, nm, nt, flags=flags | gpu.POST_NONE, seed=9)
+    got = {}
+    for mode in (0, 1, 2, 3):
+        with _Env(SPIRA_SPEC_DIV=mode):
+            hdr, _ = gpu.render(*_args(s), p, prec)
+            got[mode] = (hdr, gpu.counters())
+    ref, c = got[0][0], got[3][1]
+    for mode in (1, 2, 3):
+        assert np.array_equal(got[mode][0], ref), (scene, prec, mode)
+        for k in ("segments", "rays_parked"):
+            assert got[mode][1][k] == got[0][1][k], (scene, prec, mode, k)
+    assert got[1][1]["redone_waves"] == 0                    # declined by the predictor
+    assert got[2][1]["redone_waves"] > 0
+    assert (got[0][1]["rays_parked"] > 0) == (nt > 0)
     waves = (W * H * spp + 127) // 128
-    print("far sphere, %s: %d of %d waves rendered again" % (prec, c["redone_waves"], waves))
+    print("far sphere, %s %s: %d of %d waves rendered again" % (scene, prec, c["redone_waves"], waves))
     assert 0 < c["redone_waves"] < 0.9 * waves
-    assert np.array_equal(ref, got) and np.array_equal(ref, dflt)
-    ohdr, _, oseg = oracle.render(sp, s["materials8"], None, s["camera12"], oracle.make_params(W, H, spp, depth, ns + 1, nm, nt, seed=9), prec)
-    assert _close(got, ohdr)[0] == 0 and oseg == c["segments"]
+    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(W, H, spp, depth, ns, nm, nt, flags=flags | gpu.POST_NONE, seed=9), prec)
+    assert _close(got[3][0], ohdr)[0] == 0 and oseg == c["segments"]
+
+
+def test_predictor_declines_a_mesh_with_near_zero_coordinates(gpu, oracle):
+    """scene_s4(level=1) holds vertex coordinates of ~1e-18 (rounding left by its 90-degree rotation), below Float32's 2^-20: the predictor turns
+    speculation off for the whole render, as it does for exported meshes full of such noise.  The default path then renders through the exact
+    kernels alone: the launches of SPIRA_SPEC_DIV=0, its bits, and the oracle's image."""
+    s = scenes.scene_s4(level=1)
+    ns, nm, nt = _counts(s)
+    t = np.abs(s["triangles10"][:, :9].astype(np.float32))
+    assert 0 < t[t > 0].min() < 2.0 ** -20
+    p = gpu.make_params(160, 90, 4, 8, ns, nm, nt, flags=gpu.POST_NONE, seed=13)
+    with _Env(SPIRA_SPEC_DIV=0):
+        ref, _ = gpu.render(*_args(s), p, "f32")
+        c0 = gpu.counters()
+    dflt, _ = gpu.render(*_args(s), p, "f32")
+    c1 = gpu.counters()
+    with _Env(SPIRA_SPEC_DIV=3):
+        forced, _ = gpu.render(*_args(s), p, "f32")
+        c3 = gpu.counters()
+    assert np.array_equal(dflt, ref) and np.array_equal(forced, ref)
+    assert c1["launches"] == c0["launches"] and c1["redone_waves"] == 0
+    assert c3["launches"] == c0["launches"] + c0["passes"]          # (forced on: the speculative launch is made)
+    for k in ("segments", "rays_parked"):
+        assert c1[k] == c0[k] == c3[k], k
+    ohdr, _, oseg = oracle.render(*_args(s), oracle.make_params(160, 90, 4, 8, ns, nm, nt, seed=13), "f32")
+    assert _close(ref, ohdr)[0] == 0 and oseg == c0["segments"]
