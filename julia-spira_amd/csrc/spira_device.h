@@ -1442,7 +1442,7 @@ template <class T> struct PathArgs {
     uint32_t *qref[2];               // Float32 only: the hit reference of each queued packet (Float64 packs it beside q)
     uint2 *qkey[2];                  // sphere scenes without extensions: the path's half-made RNG key beside each packet (k_path, kCarry)
     uint32_t cam_consts;             // the launch's LDS block has room for one packet per sphere behind the camera: the camera rays' share of a sphere test (closest_hit_local, CAM)
-    Pack3<T> *L;                     // per-path radiance of the pass batch (slot-major)
+    Pack3<T> *L;                     // per-path radiance of the pass batch (slot-major; pixel-owning passes with l_private: one block per wave, below)
     uint32_t *blk_stats;             // [NW][4] segments, radiance RMWs, radiance stores, packets enqueued
     uint32_t cap;                    // region size in packets (a multiple of R*64)
     uint32_t pass;
@@ -1473,6 +1473,13 @@ template <class T> struct PathArgs {
     FastDiv fd_keff;
     uint32_t k_eff;                  // slots of this pass (n_first / tile_pixels)
     uint32_t accum_first;            // the first pass of a fresh render: the sums start at 0
+    // Nobody but the owning wave touches the radiance of its paths, so (l_private) wave w keeps the radiance of its path e at L[w * 64 k_eff + e]: a run's
+    // RUN x k_eff entries are one contiguous block (6 KB at 64 slots in Float64), a full row's store RUN x 64 / RUN x 24 = 1 536 contiguous bytes, and
+    // eight consecutive slots of the end-of-wave sum 768 contiguous bytes per run — in the slot-major layout every one of them is a piece of RUN entries
+    // on its own slot plane (tile_pixels entries apart), whole 128-byte lines fetched and written for 96 bytes used.  The queue word q of the path is
+    // then w * 64 k_eff + e instead of the path index: the carried RNG key stands in for that (kCarry, max_depth <= 128 — the host sets the flag only
+    // there; 0: slot-major).  L then holds 64 NW k_eff <= 2^31 entries (>= n_first: the last wave's pixels past the tile's end have entries nobody touches).
+    uint32_t l_private;
 };
 
 // Pixel-owning passes: lane l of wave w owns pixel ((l / RUN) * nw + w) * RUN + l % RUN — 64 / RUN runs of RUN adjacent pixels, nw * RUN pixels
@@ -1504,6 +1511,26 @@ __device__ __forceinline__ void resolve_pixel(Pack4<T> *accum, const Pack3<T> *L
     }
     for (; s < k_eff; ++s) {
         const Pack3<T> l = L[(size_t)s * tile_pixels + p];
+        acc.x = acc.x + l.x; acc.y = acc.y + l.y; acc.z = acc.z + l.z;
+    }
+    accum[p] = acc;
+}
+// The same for a pixel-owning wave's private block (PathArgs::l_private): `Lp` points at slot 0 of the lane's pixel, the slots follow RUN entries apart.
+template <class T>
+__device__ __forceinline__ void resolve_pixel_run(Pack4<T> *accum, const Pack3<T> *Lp, uint32_t k_eff, bool first_pass, uint32_t p) {
+    constexpr uint32_t kRun = SPIRA_RESOLVE_RUN;
+    Pack4<T> acc;
+    if (first_pass) { acc.x = 0; acc.y = 0; acc.z = 0; acc.w = 0; } else acc = accum[p];
+    uint32_t s = 0;
+    for (; s + 8 <= k_eff; s += 8) {
+        Pack3<T> l[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) l[k] = Lp[(s + k) * kRun];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { acc.x = acc.x + l[k].x; acc.y = acc.y + l[k].y; acc.z = acc.z + l[k].z; }
+    }
+    for (; s < k_eff; ++s) {
+        const Pack3<T> l = Lp[s * kRun];
         acc.x = acc.x + l.x; acc.y = acc.y + l.y; acc.z = acc.z + l.z;
     }
     accum[p] = acc;
@@ -1611,6 +1638,9 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     const bool own = !BVH && !EXT && !TRI && sizeof(T) == 8 && a.accum != nullptr;      // a pixel-owning pass (PathArgs::accum)
     const uint32_t n_own = own ? 64u * a.k_eff : 0u;             // its paths of this wave
     const uint32_t n_sub_first = own ? (n_own + SUB - 1) / SUB : (a.n_first + SUB - 1) / SUB;
+    // the wave's radiance in a block of its own (PathArgs::l_private): the queue word of path e of the wave is l_base + e instead of the path index
+    const bool priv = kCarry && own && a.l_private != 0;
+    const uint32_t l_base = priv ? wid * n_own : 0u;
 
     // park a ray on the wave's mesh list (entry = 3 packets: {o, d.x} {d.y, d.z, beta.xy} {beta.z, closest so far, q, object so far + stage of the hit})
     auto park = [&](uint32_t slot_i, const Vec<T> o_, const Vec<T> d_, const Vec<T> beta_, T closest_, uint32_t q_, int prim_, uint32_t stage_hit) {
@@ -1675,11 +1705,12 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                     qf = (t - run * a.k_eff) * rc.tile_pixels + px;
                     in = in && px < rc.tile_pixels;
                 }
+                const uint32_t ql = priv ? l_base + idx : qf;              // where the path's radiance lives: what the queue word carries
                 if (in) {
                     if (first) {
                         uint32_t pixel, sample, pi, pj;
                         Vec<T> d;
-                        q[r] = qf;
+                        q[r] = ql;
                         path_of<T>(rc, qf, a.pass, pi, pj, pixel, sample);
                         if (kCarry) { ka[r] = mix32(rc.sA + pixel) ^ (sample << 8); kb[r] = mix32(rc.sB ^ pixel) + (sample << 8); }
                         camera_ray_lds<T>(rc, cam_lds, pix_div, pi, pj, pixel, sample, o[r], d, pol);
@@ -1697,7 +1728,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                         else if (prim < 0) {                      // the camera ray leaves the scene: sky, :365-366
                             const Vec<T> c = sky_term_x<T, EXT>(d, beta[r], &ex[r]);
                             Pack3<T> l; l.x = c.x; l.y = c.y; l.z = c.z;
-                            a.L[qf] = l;
+                            a.L[ql] = l;
                             ++n_store;
                         } else {
                             valid[r] = true;
@@ -2126,7 +2157,10 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         const uint32_t px = owned_pixel(wid, NW, lane);
-        if (px < rc.tile_pixels) resolve_pixel<T>(a.accum, a.L, rc.tile_pixels, a.k_eff, a.accum_first != 0, px);
+        if (px < rc.tile_pixels) {
+            if (priv) resolve_pixel_run<T>(a.accum, a.L + l_base + (lane / SPIRA_RESOLVE_RUN) * a.k_eff * SPIRA_RESOLVE_RUN + lane % SPIRA_RESOLVE_RUN, a.k_eff, a.accum_first != 0, px);
+            else resolve_pixel<T>(a.accum, a.L, rc.tile_pixels, a.k_eff, a.accum_first != 0, px);
+        }
         // k_resolve's fold of the statistics rows, one wave instruction: lane i adds counter i (Stats' first four fields)
         const uint32_t seg = __shfl(n_seg, 0), rmw = __shfl(n_rmw, 0), sto = __shfl(n_store, 0);
         if (lane < 4) {

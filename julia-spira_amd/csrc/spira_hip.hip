@@ -623,7 +623,7 @@ int check_handle(const spira_scene *h) {
 struct PathPlan {
     uint64_t waves = 0;        // NW of the largest pass (G_max * waves per workgroup)
     uint64_t packets = 0;      // NW * cap of the largest pass: entries of every per-packet array (worst case: every path queued / parked once)
-    uint64_t batch = 0;        // paths of the largest pass (entries of L)
+    uint64_t batch = 0;        // entries of L: the paths of the largest pass; pixel-owning passes with wave-private radiance blocks (PathArgs::l_private): 64 * slots per wave
     bool queues = false;       // hit queues: max_depth > 1, or a mesh scene (a parked camera ray's hit comes back from its session as a packet)
     bool mesh = false;         // mesh lists (deferred traversal)
     bool two_pass = false;     // per-wave parked counts handed from the parking launch to the fat-wave launch
@@ -668,7 +668,9 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
         bad = "parked-ray counts of a two-launch mesh pass";
     if (!bad && a.redo && !covers(c.redo, a.redo, nw * sizeof(uint32_t))) bad = "redo flags";
     if (!bad && !covers(c.blkstats, a.blk_stats, nw * 4 * sizeof(uint32_t))) bad = "per-wave statistics";
-    if (!bad && !covers(c.L, a.L, (uint64_t)a.n_first * sizeof(spira::Pack3<T>))) bad = "per-path radiance";
+    // (wave-private radiance blocks: 64 k_eff entries for every wave of the grid, more than n_first when the tile's pixel count is no multiple of 64 * waves per workgroup)
+    const uint64_t l_entries = a.l_private ? std::max<uint64_t>(a.n_first, 64ull * nw * a.k_eff) : a.n_first;
+    if (!bad && !covers(c.L, a.L, l_entries * sizeof(spira::Pack3<T>))) bad = "per-path radiance";
     if (!bad && !covers(c.stats, a.stats, sizeof(spira::Stats))) bad = "counters";
     if (!bad && a.accum) {                  // pixel-owning pass: an instantiation that resolves, a wave for every pixel, every wave's paths in its region
         const uint64_t tp = a.rc.tile_pixels;
@@ -676,6 +678,8 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
             a.k_eff == 0 || a.k_eff > 64 || (uint64_t)a.k_eff * tp != a.n_first || 64 * nw < tp || a.cap < 64ull * a.k_eff)
             bad = "pixel-owning pass";
     }
+    // wave-private radiance blocks: pixel-owning passes whose queue word need not be the path index (the RNG key is carried: max_depth <= 128)
+    if (!bad && a.l_private && (!a.accum || !SPIRA_CARRY_KEY || a.rc.max_depth > 128 || l_entries > 0x80000000ull)) bad = "wave-private radiance blocks";
     if (bad) return fail(SPIRA_E_LIMIT, std::string("internal: a workspace is smaller than the launch needs (") + bad + ")");
     return 0;
 }
@@ -762,8 +766,13 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
         const uint64_t nw = (uint64_t)G * wpb;
         cap = (uint32_t)(((n_sub + nw - 1) / nw) * sub);
     };
+    // ... and keep the radiance of their paths in one contiguous block per wave (PathArgs::l_private) wherever the queue word is free to address it: the
+    // RNG key is carried through the queue for max_depth <= 128 (deeper renders derive it from the path index and keep the slot-major L).
+    // SPIRA_PRIVATE_L=0: the slot-major layout (A/B).
+    const bool l_private_wanted = fused && SPIRA_CARRY_KEY && p->max_depth <= 128 && env_u32("SPIRA_PRIVATE_L", 1) != 0;
     uint32_t G_max = 0, cap_max = 0;
     geometry(batch, G_max, cap_max);
+    const bool l_private = l_private_wanted && 64ull * G_max * (spira::kBlock / 64) * slots <= 0x7FFFFFFFull;      // (the queue word has 31 bits for the entry of L)
     const uint64_t q_rays = (uint64_t)cap_max * G_max * wpb;
     if (q_rays > 0xFFFFFFFFull) return fail(SPIRA_E_LIMIT, "pass too large");
 
@@ -774,7 +783,8 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     const bool defer_mesh = persistent && mesh_scene && p->max_depth <= 128 && env_u32("SPIRA_DEFER_MESH", 1) != 0;
     // speculative division (spira_device.h, SpecDiv): decided here once, because it needs a workspace (the per-wave redo flags) — see the launch below
     PathPlan plan;
-    plan.waves = (uint64_t)G_max * wpb; plan.packets = q_rays; plan.batch = batch;
+    plan.waves = (uint64_t)G_max * wpb; plan.packets = q_rays;
+    plan.batch = l_private ? std::max<uint64_t>(batch, 64ull * G_max * wpb * slots) : batch;      // (a pixel-owning grid depends on the pixel count alone: G_max waves in every pass)
     // (max_depth == 1 needs no queue — except on a mesh scene of the persistent organisation: a parked camera ray's hit comes back from its
     //  traversal session as a packet.)
     plan.queues = !mega && (p->max_depth > 1 || (persistent && mesh_scene));
@@ -1017,6 +1027,7 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
                 if (fused) {
                     pa.accum = (P4 *)c.accum.p; pa.k_eff = k_eff; pa.fd_keff = spira::fastdiv_make(k_eff);
                     pa.accum_first = (pass == 0 && !progressive) ? 1u : 0u;
+                    pa.l_private = l_private ? 1u : 0u;
                 }
                 if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
                 HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
