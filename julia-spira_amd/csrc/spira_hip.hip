@@ -7,6 +7,9 @@
 // (mesh scenes: a parking launch + a fat-wave launch; SPIRA_KERNEL_BOUNCE: max_depth bounce kernels)
 // + 1 resolve kernel, fully asynchronous on one HIP stream, the live-ray counts staying on the
 // device, and a pass carries `slots` samples of every pixel of the tile at once.
+// What a call launches and how large its workspaces are is decided in spira_plan.h (make_plan: pure arithmetic, swept on the CPU under sanitizers);
+// here render_impl<T> validates, plans, sizes the workspaces from the plan and calls the organisation's enqueue_* function, and verify_path_args
+// checks every k_path launch against the buffers actually allocated.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <rccl/rccl.h>      // types and prototypes only: librccl is opened at run time (dlopen), never linked
@@ -31,6 +34,7 @@
 #include "spira_device.h"
 #include "spira_bvh.h"
 #include "spira_validate.h"
+#include "spira_plan.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -518,6 +522,58 @@ void prefault_destination(char *p, size_t n) {
     if (b > a) (void)madvise((void *)a, b - a, 23 /* MADV_POPULATE_WRITE (Linux 5.14) */);
 }
 
+// The context's pinned staging buffer, grown to `total` bytes.  false: no pinned memory to be had — the caller's plain path still works.
+bool stage_reserve(Ctx &c, size_t total) {
+    if (c.h_stage_cap >= total) return true;
+    if (c.h_stage) { (void)hipHostFree(c.h_stage); c.h_stage = nullptr; c.h_stage_cap = 0; }
+    if (hipHostMalloc(&c.h_stage, total, hipHostMallocDefault) == hipSuccess) { c.h_stage_cap = total; return true; }
+    c.h_stage = nullptr; (void)hipGetLastError();
+    return false;
+}
+
+// Device memory on its way to a host-pointer caller through the pinned staging buffer: stage() enqueues one piece (device -> staging, and an event
+// behind it), move() has SPIRA_STAGE_THREADS host threads (4) carry the pieces on into the caller's memory as their events complete.
+struct StagedCopy {
+    struct Piece { char *dst; size_t off, len; };
+    Ctx &c;
+    std::vector<Piece> pieces;
+    size_t off = 0;
+    explicit StagedCopy(Ctx &ctx) : c(ctx) {}
+    hipError_t stage(hipStream_t st, void *dst, const void *src, size_t len) {
+        hipError_t e = hipMemcpyAsync((char *)c.h_stage + off, src, len, hipMemcpyDeviceToHost, st);
+        if (e != hipSuccess) return e;
+        if (c.stage_ev.size() <= pieces.size()) {
+            hipEvent_t ev;
+            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
+            c.stage_ev.push_back(ev);
+        }
+        e = hipEventRecord(c.stage_ev[pieces.size()], st);
+        pieces.push_back({(char *)dst, off, len});
+        off += len;
+        return e;
+    }
+    hipError_t move() {
+        const int n_thr = (int)std::min<size_t>(std::max<uint32_t>(1, env_u32("SPIRA_STAGE_THREADS", 4)), pieces.size());
+        std::vector<hipError_t> errs((size_t)n_thr, hipSuccess);
+        const bool prefault = env_u32("SPIRA_PREFAULT", 1) != 0;
+        auto mover = [&](int t) {
+            (void)hipSetDevice(c.device);
+            if (prefault) for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) prefault_destination(pieces[i].dst, pieces[i].len);
+            for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) {
+                const hipError_t e = hipEventSynchronize(c.stage_ev[i]);
+                if (e != hipSuccess) { errs[(size_t)t] = e; return; }
+                std::memcpy(pieces[i].dst, (const char *)c.h_stage + pieces[i].off, pieces[i].len);
+            }
+        };
+        std::vector<std::thread> thr;
+        for (int t = 1; t < n_thr; ++t) thr.emplace_back(mover, t);
+        mover(0);
+        for (auto &t : thr) t.join();
+        for (hipError_t e : errs) if (e != hipSuccess) return e;
+        return hipSuccess;
+    }
+};
+
 // A frame for a host-pointer caller (`render` of either reference surface returns a host array).  hipMemcpy into pageable memory runs at
 // ~9 GB/s on this box (the runtime stages it on one thread): 5.7 ms for a 1080p Float64 frame, as long as rendering it.  Instead: device ->
 // pinned staging in 8 MB chunks (one event each), and four host threads move the chunks on into the caller's memory as they arrive: 4.3 ms
@@ -528,51 +584,16 @@ int copy_out(Ctx &c, hipStream_t st, void *const dst[2], const void *const src[2
     const int n_out = (dst[0] ? 1 : 0) + (dst[1] ? 1 : 0);
     if (!n_out) return 0;
     const size_t total = bytes_each * (size_t)n_out;
-    bool staged = bytes_each >= kMinStaged && total <= kMaxStaged;
-    if (staged && c.h_stage_cap < total) {
-        if (c.h_stage) { (void)hipHostFree(c.h_stage); c.h_stage = nullptr; c.h_stage_cap = 0; }
-        if (hipHostMalloc(&c.h_stage, total, hipHostMallocDefault) == hipSuccess) c.h_stage_cap = total;
-        else { c.h_stage = nullptr; (void)hipGetLastError(); staged = false; }      // no pinned memory to be had: the plain copy still works
-    }
-    if (!staged) {
+    if (bytes_each < kMinStaged || total > kMaxStaged || !stage_reserve(c, total)) {
         for (int k = 0; k < 2; ++k) if (dst[k]) HIP_TRY(hipMemcpyAsync(dst[k], src[k], bytes_each, hipMemcpyDeviceToHost, st));
         return 0;
     }
-    struct Piece { char *dst; size_t off, len; };
-    std::vector<Piece> pieces;
-    size_t off = 0;
-    for (int k = 0; k < 2; ++k) {
-        if (!dst[k]) continue;
-        for (size_t o = 0; o < bytes_each; o += kChunk) {
-            const size_t len = std::min(kChunk, bytes_each - o);
-            HIP_TRY(hipMemcpyAsync((char *)c.h_stage + off, (const char *)src[k] + o, len, hipMemcpyDeviceToHost, st));
-            if (c.stage_ev.size() <= pieces.size()) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                c.stage_ev.push_back(e);
-            }
-            HIP_TRY(hipEventRecord(c.stage_ev[pieces.size()], st));
-            pieces.push_back({(char *)dst[k] + o, off, len});
-            off += len;
-        }
-    }
-    const int n_thr = (int)std::min<size_t>(std::max<uint32_t>(1, env_u32("SPIRA_STAGE_THREADS", 4)), pieces.size());
-    std::vector<hipError_t> errs((size_t)n_thr, hipSuccess);
-    const bool prefault = env_u32("SPIRA_PREFAULT", 1) != 0;
-    auto mover = [&](int t) {
-        (void)hipSetDevice(c.device);
-        if (prefault) for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) prefault_destination(pieces[i].dst, pieces[i].len);
-        for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) {
-            const hipError_t e = hipEventSynchronize(c.stage_ev[i]);
-            if (e != hipSuccess) { errs[(size_t)t] = e; return; }
-            std::memcpy(pieces[i].dst, (const char *)c.h_stage + pieces[i].off, pieces[i].len);
-        }
-    };
-    std::vector<std::thread> thr;
-    for (int t = 1; t < n_thr; ++t) thr.emplace_back(mover, t);
-    mover(0);
-    for (auto &t : thr) t.join();
-    for (hipError_t e : errs) if (e != hipSuccess) return fail(SPIRA_E_HIP, std::string("copy_out: ") + hipGetErrorString(e));
+    StagedCopy sc(c);
+    for (int k = 0; k < 2; ++k)
+        for (size_t o = 0; dst[k] && o < bytes_each; o += kChunk)
+            HIP_TRY(sc.stage(st, (char *)dst[k] + o, (const char *)src[k] + o, std::min(kChunk, bytes_each - o)));
+    const hipError_t e = sc.move();
+    if (e != hipSuccess) return fail(SPIRA_E_HIP, std::string("copy_out: ") + hipGetErrorString(e));
     return 0;
 }
 
@@ -615,95 +636,361 @@ int check_handle(const spira_scene *h) {
     return 0;
 }
 
-// ---- workspaces of the persistent organisation, sized and checked in ONE place.
-// PathPlan says what the passes of a call may touch (derived from the launch geometry); ensure_path_plan() sizes every buffer a launch can be handed;
-// verify_path_args() — called right before every k_path launch — checks each pointer of PathArgs against the capacity of the buffer it points into for
-// the grid about to be launched, and refuses the launch (SPIRA_E_LIMIT) instead of letting a kernel write past a buffer nobody sized.  (Round 3's
-// fuzz found exactly that: a depth-1 mesh render writing parked rays' hits into queues only `max_depth > 1` used to size.)
-struct PathPlan {
-    uint64_t waves = 0;        // NW of the largest pass (G_max * waves per workgroup)
-    uint64_t packets = 0;      // NW * cap of the largest pass: entries of every per-packet array (worst case: every path queued / parked once)
-    uint64_t batch = 0;        // entries of L: the paths of the largest pass; pixel-owning passes with wave-private radiance blocks (PathArgs::l_private): 64 * slots per wave
-    bool queues = false;       // hit queues: max_depth > 1, or a mesh scene (a parked camera ray's hit comes back from its session as a packet)
-    bool mesh = false;         // mesh lists (deferred traversal)
-    bool two_pass = false;     // per-wave parked counts handed from the parking launch to the fat-wave launch
-    bool spec = false;         // per-wave redo flags of the speculative-division launch
-};
-template <class T>
-int ensure_path_plan(Ctx &c, const PathPlan &pl) {
-    using P4 = spira::Pack4<T>;
-    using P2 = spira::Pack2<T>;
-    if (pl.queues)
-        for (int i = 0; i < 2; ++i) {
-            if (int rc = c.qA[i].ensure(pl.packets * sizeof(P4))) return rc;
-            if (int rc = c.qB[i].ensure(pl.packets * sizeof(P4))) return rc;
-            if (int rc = c.qC[i].ensure(pl.packets * sizeof(P2))) return rc;
-            if (sizeof(T) == 4) { if (int rc = c.qR[i].ensure(pl.packets * sizeof(uint32_t))) return rc; }
-            if (!pl.mesh) { if (int rc = c.qK[i].ensure(pl.packets * sizeof(uint2))) return rc; }      // carried RNG keys (sphere scenes; the extension launches leave them unused)
-        }
-    if (pl.mesh) { if (int rc = c.mesh_list.ensure(3 * pl.packets * sizeof(P4))) return rc; }
-    if (pl.two_pass) { if (int rc = c.mesh_count.ensure(pl.waves * sizeof(uint32_t))) return rc; }
-    if (pl.spec) { if (int rc = c.redo.ensure(pl.waves * sizeof(uint32_t))) return rc; }
-    if (int rc = c.blkstats.ensure(pl.waves * 4 * sizeof(uint32_t))) return rc;
-    if (int rc = c.L.ensure(pl.batch * sizeof(spira::Pack3<T>))) return rc;
-    return c.stats.ensure(sizeof(spira::Stats));
+// ---- the launch plan of a call (spira_plan.h): what spira_device.h and the environment contribute to it
+spira::Knobs read_knobs() {
+    spira::Knobs k;
+    k.batch_rays = env_u32("SPIRA_BATCH_RAYS", k.batch_rays);
+    k.R = env_u32("SPIRA_R", k.R);
+    k.blocks_per_cu = env_u32("SPIRA_BLOCKS_PER_CU", 0);
+    k.defer_mesh = env_u32("SPIRA_DEFER_MESH", 1); k.mesh_two_pass = env_u32("SPIRA_MESH_TWO_PASS", 1);
+    k.fused_resolve = env_u32("SPIRA_FUSED_RESOLVE", 1); k.private_l = env_u32("SPIRA_PRIVATE_L", 1);
+    k.spec_div = env_u32("SPIRA_SPEC_DIV", 1);
+    // dense continuation threshold (same device, S1 1080p spp 64 depth 8, Msamples/s): f64 100 %: 20 218, 90: 20 563, 80: 20 953,
+    // 70: 20 963, 60: 20 052; f32 90: 30 222, 80: 30 141, 70: 29 567, 60: 28 354 — a packet costs twice the bytes in Float64, so it
+    // pays to keep a little more in registers there.  On the closed box S3 any threshold > 0 gives the full +22 % (f64).
+    // Round 4 (packets carry the RNG key words: a queued hit costs more), S1 ms per frame, two rounds on one box: f64 80: 5.302 / 5.277, 75: 5.245 / 5.229,
+    // 70: 5.221 / 5.240, 65: 5.272 / 5.299; f32 80: 3.382 / 3.414, 75: 3.341 / 3.354, 70: 3.340 / 3.351, 65: 3.374 / 3.351; configs[4] the same at 70 and 80.
+    k.dense_pct = std::min<uint32_t>(env_u32("SPIRA_DENSE_PCT", 70), 100);      // (Float32 re-measured on the no-SLP build of round 3, S1: 90: 37 900, 85: 38 500, 80: 38 500, 75: 38 500, 70: 37 500)
+    k.mesh_min_batch = std::max<uint32_t>(1, env_u32("SPIRA_MESH_MIN_BATCH", 128));
+    k.mesh_refill = std::min<uint32_t>(64, std::max<uint32_t>(1, env_u32("SPIRA_MESH_REFILL", 16)));
+    k.mesh_fat_waves_per_cu = env_u32("SPIRA_MESH_FAT_WAVES_PER_CU", 16);
+    k.cam_consts = env_u32("SPIRA_CAM_CONSTS", 1);
+    return k;
 }
+template <class T>
+spira::PlanIn plan_input(const Ctx &c, const spira_params *p, uint32_t rows, uint32_t nt_scene, bool progressive, bool caller_rng, bool out_on_device) {
+    spira::PlanIn in;
+    in.width = p->width; in.rows = rows; in.spp = p->spp; in.max_depth = p->max_depth; in.flags = p->flags; in.batch_rays = p->batch_rays;
+    in.n_triangles = nt_scene; in.num_cus = (uint32_t)c.num_cus;
+    in.progressive = progressive; in.caller_rng = caller_rng; in.out_on_device = out_on_device;
+    in.prec = sizeof(T); in.block = spira::kBlock; in.waves_per_simd = SPIRA_WAVES_PER_SIMD(T); in.carry_key = SPIRA_CARRY_KEY;
+    in.pack4 = sizeof(spira::Pack4<T>); in.pack3 = sizeof(spira::Pack3<T>); in.pack2 = sizeof(spira::Pack2<T>);
+    in.k = read_knobs();
+    return in;
+}
+
+// Every workspace of the context at the size the plan gives it: the one place that sizes them.
+int ensure_workspaces(Ctx &c, const spira::Workspace &w) {
+    for (int i = 0; i < 2; ++i) {
+        if (int rc = c.qA[i].ensure(w.queue4)) return rc;
+        if (int rc = c.qB[i].ensure(w.queue4)) return rc;
+        if (int rc = c.qC[i].ensure(w.queue2)) return rc;
+        if (int rc = c.qR[i].ensure(w.q_ref)) return rc;
+        if (int rc = c.qK[i].ensure(w.q_key)) return rc;
+        if (int rc = c.qX[i].ensure(w.q_x)) return rc;
+    }
+    const struct { DevBuf &b; uint64_t bytes; } rest[] = {
+        {c.mesh_list, w.mesh_list}, {c.mesh_count, w.mesh_count}, {c.redo, w.redo}, {c.blkstats, w.blkstats}, {c.L, w.L}, {c.counts, w.counts},
+        {c.stats, sizeof(spira::Stats)}, {c.accum, w.accum}, {c.out_tmp, w.out_tmp}, {c.rng, w.rng},
+        {c.hyb_state, w.hyb_state}, {c.hyb_mat, w.hyb_mat}, {c.hyb_flags, w.hyb_flags}};
+    for (const auto &r : rest)
+        if (int rc = r.b.ensure(r.bytes)) return rc;
+    return 0;
+}
+
+// Called right before every k_path launch: each pointer of PathArgs against the capacity of the buffer it points into, for the grid about to be
+// launched (spira_plan.h, path_need); a launch that would not fit is refused (SPIRA_E_LIMIT) instead of letting a kernel write past a buffer nobody
+// sized.  (Round 3's fuzz found exactly that: a depth-1 mesh render writing parked rays' hits into queues only `max_depth > 1` used to size.)
 template <class T>
 int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_launch_blocks) {
     using P4 = spira::Pack4<T>;
     using P2 = spira::Pack2<T>;
-    const uint64_t nw = (uint64_t)first_launch_blocks * (spira::kBlock / 64), n = nw * a.cap;      // (a fat wave of the second launch owns the regions of the waves it takes over: the same n)
+    spira::PathLaunch l;
+    l.blocks = first_launch_blocks; l.cap = a.cap; l.n_first = a.n_first; l.k_eff = a.k_eff;
+    l.tile_pixels = a.rc.tile_pixels; l.max_depth = a.rc.max_depth; l.flags = a.rc.flags; l.n_lds_triangles = a.scene.n_triangles;
+    l.mesh_mode = a.mesh_mode; l.resume_k = a.resume_k; l.resume_nw = a.resume_nw;
+    l.mesh = a.scene.n_bvh_tris != 0; l.pixel_owning = a.accum != nullptr; l.l_private = a.l_private != 0;
+    l.prec = sizeof(T); l.wpb = spira::kBlock / 64; l.carry_key = SPIRA_CARRY_KEY;
+    const spira::PathNeed need = spira::path_need(l);
+    const uint64_t nw = need.nw, n = need.packets;
     auto covers = [](const DevBuf &b, const void *ptr, uint64_t bytes) { return ptr == b.p && b.p != nullptr && b.cap >= bytes; };
-    const char *bad = nullptr;
-    const bool mesh = a.scene.n_bvh_tris != 0;
-    if ((uint64_t)a.n_first > n) bad = "the pass does not fit its queue regions";
-    if (a.rc.max_depth > 1 || mesh)
+    const char *bad = need.fits ? nullptr : "the pass does not fit its queue regions";
+    if (a.rc.max_depth > 1 || l.mesh)
         for (int i = 0; i < 2 && !bad; ++i) {
             if (!covers(c.qA[i], a.q[i].A, n * sizeof(P4)) || !covers(c.qB[i], a.q[i].B, n * sizeof(P4)) || !covers(c.qC[i], a.q[i].C, n * sizeof(P2))) bad = "hit queues";
             else if (sizeof(T) == 4 && !covers(c.qR[i], a.qref[i], n * sizeof(uint32_t))) bad = "hit reference arrays";
-            else if (!mesh && !covers(c.qK[i], a.qkey[i], n * sizeof(uint2))) bad = "carried RNG keys";
+            else if (!l.mesh && !covers(c.qK[i], a.qkey[i], n * sizeof(uint2))) bad = "carried RNG keys";
         }
     if (!bad && a.mesh_list && !covers(c.mesh_list, a.mesh_list, 3 * n * sizeof(P4))) bad = "mesh lists";
-    if (!bad && a.mesh_mode != 0 && (!a.mesh_list || !covers(c.mesh_count, a.mesh_count, nw * sizeof(uint32_t)) || a.resume_k == 0 || a.resume_k > 16 || nw % a.resume_k != 0 || a.resume_nw != nw))
-        bad = "parked-ray counts of a two-launch mesh pass";
+    if (!bad && a.mesh_mode != 0 && (!a.mesh_list || !covers(c.mesh_count, a.mesh_count, nw * sizeof(uint32_t)) || !need.resume_ok)) bad = "parked-ray counts of a two-launch mesh pass";
     if (!bad && a.redo && !covers(c.redo, a.redo, nw * sizeof(uint32_t))) bad = "redo flags";
     if (!bad && !covers(c.blkstats, a.blk_stats, nw * 4 * sizeof(uint32_t))) bad = "per-wave statistics";
-    // (wave-private radiance blocks: 64 k_eff entries for every wave of the grid, more than n_first when the tile's pixel count is no multiple of 64 * waves per workgroup)
-    const uint64_t l_entries = a.l_private ? std::max<uint64_t>(a.n_first, 64ull * nw * a.k_eff) : a.n_first;
-    if (!bad && !covers(c.L, a.L, l_entries * sizeof(spira::Pack3<T>))) bad = "per-path radiance";
+    if (!bad && !covers(c.L, a.L, need.l_entries * sizeof(spira::Pack3<T>))) bad = "per-path radiance";
     if (!bad && !covers(c.stats, a.stats, sizeof(spira::Stats))) bad = "counters";
-    if (!bad && a.accum) {                  // pixel-owning pass: an instantiation that resolves, a wave for every pixel, every wave's paths in its region
-        const uint64_t tp = a.rc.tile_pixels;
-        if (!covers(c.accum, a.accum, tp * sizeof(spira::Pack4<T>)) || sizeof(T) != 8 || a.scene.n_triangles || mesh || (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) ||
-            a.k_eff == 0 || a.k_eff > 64 || (uint64_t)a.k_eff * tp != a.n_first || 64 * nw < tp || a.cap < 64ull * a.k_eff)
-            bad = "pixel-owning pass";
-    }
-    // wave-private radiance blocks: pixel-owning passes whose queue word need not be the path index (the RNG key is carried: max_depth <= 128)
-    if (!bad && a.l_private && (!a.accum || !SPIRA_CARRY_KEY || a.rc.max_depth > 128 || l_entries > 0x80000000ull)) bad = "wave-private radiance blocks";
+    if (!bad && a.accum && (!covers(c.accum, a.accum, (uint64_t)a.rc.tile_pixels * sizeof(P4)) || !need.owning_ok)) bad = "pixel-owning pass";
+    if (!bad && a.l_private && !need.private_ok) bad = "wave-private radiance blocks";
     if (bad) return fail(SPIRA_E_LIMIT, std::string("internal: a workspace is smaller than the launch needs (") + bad + ")");
     return 0;
 }
 
+// Everything but the scene check of a render call's arguments, in the order the errors are documented in.  `rows`: of the tile.
+template <class T>
+int validate_call(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                  const T *out_hdr, const T *out_img, bool progressive, uint32_t sample0, const uint32_t *rng_states, uint32_t *rows) {
+    if (!p) return fail(SPIRA_E_INVALID, "params is NULL");
+    const uint32_t nt = triangles10 ? p->n_triangles : 0;
+    if (h) { if (int rc = check_handle<T>(h)) return rc; }
+    else if (int rc = validate_scene<T>(spheres5, materials8, triangles10, p->n_spheres, p->n_materials, nt)) return rc;
+    if (int rc = validate_params(camera12, p, h ? h->store.nt : nt, rows)) return rc;
+    if (!out_hdr && !out_img) return fail(SPIRA_E_INVALID, "both outputs are NULL");
+    const char *msg = nullptr;
+    if (int rc = spira::sample_range_check(progressive, sample0, p->spp, &msg)) return fail(rc, msg);
+    if (progressive && (p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_HYBRID) return fail(SPIRA_E_UNSUPPORTED, "SPIRA_SEM_HYBRID has no accumulate entry (its image is a mean of tone-mapped samples)");
+    if (progressive && (p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_METAL && sample0 > 0 && !rng_states)
+        return fail(SPIRA_E_INVALID, "SPIRA_SEM_METAL with sample0 > 0 needs rng_states (the LCG states the previous call left); "
+                                     "without them every call would replay the samples of the first");
+    return 0;
+}
+
+// ---- one enqueue function per kernel organisation.  A call's state, as they all see it:
+template <class T> struct Call {
+    Ctx &c;
+    hipStream_t st;
+    const spira_params *p;
+    const spira::Plan &plan;
+    spira::BounceArgs<T> a{};        // scene, render constants, L, stats: what every organisation's arguments start from
+    size_t lds = 0;                  // the scene's share of a workgroup's LDS
+    int spec = 0;                    // speculative division of this call (Plan::spec)
+    bool progressive = false, profile = false;
+    uint32_t sample0 = 0, *d_rng = nullptr;
+    uint64_t launches = 0, metal_launches = 0;
+    using P4 = spira::Pack4<T>;
+    using P2 = spira::Pack2<T>;
+    P4 *accum() const { return (P4 *)c.accum.p; }
+    spira::Stats *stats() const { return (spira::Stats *)c.stats.p; }
+    uint32_t *redo() const { return (uint32_t *)c.redo.p; }
+    spira::RayQueue<T> queue(int i) const { return {(P4 *)c.qA[i].p, (P4 *)c.qB[i].p, (P2 *)c.qC[i].p}; }
+    dim3 block() const { return dim3(spira::kBlock); }
+    int resume() const { return progressive ? (sample0 > 0 ? 3 : 1) : 0; }      // SPIRA_SEM_METAL: bit 0 continue the sums, bit 1 continue the LCG states
+};
+
+// render_hybrid_gpu as written (spira_device.h, k_hybrid): the whole image in lock step, max_depth + 1 launches per sample, all on this stream
+template <class T>
+int enqueue_hybrid(Call<T> &k) {
+    Ctx &c = k.c;
+    const spira_params *p = k.p;
+    const spira::Workspace &w = k.plan.ws;
+    const uint32_t P = (uint32_t)k.plan.tile_pixels, hblocks = k.plan.blocks(P);
+    HIP_TRY(hipMemsetAsync(c.hyb_flags.p, 0, w.hyb_flags, k.st));
+    HIP_TRY(hipMemsetAsync(c.accum.p, 0, w.accum, k.st));
+    HIP_TRY(hipMemsetAsync(c.hyb_mat.p, 0, w.hyb_mat, k.st));
+    HIP_TRY(hipMemsetAsync(c.hyb_state.p, 0, w.hyb_state, k.st));
+    hipLaunchKernelGGL(spira::k_hybrid_init, dim3(hblocks), k.block(), 0, k.st, (uint32_t *)c.rng.p, P, k.a.rc.sA, k.a.rc.sB);
+    spira::HybridArgs<T> ha{};
+    ha.scene = k.a.scene; ha.rc = k.a.rc; ha.state = (T *)c.hyb_state.p; ha.mat = (uint32_t *)c.hyb_mat.p; ha.rng = (uint32_t *)c.rng.p;
+    ha.accum = k.accum(); ha.flags = (uint32_t *)c.hyb_flags.p; ha.stats = k.stats();
+    for (uint32_t smp = 1; smp <= p->spp; ++smp)
+        for (uint32_t ph = 0; ph <= p->max_depth; ++ph) {
+            ha.sample = smp; ha.phase = ph;
+            launch_lds(spira::k_hybrid<T>, dim3(hblocks), k.block(), k.lds, k.st, ha);
+        }
+    if (int rc = lds_optin_failed()) return rc;
+    k.launches += 1 + (uint64_t)p->spp * (p->max_depth + 1);
+    return 0;
+}
+
+// the .metal estimator in wavefront form: every wave owns a block of pixels and walks sample after sample on it
+template <class T>
+int enqueue_metal_wavefront(Call<T> &k) {
+    Ctx &c = k.c;
+    const spira::Plan &plan = k.plan;
+    const dim3 grid(plan.G_metal);
+    spira::MetalArgs<T> ma{};
+    ma.scene = k.a.scene; ma.rc = k.a.rc;
+    ma.ppw = plan.ppw;
+    for (int i = 0; i < 2; ++i) { ma.q[i] = k.queue(i); ma.qx[i] = (uint2 *)c.qX[i].p; }
+    if (!k.d_rng) k.d_rng = (uint32_t *)c.rng.p;
+    ma.L = k.a.L; ma.accum = k.accum(); ma.rng_states = k.d_rng; ma.blk_stats = (uint32_t *)c.blkstats.p;
+    ma.resume = k.resume();
+    if (int rc = profile_events(c, c.ev_used + 2)) return rc;      // (a later slab's bracket comes after slab 0's)
+    HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+    ma.stats = k.stats(); ma.redo = nullptr; ma.redo_only = 0;
+    if (k.spec) {                          // speculative division as in k_path
+        ma.redo = k.redo();
+        ma.redo_only = k.spec == 2 ? 2 : 0;
+        launch_lds(spira::k_path_metal<T, 2, true>, grid, k.block(), k.lds, k.st, ma);
+        ma.redo_only = 1;
+        ++k.launches;
+    }
+    if (plan.R == 2) launch_lds(spira::k_path_metal<T, 2, false>, grid, k.block(), k.lds, k.st, ma);
+    else launch_lds(spira::k_path_metal<T, 1, false>, grid, k.block(), k.lds, k.st, ma);
+    if (int rc = lds_optin_failed()) return rc;
+    HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+    hipLaunchKernelGGL(spira::k_fold_stats, dim3(1), dim3(64), 0, k.st, (const uint32_t *)c.blkstats.p, plan.G_metal * plan.wpb, k.stats());
+    k.launches += 2;
+    k.metal_launches = 1;
+    return 0;
+}
+
+// SPIRA_SEM_METAL in one launch: every lane owns a pixel and walks its spp samples (the LCG state runs through them); with speculative
+// division (fresh renders of scenes of ordinary scale) the exact launch behind renders reported waves again
+template <class T>
+int enqueue_metal(Call<T> &k) {
+    const dim3 grid(k.plan.blocks(k.plan.tile_pixels));
+    k.a.pass = 0; k.a.n_first = (uint32_t)k.plan.tile_pixels;
+    if (k.spec) {
+        launch_lds(spira::k_variant_metal<T, true>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), k.spec == 2 ? 2 : 0);
+        launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), 1);
+    } else
+        launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), (uint32_t *)nullptr, 0);
+    k.launches += k.spec ? 2 : 1;
+    return 0;
+}
+
+// ---- organisations that render `slots` samples of every pixel per pass: the launches of pass k.a.pass (*stat_rows: rows of per-wave statistics k_resolve folds)
+template <class T>
+int enqueue_cpu_pass(Call<T> &k) {
+    const dim3 grid(k.plan.blocks(k.a.n_first));
+    if (k.spec) {                          // speculative division as in k_path / k_variant_metal
+        launch_lds(spira::k_variant_cpu<T, true>, grid, k.block(), k.lds, k.st, k.a, k.redo(), k.spec == 2 ? 2 : 0);
+        launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, k.redo(), 1);
+    } else
+        launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, (uint32_t *)nullptr, 0);
+    k.launches += k.spec ? 2 : 1;
+    return 0;
+}
+
+template <class T>
+int enqueue_mega_pass(Call<T> &k) {
+    const dim3 grid(k.plan.blocks(k.a.n_first));
+    const bool ext = (k.p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    if (k.a.scene.n_bvh_tris) { if (ext) launch_lds(spira::k_mega<T, true, true>, grid, k.block(), k.lds, k.st, k.a); else launch_lds(spira::k_mega<T, true, false>, grid, k.block(), k.lds, k.st, k.a); }
+    else { if (ext) launch_lds(spira::k_mega<T, false, true>, grid, k.block(), k.lds, k.st, k.a); else launch_lds(spira::k_mega<T, false, false>, grid, k.block(), k.lds, k.st, k.a); }
+    ++k.launches;
+    return 0;
+}
+
+// k_path, one launch: every wave walks all max_depth stages on its own region of the hit queues (mesh scenes: a parking launch + a fat-wave launch)
+template <class T>
+int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
+    using P4 = typename Call<T>::P4;
+    Ctx &c = k.c;
+    const spira::Plan &plan = k.plan;
+    const spira::Knobs &kn = plan.in.k;
+    spira::PathArgs<T> pa{};
+    pa.scene = k.a.scene; pa.rc = k.a.rc; pa.L = k.a.L; pa.pass = k.a.pass; pa.n_first = k.a.n_first;
+    pa.dense_pct = kn.dense_pct;
+    pa.mesh_list = plan.defer_mesh ? (P4 *)c.mesh_list.p : nullptr;
+    const spira::Geometry g = plan.geometry(pa.n_first);
+    const uint32_t G = g.G;
+    pa.cap = g.cap;
+    *stat_rows = G * plan.wpb;
+    for (int i = 0; i < 2; ++i) {
+        pa.q[i] = k.queue(i);
+        pa.qref[i] = (uint32_t *)c.qR[i].p;
+        pa.qkey[i] = (uint2 *)c.qK[i].p;
+    }
+    pa.blk_stats = (uint32_t *)c.blkstats.p;
+    pa.stats = k.stats();
+    if (k.spec) pa.redo = k.redo();      // (sized by the plan whenever SPIRA_SPEC_DIV != 0)
+    pa.mesh_mode = 0; pa.mesh_count = nullptr; pa.resume_k = 1; pa.resume_nw = 0;
+    pa.mesh_min_batch = kn.mesh_min_batch;
+    pa.refill_free = kn.mesh_refill;
+    size_t lds_a = k.lds + (size_t)plan.wpb * plan.sub * sizeof(P4) + 128;             // + one work list per wave + the camera
+    // ... + one packet per sphere: what a sphere test of a CAMERA ray does not depend on the ray for (closest_hit_local, CAM) — where the block has the room
+    pa.cam_consts = (kn.cam_consts && pa.scene.n_spheres && lds_a + (size_t)pa.scene.n_spheres * sizeof(P4) <= (size_t)160 * 1024) ? 1u : 0u;
+    if (pa.cam_consts) lds_a += (size_t)pa.scene.n_spheres * sizeof(P4);
+    if (plan.two_pass) {
+        pa.mesh_mode = 1; pa.mesh_count = (uint32_t *)c.mesh_count.p;
+        pa.resume_nw = G * plan.wpb; pa.resume_k = plan.fat_k(pa.resume_nw);
+    }
+    if (plan.fused) {
+        pa.accum = k.accum(); pa.k_eff = plan.k_eff(pa.pass); pa.fd_keff = spira::fastdiv_make(pa.k_eff);
+        pa.accum_first = (pa.pass == 0 && !k.progressive) ? 1u : 0u;
+        pa.l_private = plan.l_private ? 1u : 0u;
+    }
+    if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
+    HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+    if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec)) return rc;
+    if (int rc = lds_optin_failed()) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
+    k.launches += k.spec ? 2 : 1;      // the speculative launch and its exact follow-up
+    if (pa.mesh_mode == 1) {           // second launch: nw / k fat waves
+        if (c.ev_mid.size() <= c.ev_mid_used) {
+            hipEvent_t e;
+            HIP_TRY(hipEventCreate(&e));
+            c.ev_mid.push_back(e); c.ev_mid_end.push_back(0);
+        }
+        HIP_TRY(hipEventRecord(c.ev_mid[c.ev_mid_used], k.st));
+        c.ev_mid_end[c.ev_mid_used++] = c.ev_used;      // (the closing event of this pass's bracket is recorded next)
+        spira::PathArgs<T> pb = pa;
+        pb.mesh_mode = 2; pb.n_first = 0;
+        const uint32_t nwb = pa.resume_nw / pa.resume_k;
+        launch_path_resume_entry<T>((int)plan.R, dim3((nwb + plan.wpb - 1) / plan.wpb), lds_a, k.st, pb);
+        if (int rc = lds_optin_failed()) return rc;
+        ++k.launches;
+    }
+    HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+    return 0;
+}
+
+// round-1 organisation: one launch per bounce; bounce b writes queue b & 1 and reads the other
+template <class T>
+int enqueue_bounce_pass(Call<T> &k, uint32_t *stat_rows) {
+    using P4 = typename Call<T>::P4;
+    Ctx &c = k.c;
+    const spira::Plan &plan = k.plan;
+    const spira::Geometry g = plan.geometry(k.a.n_first);
+    const size_t nw = (size_t)g.G * plan.wpb;
+    k.a.cap = g.cap;
+    *stat_rows = k.p->max_depth * g.G * plan.wpb;
+    for (uint32_t b = 0; b < k.p->max_depth; ++b) {
+        k.a.bounce = b;
+        k.a.qout = k.queue(b & 1);
+        k.a.qin = k.queue((b & 1) ^ 1);
+        k.a.cnt_in = (const uint32_t *)c.counts.p + (size_t)b * nw;
+        k.a.cnt_out = (uint32_t *)c.counts.p + (size_t)(b + 1) * nw;
+        k.a.blk_stats = (uint32_t *)c.blkstats.p + (size_t)b * nw * 4;
+        if (k.profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+        const size_t lds_b = k.lds + (size_t)plan.wpb * plan.sub * sizeof(P4);   // + one work list per wave (one slot per ray of a sub-chunk)
+        if (b == 0) launch_bounce<T, true>((int)plan.R, dim3(g.G), lds_b, k.st, k.a);
+        else launch_bounce<T, false>((int)plan.R, dim3(g.G), lds_b, k.st, k.a);
+        if (int rc = lds_optin_failed()) return rc;
+        if (k.profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
+        ++k.launches;
+    }
+    return 0;
+}
+
+// accum[pixel] += the pass's samples of L, in sample order (not after pixel-owning passes: their waves resolved their pixels and added their counters)
+template <class T>
+void enqueue_resolve(Call<T> &k, uint32_t stat_rows) {
+    const spira::Plan &plan = k.plan;
+    hipLaunchKernelGGL((spira::k_resolve<T>), dim3(plan.blocks(plan.tile_pixels)), k.block(), 0, k.st, k.accum(), (const spira::Pack3<T> *)k.c.L.p,
+                       (uint32_t)plan.tile_pixels, plan.k_eff(k.a.pass), (k.a.pass == 0 && !k.progressive) ? 1 : 0,
+                       stat_rows ? (const uint32_t *)k.c.blkstats.p : (const uint32_t *)nullptr, stat_rows, k.stats());
+    ++k.launches;
+}
+
+template <class T>
+void enqueue_finalize(Call<T> &k, T *d_hdr, T *d_img) {
+    using P4 = typename Call<T>::P4;
+    const spira::Plan &plan = k.plan;
+    const dim3 grid(plan.blocks(plan.tile_pixels));
+    if (k.progressive)      // hand the running sums back untouched (x / 1 is exact)
+        hipLaunchKernelGGL((spira::k_finalize<T>), grid, k.block(), 0, k.st, (const P4 *)k.accum(), (uint32_t)plan.tile_pixels, 1u, (uint32_t)SPIRA_POST_NONE, d_hdr, (T *)nullptr);
+    else
+        hipLaunchKernelGGL((spira::k_finalize<T>), grid, k.block(), 0, k.st, (const P4 *)k.accum(), (uint32_t)plan.tile_pixels, k.p->spp,
+                           (k.p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_HYBRID ? (uint32_t)SPIRA_POST_NONE : (k.p->flags & SPIRA_POST_MASK), d_hdr, d_img);      // (HYBRID: the sum is already tone-mapped, K7 per sample)
+    ++k.launches;
+}
+
+// Validation -> plan -> workspaces -> scene -> prologue (events, a progressive call's running sums) -> the organisation's launches -> epilogue.
+// (The kernels of a translation unit come out in the order in which their launches are first named from here, enqueue function by enqueue function:
+// keep that order, and every launch but k_load_accum's inside one of them, and the code object does not change when this function does.)
 template <class T>
 int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
                 T *out_hdr, T *out_img, bool out_on_device, void *user_stream,
                 bool progressive = false, uint32_t sample0 = 0, uint32_t *rng_states = nullptr, const SlabCtl *slab = nullptr) {
     // progressive: out_hdr is the caller's running SUM (in/out), samples [sample0, sample0 + spp) are added to it
+    using spira::Org;
+    using P4 = spira::Pack4<T>;
     uint32_t rows = 0;
     const bool cont = slab && slab->index > 0;      // a later slab of a host-output frame: continues slab 0's call (SlabCtl)
-    if (!p) return fail(SPIRA_E_INVALID, "params is NULL");
     tl_lds_optin = hipSuccess;           // (a flag an earlier call of this thread left behind by returning early must not fail this one)
     Lap lap("render");
-    if (h) { if (int rc = check_handle<T>(h)) return rc; }
-    else if (!cont) { if (int rc = validate_scene<T>(spheres5, materials8, triangles10, p->n_spheres, p->n_materials, triangles10 ? p->n_triangles : 0)) return rc; }
-    if (int rc = validate_params(camera12, p, h ? h->store.nt : (triangles10 ? p->n_triangles : 0), &rows)) return rc;
+    if (slab) rows = p->rows;            // (render_host_slabs validated the frame its slabs are cut from)
+    else if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, progressive, sample0, rng_states, &rows)) return rc;
     lap("validate");
-    if (!out_hdr && !out_img) return fail(SPIRA_E_INVALID, "both outputs are NULL");
-    if (progressive && (uint64_t)sample0 + p->spp > SPIRA_MAX_SPP) return fail(SPIRA_E_LIMIT, "sample0 + spp exceeds 2^24");
-    if (progressive && (p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_HYBRID) return fail(SPIRA_E_UNSUPPORTED, "SPIRA_SEM_HYBRID has no accumulate entry (its image is a mean of tone-mapped samples)");
-    if (progressive && (p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_METAL && sample0 > 0 && !rng_states)
-        return fail(SPIRA_E_INVALID, "SPIRA_SEM_METAL with sample0 > 0 needs rng_states (the LCG states the previous call left); "
-                                     "without them every call would replay the samples of the first");
     Ctx *cp = nullptr;
     if (int rc = get_ctx(&cp)) return rc;
     Ctx &c = *cp;
@@ -712,126 +999,37 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     if (int rc = order_after_previous(c, st)) return rc;
     lap("context");
 
-    const uint32_t W = p->width;
-    const uint64_t tile_pixels = (uint64_t)rows * W;
-    // default pass size: 160 Mi rays (a 1080p x 64 spp frame is one pass); ~16 GB (f32) / 31 GB (f64) of the 288 GB
-    uint32_t target = p->batch_rays ? p->batch_rays : env_u32("SPIRA_BATCH_RAYS", 160u << 20);
-    uint64_t slots64 = std::max<uint64_t>(1, target / tile_pixels);
-    slots64 = std::min<uint64_t>(slots64, p->spp);
-    slots64 = (p->spp + (p->spp + slots64 - 1) / slots64 - 1) / ((p->spp + slots64 - 1) / slots64);      // equal passes: spp 256 at 80 slots -> 4 x 64, not 3 x 80 + 16
-    if (slots64 * tile_pixels > 0x7FFFFFFFull) return fail(SPIRA_E_LIMIT, "tile too large: rows*width must be < 2^31");
-    const uint32_t slots = (uint32_t)slots64;
-    const uint64_t batch = slots64 * tile_pixels;
-    const uint32_t sem = p->flags & SPIRA_SEM_MASK;
-    // the secondary variants run one lane per path / per pixel: no queues, no bounce kernels
-    const bool mega = (p->flags & SPIRA_KERNEL_MASK) == SPIRA_KERNEL_MEGA || sem != SPIRA_SEM_A;
-    const bool metal_wavefront = sem == SPIRA_SEM_METAL && (p->flags & SPIRA_KERNEL_MASK) == SPIRA_KERNEL_WAVEFRONT;
-    uint64_t metal_launches = 0;
-    const bool per_bounce = !mega && (p->flags & SPIRA_KERNEL_MASK) == SPIRA_KERNEL_BOUNCE;     // round-1 organisation: one launch per bounce
-    const bool persistent = !mega && !per_bounce;                                                // k_path: one launch per pass
-    const bool profile = ((p->flags & SPIRA_FLAG_PROFILE) != 0 && per_bounce) || persistent;     // k_path launches are always bracketed (2 events per pass)
-    int R = (int)env_u32("SPIRA_R", 2);
-    if (R != 1 && R != 2) R = 2;
-    if (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) R = 2;      // the extension instantiations exist for R = 2 only
-
-    // ---- launch geometry: NW = 4*G autonomous waves per bounce kernel, each owning `cap` rays of both queues
-    // workgroups per CU: the persistent kernel runs a whole pass per launch, so its launch tail is one workgroup's share of the
-    // pass: 32 per CU (8 rounds of resident workgroups) measured best on S1 (16: -3.5 %, 64: -1 %, 128: -5 %; S3 likes 64-128, +1.7 %)
-    // Mesh scenes want fewer, fatter waves: a wave's round ends with the dense traversal of the rays it parked at the mesh's box, and a
-    // traversal batch costs its slowest ray's chain of dependent node fetches whether it holds 64 rays or 10 (config 5, 81 920 triangles:
-    // f32 32 per CU 7.54 ms, 16: 6.78, 8: 7.29, 4: 7.04; f64 32: 11.67, 8: 10.29, 4: 9.68; re-measured with the round's final kernels: f32 16: 6.83, 8: 7.02, 32: 7.39,
-    // f64 4: 9.54, 8: 10.13, 16: 10.49 — and counts that are not powers of two lose 10-40 %: the grid no longer divides evenly over 8 XCDs x 32 CUs).
+    spira::Plan plan;
+    const char *msg = nullptr;
     const uint32_t nt_scene = h ? h->store.nt : (triangles10 ? p->n_triangles : 0);
-    const bool mesh_two_pass = persistent && nt_scene > SPIRA_LDS_TRIANGLES && p->max_depth <= 128 && env_u32("SPIRA_DEFER_MESH", 1) && env_u32("SPIRA_MESH_TWO_PASS", 1);
-    const uint32_t blocks_per_cu = !persistent ? 16 : ((nt_scene > SPIRA_LDS_TRIANGLES && !mesh_two_pass) ? 4 : 32);
-    const uint32_t max_blocks = (uint32_t)c.num_cus * env_u32("SPIRA_BLOCKS_PER_CU", blocks_per_cu);
-    const uint32_t wpb = spira::kBlock / 64;
-    const uint32_t sub = 64 * R;                                   // rays per wave sub-chunk
-    // pixel-owning passes (PathArgs::accum): each wave sums its own 64 pixels at its end instead of k_resolve streaming the whole of L after the
-    // launch — S1 Float64 -1.5 … -4.5 %.  Only where that was measured to pay: Float64 scenes of spheres alone, no extension, at most 64 slots per pass.
-    // In Float32 the end-of-wave sum costs k_path what k_resolve costs (S1 +0.30 / 0.29 ms); in the kernels with the LDS triangle scan or the
-    // extensions its code costs spilled registers (glass scene Float64 +15 %, S2 +4 %).  SPIRA_FUSED_RESOLVE=0: round-robin dealing + k_resolve (A/B, tests).
-    // (R = 2 too: the instantiation of SPIRA_R=1 is compiled with the triangle scan.)
-    const bool fused = persistent && sizeof(T) == 8 && R == 2 && nt_scene == 0 && (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) == 0 &&
-                       slots <= 64 && env_u32("SPIRA_FUSED_RESOLVE", 1) != 0;
-    auto geometry = [&](uint64_t n_first, uint32_t &G, uint32_t &cap) {
-        if (fused) {                                                // one wave per 64 pixels; its region holds all its paths
-            const uint64_t k = n_first / tile_pixels;
-            G = (uint32_t)((tile_pixels + 64 * wpb - 1) / (64 * wpb));
-            cap = (uint32_t)((64 * k + sub - 1) / sub * sub);
-            return;
-        }
-        const uint64_t n_sub = (n_first + sub - 1) / sub;
-        G = (uint32_t)std::min<uint64_t>((n_sub + wpb - 1) / wpb, max_blocks);
-        const uint64_t nw = (uint64_t)G * wpb;
-        cap = (uint32_t)(((n_sub + nw - 1) / nw) * sub);
-    };
-    // ... and keep the radiance of their paths in one contiguous block per wave (PathArgs::l_private) wherever the queue word is free to address it: the
-    // RNG key is carried through the queue for max_depth <= 128 (deeper renders derive it from the path index and keep the slot-major L).
-    // SPIRA_PRIVATE_L=0: the slot-major layout (A/B).
-    const bool l_private_wanted = fused && SPIRA_CARRY_KEY && p->max_depth <= 128 && env_u32("SPIRA_PRIVATE_L", 1) != 0;
-    uint32_t G_max = 0, cap_max = 0;
-    geometry(batch, G_max, cap_max);
-    const bool l_private = l_private_wanted && 64ull * G_max * (spira::kBlock / 64) * slots <= 0x7FFFFFFFull;      // (the queue word has 31 bits for the entry of L)
-    const uint64_t q_rays = (uint64_t)cap_max * G_max * wpb;
-    if (q_rays > 0xFFFFFFFFull) return fail(SPIRA_E_LIMIT, "pass too large");
-
-    // ---- workspaces (cached per device, grown on demand; sized for 288 GB HBM: no chunking of a pass)
-    using P4 = spira::Pack4<T>;
-    using P2 = spira::Pack2<T>;
-    const bool mesh_scene = nt_scene > SPIRA_LDS_TRIANGLES;
-    const bool defer_mesh = persistent && mesh_scene && p->max_depth <= 128 && env_u32("SPIRA_DEFER_MESH", 1) != 0;
-    // speculative division (spira_device.h, SpecDiv): decided here once, because it needs a workspace (the per-wave redo flags) — see the launch below
-    PathPlan plan;
-    plan.waves = (uint64_t)G_max * wpb; plan.packets = q_rays;
-    plan.batch = l_private ? std::max<uint64_t>(batch, 64ull * G_max * wpb * slots) : batch;      // (a pixel-owning grid depends on the pixel count alone: G_max waves in every pass)
-    // (max_depth == 1 needs no queue — except on a mesh scene of the persistent organisation: a parked camera ray's hit comes back from its
-    //  traversal session as a packet.)
-    plan.queues = !mega && (p->max_depth > 1 || (persistent && mesh_scene));
-    plan.mesh = defer_mesh; plan.two_pass = defer_mesh && mesh_two_pass; plan.spec = persistent && env_u32("SPIRA_SPEC_DIV", 1) != 0;
-    if (persistent) { if (int rc = ensure_path_plan<T>(c, plan)) return rc; }
-    else {
-        if (plan.queues)
-            for (int i = 0; i < 2; ++i) {
-                if (int rc = c.qA[i].ensure(q_rays * sizeof(P4))) return rc;
-                if (int rc = c.qB[i].ensure(q_rays * sizeof(P4))) return rc;
-                if (int rc = c.qC[i].ensure(q_rays * sizeof(P2))) return rc;
-            }
-        if (sem != SPIRA_SEM_HYBRID) { if (int rc = c.L.ensure(batch * sizeof(spira::Pack3<T>))) return rc; }
-        // per-wave survivor counts exist in the per-bounce organisation only; statistics: one row per wave per launch
-        if (per_bounce) { if (int rc = c.counts.ensure((size_t)(p->max_depth + 2) * G_max * wpb * sizeof(uint32_t))) return rc; }
-        if (int rc = c.blkstats.ensure((size_t)(per_bounce ? p->max_depth + 1 : 1) * G_max * wpb * 4 * sizeof(uint32_t))) return rc;
-        if (int rc = c.stats.ensure(sizeof(spira::Stats))) return rc;
-    }
-    if (int rc = c.accum.ensure(tile_pixels * sizeof(P4))) return rc;
-
+    if (int rc = spira::make_plan(plan_input<T>(c, p, rows, nt_scene, progressive, progressive && rng_states, out_on_device), plan, &msg)) return fail(rc, msg);
+    if (int rc = ensure_workspaces(c, plan.ws)) return rc;
     lap("workspaces");
-    spira::BounceArgs<T> a{};
-    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, p, a.scene, cont)) return rc;
-    if (int rc = attach_spd<T>(c, st, p, a.scene)) return rc;
-    lap("scene");
-    const bool scene_moderate = h ? h->store.moderate : c.scene.moderate;
-    fill_const<T>(a.rc, camera12, p, rows, slots);
-    if (!fastdiv_selfcheck(a.rc.tile_pixels, (uint32_t)batch) || !fastdiv_selfcheck(a.rc.width, a.rc.tile_pixels) ||
-        !fastdiv_selfcheck(a.rc.stripe_h ? a.rc.stripe_h : 1, rows))
-        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-    a.L = (spira::Pack3<T> *)c.L.p;
-    a.stats = (spira::Stats *)c.stats.p;
 
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    const uint32_t n_pass = (p->spp + slots - 1) / slots;
+    Call<T> k{c, st, p, plan};
+    const uint64_t tile_pixels = plan.tile_pixels;
+    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, p, k.a.scene, cont)) return rc;
+    if (int rc = attach_spd<T>(c, st, p, k.a.scene)) return rc;
+    lap("scene");
+    k.spec = plan.spec((h ? h->store.moderate : c.scene.moderate) && spira::camera_scale_moderate<T>(camera12));
+    fill_const<T>(k.a.rc, camera12, p, rows, plan.slots);
+    if (!fastdiv_selfcheck(k.a.rc.tile_pixels, (uint32_t)plan.batch) || !fastdiv_selfcheck(k.a.rc.width, k.a.rc.tile_pixels) ||
+        !fastdiv_selfcheck(k.a.rc.stripe_h ? k.a.rc.stripe_h : 1, rows))
+        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+    k.a.L = (spira::Pack3<T> *)c.L.p;
+    k.a.stats = k.stats();
+    k.lds = spira::scene_lds_bytes<T>(k.a.scene.n_spheres, k.a.scene.n_materials, k.a.scene.n_triangles);
+    k.progressive = progressive; k.sample0 = sample0;
+    // k_path launches are always bracketed (2 events per pass); the per-bounce ones on request
+    k.profile = plan.org == Org::Path || (plan.org == Org::Bounce && (p->flags & SPIRA_FLAG_PROFILE) != 0);
 
     T *d_hdr = out_hdr, *d_img = out_img;
     if (!out_on_device) {
-        size_t plane3 = 3 * tile_pixels * sizeof(T);
-        if (int rc = c.out_tmp.ensure(2 * plane3)) return rc;
         d_hdr = out_hdr ? (T *)c.out_tmp.p : nullptr;
-        d_img = out_img ? (T *)((char *)c.out_tmp.p + plane3) : nullptr;
+        d_img = out_img ? (T *)((char *)c.out_tmp.p + 3 * tile_pixels * sizeof(T)) : nullptr;
     }
-
-    size_t n_prof = 0;
-    if (profile) {
-        n_prof = (size_t)n_pass * (persistent ? 1 : std::max<uint32_t>(p->max_depth, 1)) * 2;
+    if (k.profile) {
+        const size_t n_prof = (size_t)plan.n_pass * (plan.org == Org::Path ? 1 : p->max_depth) * 2;
         if (int rc = profile_events(c, (cont ? c.ev_used : 0) + n_prof)) return rc;
     }
     if (!cont) {                         // (a later slab adds its brackets and device counters to slab 0's)
@@ -840,268 +1038,49 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
         HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), st));
         HIP_TRY(hipEventRecord(c.ev_start, st));
     }
-    uint64_t launches = 0;
 
     // progressive accumulation: the caller's running sums (and, METAL, LCG states) seed the accumulator
-    a.rc.sample0 = progressive ? sample0 : 0;
-    uint32_t *d_rng = nullptr;
+    k.a.rc.sample0 = progressive ? sample0 : 0;
     if (progressive) {
-        const uint32_t lblocks = std::min<uint32_t>((uint32_t)((tile_pixels + spira::kBlock - 1) / spira::kBlock), max_blocks);
         if (!out_on_device) HIP_TRY(hipMemcpyAsync(d_hdr, out_hdr, 3 * tile_pixels * sizeof(T), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((spira::k_load_accum<T>), dim3(lblocks), dim3(spira::kBlock), 0, st, (P4 *)c.accum.p, (const T *)d_hdr, (uint32_t)tile_pixels);
-        ++launches;
-        if (rng_states) {
-            d_rng = rng_states;
-            if (!out_on_device) {
-                if (int rc = c.rng.ensure(tile_pixels * sizeof(uint32_t))) return rc;
-                d_rng = (uint32_t *)c.rng.p;
-                if (sample0 > 0) HIP_TRY(hipMemcpyAsync(d_rng, rng_states, tile_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            }
-        }
+        hipLaunchKernelGGL((spira::k_load_accum<T>), dim3(plan.blocks(tile_pixels)), k.block(), 0, st, k.accum(), (const T *)d_hdr, (uint32_t)tile_pixels);
+        ++k.launches;
+        k.d_rng = (rng_states && !out_on_device) ? (uint32_t *)c.rng.p : rng_states;
+        if (rng_states && !out_on_device && sample0 > 0) HIP_TRY(hipMemcpyAsync(k.d_rng, rng_states, tile_pixels * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
 
-    if (p->max_depth == 0) {
-        if (!progressive) HIP_TRY(hipMemsetAsync(c.accum.p, 0, tile_pixels * sizeof(P4), st));   // depth <= 0 -> Vec3(0,0,0), :330
-    } else if (sem == SPIRA_SEM_HYBRID) {
-        // render_hybrid_gpu as written (spira_device.h, k_hybrid): the whole image in lock step, max_depth + 1 launches per sample, all on this stream
-        const uint64_t P = tile_pixels;
-        if (P > 0xFFFFFFFFull / 2) return fail(SPIRA_E_LIMIT, "image too large for SPIRA_SEM_HYBRID");
-        if (int rc = c.hyb_state.ensure(12 * P * sizeof(T))) return rc;
-        if (int rc = c.hyb_mat.ensure(P * sizeof(uint32_t))) return rc;
-        if (int rc = c.rng.ensure(P * sizeof(uint32_t))) return rc;
-        const size_t n_flags = (size_t)p->spp * (p->max_depth + 1);
-        if (int rc = c.hyb_flags.ensure(n_flags * sizeof(uint32_t))) return rc;
-        HIP_TRY(hipMemsetAsync(c.hyb_flags.p, 0, n_flags * sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(c.accum.p, 0, P * sizeof(P4), st));
-        HIP_TRY(hipMemsetAsync(c.hyb_mat.p, 0, P * sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(c.hyb_state.p, 0, 12 * P * sizeof(T), st));
-        const uint32_t hblocks = std::min<uint32_t>((uint32_t)((P + spira::kBlock - 1) / spira::kBlock), max_blocks);
-        hipLaunchKernelGGL(spira::k_hybrid_init, dim3(hblocks), dim3(spira::kBlock), 0, st, (uint32_t *)c.rng.p, (uint32_t)P, a.rc.sA, a.rc.sB);
-        spira::HybridArgs<T> ha{};
-        ha.scene = a.scene; ha.rc = a.rc; ha.state = (T *)c.hyb_state.p; ha.mat = (uint32_t *)c.hyb_mat.p; ha.rng = (uint32_t *)c.rng.p;
-        ha.accum = (P4 *)c.accum.p; ha.flags = (uint32_t *)c.hyb_flags.p; ha.stats = (spira::Stats *)c.stats.p;
-        for (uint32_t smp = 1; smp <= p->spp; ++smp)
-            for (uint32_t ph = 0; ph <= p->max_depth; ++ph) {
-                ha.sample = smp; ha.phase = ph;
-                launch_lds(spira::k_hybrid<T>, dim3(hblocks), dim3(spira::kBlock), lds, st, ha);
-            }
-        if (int rc = lds_optin_failed()) return rc;
-        launches += 1 + (uint64_t)p->spp * (p->max_depth + 1);
-    } else if (sem == SPIRA_SEM_METAL && metal_wavefront) {
-        // the .metal estimator in wavefront form: every wave owns a block of pixels and walks sample after sample on it
-        spira::MetalArgs<T> ma{};
-        ma.scene = a.scene; ma.rc = a.rc;
-        const uint32_t g_res = (uint32_t)c.num_cus * (sizeof(T) == 8 ? SPIRA_WAVES_F64 : SPIRA_WAVES_F32);     // one resident round of workgroups
-        const uint64_t nw0 = (uint64_t)g_res * wpb;
-        ma.ppw = (uint32_t)((((tile_pixels + nw0 - 1) / nw0) + 63) / 64 * 64);
-        const uint32_t Gm = (uint32_t)((tile_pixels + (uint64_t)ma.ppw * wpb - 1) / ((uint64_t)ma.ppw * wpb));
-        const uint64_t slots_q = (uint64_t)Gm * wpb * ma.ppw;
-        for (int i = 0; i < 2; ++i) {
-            if (int rc = c.qA[i].ensure(slots_q * sizeof(P4))) return rc;
-            if (int rc = c.qB[i].ensure(slots_q * sizeof(P4))) return rc;
-            if (int rc = c.qC[i].ensure(slots_q * sizeof(P2))) return rc;
-            if (int rc = c.qX[i].ensure(slots_q * sizeof(uint2))) return rc;
-            ma.q[i] = {(P4 *)c.qA[i].p, (P4 *)c.qB[i].p, (P2 *)c.qC[i].p};
-            ma.qx[i] = (uint2 *)c.qX[i].p;
-        }
-        if (!d_rng) {
-            if (int rc = c.rng.ensure(tile_pixels * sizeof(uint32_t))) return rc;
-            d_rng = (uint32_t *)c.rng.p;
-        }
-        if (int rc = c.blkstats.ensure((size_t)Gm * wpb * 4 * sizeof(uint32_t))) return rc;
-        ma.L = (spira::Pack3<T> *)c.L.p; ma.accum = (P4 *)c.accum.p; ma.rng_states = d_rng; ma.blk_stats = (uint32_t *)c.blkstats.p;
-        ma.resume = progressive ? (sample0 > 0 ? 3 : 1) : 0;          // bit 0: continue the sums, bit 1: continue the LCG states
-        if (int rc = profile_events(c, 2)) return rc;
-        HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-        int spec = (int)env_u32("SPIRA_SPEC_DIV", 1);      // speculative division as in k_path (fresh renders only: a progressive call updates sums and states in place)
-        if (spec == 1 && !(scene_moderate && spira::camera_scale_moderate<T>(camera12))) spec = 0;
-        if (spec == 3) spec = 1;
-        if (ma.resume || R != 2) spec = 0;
-        ma.stats = (spira::Stats *)c.stats.p; ma.redo = nullptr; ma.redo_only = 0;
-        if (spec) {
-            if (int rc = c.redo.ensure((size_t)Gm * wpb * sizeof(uint32_t))) return rc;
-            ma.redo = (uint32_t *)c.redo.p;
-            ma.redo_only = spec == 2 ? 2 : 0;
-            launch_lds(spira::k_path_metal<T, 2, true>, dim3(Gm), dim3(spira::kBlock), lds, st, ma);
-            ma.redo_only = 1;
-            ++launches;
-        }
-        if (R == 2) launch_lds(spira::k_path_metal<T, 2, false>, dim3(Gm), dim3(spira::kBlock), lds, st, ma);
-        else launch_lds(spira::k_path_metal<T, 1, false>, dim3(Gm), dim3(spira::kBlock), lds, st, ma);
-        if (int rc = lds_optin_failed()) return rc;
-        HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-        hipLaunchKernelGGL(spira::k_fold_stats, dim3(1), dim3(64), 0, st, (const uint32_t *)c.blkstats.p, Gm * wpb, (spira::Stats *)c.stats.p);
-        launches += 2;
-        metal_launches = 1;
-    } else if (sem == SPIRA_SEM_METAL) {
-        // one launch: every lane owns a pixel and walks its spp samples (the LCG state runs through them)
-        uint32_t blocks = std::min<uint32_t>((uint32_t)((tile_pixels + spira::kBlock - 1) / spira::kBlock), max_blocks);
-        a.pass = 0; a.n_first = (uint32_t)tile_pixels;
-        const int resume = progressive ? (sample0 > 0 ? 3 : 1) : 0;       // bit 0: continue the sums, bit 1: continue the LCG states
-        // speculative division as in k_path (SPIRA_SPEC_DIV): fresh renders of scenes of ordinary scale; the exact launch behind renders reported waves again
-        int spec = (int)env_u32("SPIRA_SPEC_DIV", 1);
-        if (spec == 1 && !(scene_moderate && spira::camera_scale_moderate<T>(camera12))) spec = 0;
-        if (spec == 3) spec = 1;
-        if (resume) spec = 0;
-        if (spec) {
-            if (int rc = c.redo.ensure((size_t)blocks * wpb * sizeof(uint32_t))) return rc;
-            uint32_t *redo = (uint32_t *)c.redo.p;
-            launch_lds(spira::k_variant_metal<T, true>, dim3(blocks), dim3(spira::kBlock), lds, st, a, (P4 *)c.accum.p, d_rng, resume, redo, spec == 2 ? 2 : 0);
-            launch_lds(spira::k_variant_metal<T, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a, (P4 *)c.accum.p, d_rng, resume, redo, 1);
-            launches += 2;
-        } else {
-            launch_lds(spira::k_variant_metal<T, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a, (P4 *)c.accum.p, d_rng, resume, (uint32_t *)nullptr, 0);
-            ++launches;
-        }
-    } else {
-        for (uint32_t pass = 0; pass < n_pass; ++pass) {
-            const uint32_t k_eff = std::min(slots, p->spp - pass * slots);
-            const uint32_t n_first = (uint32_t)((uint64_t)k_eff * tile_pixels);
-            a.pass = pass;
-            a.n_first = n_first;
-            uint32_t G = 0, stat_rows = 0;
-            if (sem == SPIRA_SEM_CPU) {
-                uint32_t blocks = std::min<uint32_t>((n_first + spira::kBlock - 1) / spira::kBlock, max_blocks);
-                int spec = (int)env_u32("SPIRA_SPEC_DIV", 1);      // speculative division as in k_path / k_variant_metal
-                if (spec == 1 && !(scene_moderate && spira::camera_scale_moderate<T>(camera12))) spec = 0;
-                if (spec == 3) spec = 1;
-                if (spec) {
-                    if (int rc = c.redo.ensure((size_t)max_blocks * wpb * sizeof(uint32_t))) return rc;
-                    uint32_t *redo = (uint32_t *)c.redo.p;
-                    launch_lds(spira::k_variant_cpu<T, true>, dim3(blocks), dim3(spira::kBlock), lds, st, a, redo, spec == 2 ? 2 : 0);
-                    launch_lds(spira::k_variant_cpu<T, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a, redo, 1);
-                    launches += 2;
-                } else {
-                    launch_lds(spira::k_variant_cpu<T, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a, (uint32_t *)nullptr, 0);
-                    ++launches;
-                }
-            } else if (mega) {
-                uint32_t blocks = std::min<uint32_t>((n_first + spira::kBlock - 1) / spira::kBlock, max_blocks);
-                const bool ext = (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
-                if (a.scene.n_bvh_tris) { if (ext) launch_lds(spira::k_mega<T, true, true>, dim3(blocks), dim3(spira::kBlock), lds, st, a); else launch_lds(spira::k_mega<T, true, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a); }
-                else { if (ext) launch_lds(spira::k_mega<T, false, true>, dim3(blocks), dim3(spira::kBlock), lds, st, a); else launch_lds(spira::k_mega<T, false, false>, dim3(blocks), dim3(spira::kBlock), lds, st, a); }
-                ++launches;
-            } else if (persistent) {
-                // one launch: every wave walks all max_depth stages on its own region of the hit queues
-                spira::PathArgs<T> pa{};
-                pa.scene = a.scene; pa.rc = a.rc; pa.L = a.L; pa.pass = pass; pa.n_first = n_first;
-                // dense continuation threshold (same device, S1 1080p spp 64 depth 8, Msamples/s): f64 100 %: 20 218, 90: 20 563, 80: 20 953,
-                // 70: 20 963, 60: 20 052; f32 90: 30 222, 80: 30 141, 70: 29 567, 60: 28 354 — a packet costs twice the bytes in Float64, so it
-                // pays to keep a little more in registers there.  On the closed box S3 any threshold > 0 gives the full +22 % (f64).
-                // Round 4 (packets carry the RNG key words: a queued hit costs more), S1 ms per frame, two rounds on one box: f64 80: 5.302 / 5.277, 75: 5.245 / 5.229,
-                // 70: 5.221 / 5.240, 65: 5.272 / 5.299; f32 80: 3.382 / 3.414, 75: 3.341 / 3.354, 70: 3.340 / 3.351, 65: 3.374 / 3.351; configs[4] the same at 70 and 80.
-                pa.dense_pct = std::min<uint32_t>(env_u32("SPIRA_DENSE_PCT", 70), 100);      // (Float32 re-measured on the no-SLP build of round 3, S1: 90: 37 900, 85: 38 500, 80: 38 500, 75: 38 500, 70: 37 500)
-                // BVH scenes: the wave-owned lists of rays waiting for their dense traversal batch (3 packets per entry, `cap` entries per wave)
-                pa.mesh_list = plan.mesh ? (P4 *)c.mesh_list.p : nullptr;
-                geometry(n_first, G, pa.cap);
-                stat_rows = G * wpb;
-                for (int i = 0; i < 2; ++i) {
-                    pa.q[i] = {(P4 *)c.qA[i].p, (P4 *)c.qB[i].p, (P2 *)c.qC[i].p};
-                    pa.qref[i] = (uint32_t *)c.qR[i].p;
-                    pa.qkey[i] = (uint2 *)c.qK[i].p;
-                }
-                pa.blk_stats = (uint32_t *)c.blkstats.p;
-                pa.stats = (spira::Stats *)c.stats.p;
-                // speculative division (spira_device.h, SpecDiv): +7 % on S1 while (almost) no wave has to be rendered again, which is what a scene
-                // and camera of ordinary magnitudes give; a scene scaled to 1e-30 would have every wave rendered twice, so it is not tried there
-                // SPIRA_SPEC_DIV: 0 off, 1 default, 2 report every wave (the whole pass is rendered twice), 3 on even where the predictor says no
-                int spec = (int)env_u32("SPIRA_SPEC_DIV", 1);
-                if (spec == 1 && !(scene_moderate && spira::camera_scale_moderate<T>(camera12))) spec = 0;
-                if (spec == 3) spec = 1;
-                if (spec) pa.redo = (uint32_t *)c.redo.p;      // (sized by the plan whenever SPIRA_SPEC_DIV != 0)
-                pa.mesh_mode = 0; pa.mesh_count = nullptr; pa.resume_k = 1; pa.resume_nw = 0;
-                pa.mesh_min_batch = std::max<uint32_t>(1, env_u32("SPIRA_MESH_MIN_BATCH", 128));
-                pa.refill_free = std::min<uint32_t>(64, std::max<uint32_t>(1, env_u32("SPIRA_MESH_REFILL", 16)));
-                size_t lds_a = lds + (size_t)wpb * sub * sizeof(P4) + 128;             // + one work list per wave + the camera
-                // ... + one packet per sphere: what a sphere test of a CAMERA ray does not depend on the ray for (closest_hit_local, CAM) — where the block has the room
-                pa.cam_consts = (env_u32("SPIRA_CAM_CONSTS", 1) && a.scene.n_spheres && lds_a + (size_t)a.scene.n_spheres * sizeof(P4) <= (size_t)160 * 1024) ? 1u : 0u;
-                if (pa.cam_consts) lds_a += (size_t)a.scene.n_spheres * sizeof(P4);
-                if (plan.two_pass) {
-                    pa.mesh_mode = 1; pa.mesh_count = (uint32_t *)c.mesh_count.p;
-                    // the fat waves of the second launch: about 16 per CU (4 per SIMD), each taking over k <= 16 first-launch waves; k divides their number
-                    const uint32_t nw = G * wpb, fat = std::max<uint32_t>(1, (uint32_t)c.num_cus * env_u32("SPIRA_MESH_FAT_WAVES_PER_CU", 16));
-                    uint32_t k = 16;
-                    while (k > 1 && (nw % k != 0 || nw / k < fat)) k >>= 1;
-                    pa.resume_k = k; pa.resume_nw = nw;
-                }
-                if (fused) {
-                    pa.accum = (P4 *)c.accum.p; pa.k_eff = k_eff; pa.fd_keff = spira::fastdiv_make(k_eff);
-                    pa.accum_first = (pass == 0 && !progressive) ? 1u : 0u;
-                    pa.l_private = l_private ? 1u : 0u;
-                }
-                if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
-                HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-                if (int rc = launch_path<T>(R, dim3(G), lds_a, st, pa, spec)) return rc;
-                if (int rc = lds_optin_failed()) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
-                launches += (spec && R == 2) ? 2 : 1;      // the speculative launch and its exact follow-up
-                if (pa.mesh_mode == 1) {           // second launch: nw / k fat waves
-                    if (c.ev_mid.size() <= c.ev_mid_used) {
-                        hipEvent_t e;
-                        HIP_TRY(hipEventCreate(&e));
-                        c.ev_mid.push_back(e); c.ev_mid_end.push_back(0);
-                    }
-                    HIP_TRY(hipEventRecord(c.ev_mid[c.ev_mid_used], st));
-                    c.ev_mid_end[c.ev_mid_used++] = c.ev_used;      // (the closing event of this pass's bracket is recorded next)
-                    spira::PathArgs<T> pb = pa;
-                    pb.mesh_mode = 2; pb.n_first = 0;
-                    const uint32_t nwb = pa.resume_nw / pa.resume_k;
-                    launch_path_resume_entry<T>(R, dim3((nwb + wpb - 1) / wpb), lds_a, st, pb);
-                    if (int rc = lds_optin_failed()) return rc;
-                    ++launches;
-                }
-                HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-            } else {
-                geometry(n_first, G, a.cap);
-                stat_rows = p->max_depth * G * wpb;
-                const size_t nw = (size_t)G * wpb;
-                for (uint32_t b = 0; b < p->max_depth; ++b) {
-                    a.bounce = b;
-                    int qi = b & 1;      // bounce b writes queue qi, reads queue qi^1
-                    a.qout = {(P4 *)c.qA[qi].p, (P4 *)c.qB[qi].p, (P2 *)c.qC[qi].p};
-                    a.qin = {(P4 *)c.qA[qi ^ 1].p, (P4 *)c.qB[qi ^ 1].p, (P2 *)c.qC[qi ^ 1].p};
-                    a.cnt_in = (const uint32_t *)c.counts.p + (size_t)b * nw;
-                    a.cnt_out = (uint32_t *)c.counts.p + (size_t)(b + 1) * nw;
-                    a.blk_stats = (uint32_t *)c.blkstats.p + (size_t)b * nw * 4;
-                    if (profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-                    const size_t lds_b = lds + (size_t)wpb * sub * sizeof(P4);   // + one work list per wave (one slot per ray of a sub-chunk)
-                    if (b == 0) launch_bounce<T, true>(R, dim3(G), lds_b, st, a);
-                    else launch_bounce<T, false>(R, dim3(G), lds_b, st, a);
-                    if (int rc = lds_optin_failed()) return rc;
-                    if (profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], st));
-                    ++launches;
-                }
-            }
-            if (fused) continue;      // the waves of the launch resolved their pixels and added their counters
-            uint32_t rblocks = std::min<uint32_t>((uint32_t)((tile_pixels + spira::kBlock - 1) / spira::kBlock), max_blocks);
-            hipLaunchKernelGGL((spira::k_resolve<T>), dim3(rblocks), dim3(spira::kBlock), 0, st, (P4 *)c.accum.p, (const spira::Pack3<T> *)c.L.p,
-                               (uint32_t)tile_pixels, k_eff, (pass == 0 && !progressive) ? 1 : 0, mega ? (const uint32_t *)nullptr : (const uint32_t *)c.blkstats.p,
-                               stat_rows, (spira::Stats *)c.stats.p);
-            ++launches;
+    int rc = 0;
+    switch (plan.org) {
+    case Org::Black: if (!progressive) HIP_TRY(hipMemsetAsync(c.accum.p, 0, tile_pixels * sizeof(P4), st)); break;   // depth <= 0 -> Vec3(0,0,0), :330
+    case Org::Hybrid: rc = enqueue_hybrid(k); break;
+    case Org::MetalWavefront: rc = enqueue_metal_wavefront(k); break;
+    case Org::Metal: rc = enqueue_metal(k); break;
+    default:                             // `slots` samples of every pixel per pass, then the pass's resolve
+        for (uint32_t pass = 0; pass < plan.n_pass && !rc; ++pass) {
+            uint32_t stat_rows = 0;
+            k.a.pass = pass;
+            k.a.n_first = plan.n_first(pass);
+            rc = plan.org == Org::Cpu ? enqueue_cpu_pass(k) : plan.org == Org::Mega ? enqueue_mega_pass(k) :
+                 plan.org == Org::Path ? enqueue_path_pass(k, &stat_rows) : enqueue_bounce_pass(k, &stat_rows);
+            if (!rc && !plan.fused) enqueue_resolve(k, stat_rows);
         }
     }
-    {
-        uint32_t fblocks = std::min<uint32_t>((uint32_t)((tile_pixels + spira::kBlock - 1) / spira::kBlock), max_blocks);
-        if (progressive)      // hand the running sums back untouched (x / 1 is exact)
-            hipLaunchKernelGGL((spira::k_finalize<T>), dim3(fblocks), dim3(spira::kBlock), 0, st, (const P4 *)c.accum.p, (uint32_t)tile_pixels,
-                               1u, (uint32_t)SPIRA_POST_NONE, d_hdr, (T *)nullptr);
-        else
-            hipLaunchKernelGGL((spira::k_finalize<T>), dim3(fblocks), dim3(spira::kBlock), 0, st, (const P4 *)c.accum.p, (uint32_t)tile_pixels,
-                               p->spp, sem == SPIRA_SEM_HYBRID ? (uint32_t)SPIRA_POST_NONE : (p->flags & SPIRA_POST_MASK), d_hdr, d_img);      // (HYBRID: the sum is already tone-mapped, K7 per sample)
-        ++launches;
-    }
+    if (rc) return rc;
+    enqueue_finalize(k, d_hdr, d_img);
     if (progressive && rng_states && !out_on_device)
-        HIP_TRY(hipMemcpyAsync(rng_states, d_rng, tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (int rc = lds_optin_failed()) return rc;
+        HIP_TRY(hipMemcpyAsync(rng_states, k.d_rng, tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (int rc2 = lds_optin_failed()) return rc2;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev_stop, st));
     HIP_TRY(hipMemcpyAsync(c.h_stats, c.stats.p, sizeof(spira::Stats), hipMemcpyDeviceToHost, st));
     lap("enqueue");
 
+    const bool bounce_kernels = plan.org == Org::Path || plan.org == Org::Bounce;
     if (!cont) c.last = spira_counters{};
     c.last.samples += (uint64_t)p->spp * tile_pixels;
-    c.last.passes += p->max_depth ? n_pass : 0;
-    c.last.launches += launches;
-    c.last.bounce_launches += metal_launches ? metal_launches : ((mega || !p->max_depth) ? 0 : (uint64_t)n_pass * (persistent ? 1 : p->max_depth));
+    c.last.passes += p->max_depth ? plan.n_pass : 0;
+    c.last.launches += k.launches;
+    c.last.bounce_launches += k.metal_launches ? k.metal_launches : !bounce_kernels ? 0 : (uint64_t)plan.n_pass * (plan.org == Org::Path ? 1 : p->max_depth);
     c.last_valid = true;
     c.last_pending = true;
     c.last_stream = st;
@@ -1109,9 +1088,9 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     if (!out_on_device) {
         void *const dst[2] = {out_hdr, out_img};
         const void *const src[2] = {d_hdr, d_img};
-        if (int rc = copy_out(c, st, dst, src, 3 * tile_pixels * sizeof(T))) return rc;
+        if (int rc2 = copy_out(c, st, dst, src, 3 * tile_pixels * sizeof(T))) return rc2;
     }
-    if (int rc = mark_done(c, st)) return rc;
+    if (int rc2 = mark_done(c, st)) return rc2;
     if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
     lap("copy_out+sync");
     return 0;
@@ -1132,7 +1111,7 @@ int render_entry_plain(const spira_scene *h, const T *spheres5, const T *materia
 
 #ifdef SPIRA_TU_MAIN
 // A large frame for a host-pointer caller, rendered as row slabs: slab k's planes go device -> pinned staging on a second stream while slab k + 1
-// renders, and the host threads of copy_out move them on into the caller's memory.  The copy of a 1080p frame (Float64 HDR: 49.8 MB, 5 ms into
+// renders, and the host threads of StagedCopy move them on into the caller's memory.  The copy of a 1080p frame (Float64 HDR: 49.8 MB, 5 ms into
 // pageable memory — as long as rendering it) then hides behind the kernels but for the last slab's share.  The RNG is keyed by the global pixel, so
 // the slabs are, bit for bit, the rows of the frame rendered whole (tests/test_gpu_runtime.py); the counters of the call add up over its slabs.
 // *done = false: the frame is not of that kind (small, striped, progressive, ...) and nothing was touched — the caller takes the plain path.
@@ -1140,44 +1119,40 @@ template <class T>
 int render_host_slabs(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
                       T *out_hdr, T *out_img, bool *done) {
     *done = false;
-    if (!p || !camera12 || (!out_hdr && !out_img)) return 0;
     const uint32_t S_env = env_u32("SPIRA_HOST_SLABS", 0xFFFFFFFFu);                // (unset: chosen below; 0 or 1: never)
-    if (S_env < 2) return 0;
+    if (!p || S_env < 2) return 0;
     if ((p->flags & SPIRA_SEM_MASK) == SPIRA_SEM_HYBRID) return 0;                   // whole images only
     if (p->rows != 0 && p->stripe_count > 1) return 0;                               // an interleaved tile (its rows are not consecutive image rows)
-    // a mesh pass ends with the tail of its fat waves, and four small passes have four of them: configs[4] 6.2 -> 7.8 ms of device time, more than the copy hides
-    if ((h ? h->store.nt : (triangles10 ? p->n_triangles : 0)) > SPIRA_LDS_TRIANGLES) return 0;
-    const uint32_t W = p->width, rows = p->rows ? p->rows : p->height, row0 = p->rows ? p->row0 : 0;
-    if (!W || !rows || !p->spp || (uint64_t)row0 + rows > p->height) return 0;      // (the plain path reports what is wrong)
-    const int n_out = (out_hdr ? 1 : 0) + (out_img ? 1 : 0);
-    const size_t plane3 = (size_t)3 * rows * W * sizeof(T), total = plane3 * (size_t)n_out;
+    const uint64_t W = p->width, rows = p->rows ? p->rows : p->height, row0 = p->rows ? p->row0 : 0;
+    if (rows * W > 0x7FFFFFFFull) return 0;                                          // (the plain path reports what is wrong)
+    const uint64_t plane3 = 3 * rows * W * sizeof(T), total = plane3 * ((out_hdr ? 1 : 0) + (out_img ? 1 : 0));
     // a slab costs ~0.1 ms of device time (its own launches and their tails) and hides its share of the copy: two for a 1080p Float32 image (24.9 MB: 4.7 -> 4.0 ms
     // end to end), four from 32 MB on (1080p Float64 HDR, 49.8 MB: 7.3 -> 6.6 ms into touched memory; profiles/experiments/r04_host_slabs_probe.py)
-    const uint32_t S = S_env != 0xFFFFFFFFu ? std::min<uint32_t>(S_env, 16) : (total < ((size_t)32 << 20) ? 2u : 4u);
-    if (total < ((size_t)8 << 20) || total > ((size_t)512 << 20) || rows < 16 * S || (uint64_t)rows * W * p->spp < ((uint64_t)16 << 20)) return 0;
+    const uint32_t S = S_env != 0xFFFFFFFFu ? std::min<uint32_t>(S_env, 16) : (total < ((uint64_t)32 << 20) ? 2u : 4u);
+    if (total < ((uint64_t)8 << 20) || total > ((uint64_t)512 << 20) || rows < 16 * S || rows * W * p->spp < ((uint64_t)16 << 20)) return 0;
+    // a mesh pass ends with the tail of its fat waves, and four small passes have four of them: configs[4] 6.2 -> 7.8 ms of device time, more than the copy hides
+    if (h) { if (int rc = check_handle<T>(h)) return rc; }                           // (the plain path's first check too)
+    if ((h ? h->store.nt : (triangles10 ? p->n_triangles : 0)) > SPIRA_LDS_TRIANGLES) return 0;
+    // the frame will be rendered as slabs: the whole call is validated here, once, before anything is sized or allocated (its slabs skip it: SlabCtl)
+    uint32_t rows_checked = 0;
+    if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, false, 0, nullptr, &rows_checked)) return rc;
     Ctx *cp = nullptr;
     if (int rc = get_ctx(&cp)) return rc;
     Ctx &c = *cp;
     std::lock_guard<std::recursive_mutex> lock(c.mu);
-    if (c.h_stage_cap < total) {
-        if (c.h_stage) { (void)hipHostFree(c.h_stage); c.h_stage = nullptr; c.h_stage_cap = 0; }
-        if (hipHostMalloc(&c.h_stage, total, hipHostMallocDefault) == hipSuccess) c.h_stage_cap = total;
-        else { c.h_stage = nullptr; (void)hipGetLastError(); return 0; }                // no pinned memory to be had: the plain path still works
-    }
+    if (!stage_reserve(c, total)) return 0;
     if (!c.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
     if (!c.ev_slab) HIP_TRY(hipEventCreateWithFlags(&c.ev_slab, hipEventDisableTiming));
     if (int rc = order_after_previous(c, c.stream)) return rc;                       // (out_tmp may still be read by the previous call)
     if (int rc = c.out_tmp.ensure(2 * plane3)) return rc;
     *done = true;
     Lap lap("host slabs");
-    struct Piece { char *dst; size_t off, len; };
-    std::vector<Piece> pieces;
-    size_t off = 0;
+    StagedCopy sc(c);
     int rc_all = 0;
     for (uint32_t s = 0, r0 = 0; s < S && !rc_all; ++s) {
-        const uint32_t rs = rows / S + (s < rows % S ? 1u : 0u);
+        const uint32_t rs = (uint32_t)(rows / S + (s < rows % S ? 1u : 0u));
         spira_params ps = *p;
-        ps.row0 = row0 + r0; ps.rows = rs; ps.stripe_h = 0; ps.stripe_count = 0; ps.stripe_rank = 0;
+        ps.row0 = (uint32_t)row0 + r0; ps.rows = rs; ps.stripe_h = 0; ps.stripe_count = 0; ps.stripe_rank = 0;
         // the slab's planar block [3][rs][W] sits at element 3 * W * r0 of its output's device frame
         T *d_hdr = out_hdr ? (T *)c.out_tmp.p + (size_t)3 * W * r0 : nullptr;
         T *d_img = out_img ? (T *)((char *)c.out_tmp.p + plane3) + (size_t)3 * W * r0 : nullptr;
@@ -1188,23 +1163,9 @@ int render_host_slabs(const spira_scene *h, const T *spheres5, const T *material
         if (e == hipSuccess) e = hipStreamWaitEvent(c.copy_stream, c.ev_slab, 0);
         T *const dev[2] = {d_hdr, d_img};
         T *const host[2] = {out_hdr, out_img};
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-            if (!host[k]) continue;
-            for (int pl = 0; pl < 3 && e == hipSuccess; ++pl) {
-                const size_t len = (size_t)rs * W * sizeof(T);
-                e = hipMemcpyAsync((char *)c.h_stage + off, dev[k] + (size_t)pl * rs * W, len, hipMemcpyDeviceToHost, c.copy_stream);
-                if (e != hipSuccess) break;
-                if (c.stage_ev.size() <= pieces.size()) {
-                    hipEvent_t ev;
-                    e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-                    if (e != hipSuccess) break;
-                    c.stage_ev.push_back(ev);
-                }
-                e = hipEventRecord(c.stage_ev[pieces.size()], c.copy_stream);
-                pieces.push_back({(char *)(host[k] + ((size_t)pl * rows + r0) * W), off, len});
-                off += len;
-            }
-        }
+        for (int k = 0; k < 2; ++k)
+            for (int pl = 0; host[k] && pl < 3 && e == hipSuccess; ++pl)
+                e = sc.stage(c.copy_stream, host[k] + ((size_t)pl * rows + r0) * W, dev[k] + (size_t)pl * rs * W, (size_t)rs * W * sizeof(T));
         if (e != hipSuccess) rc_all = fail(SPIRA_E_HIP, std::string("host-output slabs: ") + hipGetErrorString(e));
         r0 += rs;
     }
@@ -1213,26 +1174,11 @@ int render_host_slabs(const spira_scene *h, const T *spheres5, const T *material
         return rc_all;
     }
     lap("enqueue");
-    const int n_thr = (int)std::min<size_t>(std::max<uint32_t>(1, env_u32("SPIRA_STAGE_THREADS", 4)), pieces.size());
-    std::vector<hipError_t> errs((size_t)n_thr, hipSuccess);
-    const bool prefault = env_u32("SPIRA_PREFAULT", 1) != 0;
-    auto mover = [&](int t) {
-        (void)hipSetDevice(c.device);
-        if (prefault) for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) prefault_destination(pieces[i].dst, pieces[i].len);
-        for (size_t i = (size_t)t; i < pieces.size(); i += (size_t)n_thr) {
-            const hipError_t e = hipEventSynchronize(c.stage_ev[i]);
-            if (e != hipSuccess) { errs[(size_t)t] = e; return; }
-            std::memcpy(pieces[i].dst, (const char *)c.h_stage + pieces[i].off, pieces[i].len);
-        }
-    };
-    std::vector<std::thread> thr;
-    for (int t = 1; t < n_thr; ++t) thr.emplace_back(mover, t);
-    mover(0);
-    for (auto &t : thr) t.join();
+    const hipError_t moved = sc.move();
     lap("movers");
     HIP_TRY(hipStreamSynchronize(c.copy_stream));
     HIP_TRY(hipStreamSynchronize(c.stream));
-    for (hipError_t e : errs) if (e != hipSuccess) return fail(SPIRA_E_HIP, std::string("host-output slabs: ") + hipGetErrorString(e));
+    if (moved != hipSuccess) return fail(SPIRA_E_HIP, std::string("host-output slabs: ") + hipGetErrorString(moved));
     return 0;
 }
 #endif

@@ -1,0 +1,234 @@
+// spira_plan.h — the launch plan of a render call: organisation, pass split, launch geometry and the size of every workspace, as pure integer
+// arithmetic on the call's parameters (no HIP headers, no getenv: also built into the sanitizer harness tests/native/host_sanitize.cpp, which sweeps
+// it under ASan + UBSan).  spira_hip.hip fills PlanIn — the constants of spira_device.h and the SPIRA_* knobs included — sizes the context's
+// workspaces from Plan::ws and hands the plan to the organisation's enqueue function; verify_path_args() takes path_need() for its numbers.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+
+#include "../../include/spira_hip.h"
+
+namespace spira {
+
+// Every SPIRA_* environment value the plan and the k_path arguments depend on (read once per call by spira_hip.hip, read_knobs: defaults and clamps there).
+struct Knobs {
+    uint32_t batch_rays = 160u << 20;          // SPIRA_BATCH_RAYS: rays per pass where spira_params::batch_rays is 0
+    uint32_t R = 2;                            // SPIRA_R: rays per lane (1 or 2)
+    uint32_t blocks_per_cu = 0;                // SPIRA_BLOCKS_PER_CU; 0: the organisation's own (make_plan)
+    uint32_t defer_mesh = 1, mesh_two_pass = 1, fused_resolve = 1, private_l = 1;
+    uint32_t spec_div = 1;                     // SPIRA_SPEC_DIV: 0 off, 1 where the scene's scale allows, 2 report every wave, 3 on whatever the scale
+    uint32_t dense_pct = 70, mesh_min_batch = 128, mesh_refill = 16, mesh_fat_waves_per_cu = 16, cam_consts = 1;
+};
+
+struct PlanIn {
+    uint32_t width = 0, rows = 0;              // the tile (rows: after validate_params)
+    uint32_t spp = 0, max_depth = 0, flags = 0, batch_rays = 0;
+    uint32_t n_triangles = 0;                  // of the scene
+    uint32_t num_cus = 0;
+    bool progressive = false, caller_rng = false, out_on_device = false;      // (caller_rng: a progressive call that hands LCG states in and out)
+    // the constants of spira_device.h the arithmetic needs (gfx950: 256, 5 / 4, 1, 16- and 32-byte packets)
+    uint32_t prec = 0, block = 0, waves_per_simd = 0, carry_key = 0;          // sizeof(T), kBlock, SPIRA_WAVES_F32 / F64, SPIRA_CARRY_KEY
+    uint32_t pack4 = 0, pack3 = 0, pack2 = 0;                                 // sizeof(Pack4<T>), ...
+    Knobs k;
+};
+
+enum class Org { Black, Hybrid, MetalWavefront, Metal, Cpu, Mega, Path, Bounce };      // (Black: max_depth 0, every pixel is zero)
+
+struct Geometry { uint32_t G, cap; };          // workgroups of a wavefront launch; rays of each of its waves' queue regions
+
+// Bytes each workspace of the context must hold for the call (0: the call does not touch it).
+struct Workspace {
+    uint64_t queue4 = 0, queue2 = 0, q_ref = 0, q_key = 0, q_x = 0;          // per parity: qA / qB, qC, qR, qK, qX
+    uint64_t mesh_list = 0, mesh_count = 0, redo = 0, blkstats = 0, L = 0, counts = 0, accum = 0, out_tmp = 0, rng = 0;
+    uint64_t hyb_state = 0, hyb_mat = 0, hyb_flags = 0;
+};
+
+struct Plan {
+    PlanIn in;
+    Org org = Org::Black;
+    uint32_t R = 2, wpb = 0, sub = 0, max_blocks = 0;      // rays per lane, waves per workgroup, rays per wave sub-chunk, grid limit
+    uint64_t tile_pixels = 0, batch = 0;                   // batch: paths of the largest pass
+    uint32_t slots = 0, n_pass = 0;                        // samples of every pixel per pass; passes (equal: spp 256 at 80 slots -> 4 x 64, not 3 x 80 + 16)
+    bool mesh_scene = false, defer_mesh = false, two_pass = false;      // a BVH scene; its traversal deferred (mesh lists); ... as a second, fat-wave launch
+    bool fused = false, l_private = false;                 // pixel-owning passes (PathArgs::accum); wave-private radiance blocks (PathArgs::l_private)
+    bool spec_allowed = false;                             // the organisation has a speculative-division launch for this call
+    uint32_t G_max = 0, cap_max = 0;                       // geometry of the largest pass
+    uint64_t q_rays = 0;
+    uint32_t ppw = 0, G_metal = 0;                         // MetalWavefront: pixels per wave, workgroups
+    Workspace ws;
+
+    Geometry geometry(uint64_t n_first) const {
+        if (fused) {                                       // one wave per 64 pixels; its region holds all its paths
+            const uint64_t k = n_first / tile_pixels;
+            return {(uint32_t)((tile_pixels + 64 * wpb - 1) / (64 * wpb)), (uint32_t)((64 * k + sub - 1) / sub * sub)};
+        }
+        const uint64_t n_sub = (n_first + sub - 1) / sub;
+        const uint32_t G = (uint32_t)std::min<uint64_t>((n_sub + wpb - 1) / wpb, max_blocks);
+        const uint64_t nw = (uint64_t)G * wpb;
+        return {G, (uint32_t)(((n_sub + nw - 1) / nw) * sub)};
+    }
+    uint32_t k_eff(uint32_t pass) const { return std::min(slots, in.spp - pass * slots); }
+    uint32_t n_first(uint32_t pass) const { return (uint32_t)((uint64_t)k_eff(pass) * tile_pixels); }
+    // grid of a kernel that gives every item (pixel, path) a lane
+    uint32_t blocks(uint64_t n) const { return (uint32_t)std::min<uint64_t>((n + in.block - 1) / in.block, max_blocks); }
+    // the fat waves of a mesh pass's second launch: about 16 per CU (4 per SIMD), each taking over k <= 16 of the first launch's nw waves; k divides nw
+    uint32_t fat_k(uint32_t nw) const {
+        const uint32_t fat = std::max<uint32_t>(1, in.num_cus * in.k.mesh_fat_waves_per_cu);
+        uint32_t k = 16;
+        while (k > 1 && (nw % k != 0 || nw / k < fat)) k >>= 1;
+        return k;
+    }
+    // Speculative division (spira_device.h, SpecDiv): 0 off, 1 the speculative launch and the exact one over the waves it reported, 2 every wave
+    // reported (the whole pass is rendered twice; tests).  +7 % on S1 while (almost) no wave has to be rendered again, which is what a scene and
+    // camera of ordinary magnitudes give (`moderate`); a scene scaled to 1e-30 would have every wave rendered twice, so it is not tried there.
+    int spec(bool moderate) const {
+        uint32_t s = spec_allowed ? in.k.spec_div : 0;
+        if (s == 1 && !moderate) s = 0;
+        return s > 2 ? 1 : (int)s;
+    }
+};
+
+inline int sample_range_check(bool progressive, uint32_t sample0, uint32_t spp, const char **msg) {
+    if (progressive && (uint64_t)sample0 + spp > SPIRA_MAX_SPP) { *msg = "sample0 + spp exceeds 2^24"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+
+// Returns 0 or a negative SPIRA_E_* code and a static message.
+inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
+    auto bad = [&](const char *m) { *msg = m; return SPIRA_E_LIMIT; };
+    pl = Plan{};
+    pl.in = in;
+    const Knobs &k = in.k;
+    const uint32_t sem = in.flags & SPIRA_SEM_MASK, kern = in.flags & SPIRA_KERNEL_MASK;
+    const bool ext = (in.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    const uint64_t tp = pl.tile_pixels = (uint64_t)in.rows * in.width;
+    // default pass size: 160 Mi rays (a 1080p x 64 spp frame is one pass); ~16 GB (f32) / 31 GB (f64) of the 288 GB
+    const uint32_t target = in.batch_rays ? in.batch_rays : k.batch_rays;
+    uint64_t slots = std::min<uint64_t>(std::max<uint64_t>(1, target / tp), in.spp);
+    const uint64_t n_pass = (in.spp + slots - 1) / slots;
+    slots = (in.spp + n_pass - 1) / n_pass;
+    if (slots * tp > 0x7FFFFFFFull) return bad("tile too large: rows*width must be < 2^31");
+    pl.slots = (uint32_t)slots;
+    pl.n_pass = (in.spp + pl.slots - 1) / pl.slots;
+    pl.batch = slots * tp;
+    // the secondary estimators run one lane per path / per pixel (SPIRA_SEM_METAL: or one wave per block of pixels): no passes of bounce kernels
+    pl.org = sem == SPIRA_SEM_HYBRID ? Org::Hybrid : sem == SPIRA_SEM_METAL ? (kern == SPIRA_KERNEL_WAVEFRONT ? Org::MetalWavefront : Org::Metal) :
+             sem == SPIRA_SEM_CPU ? Org::Cpu : kern == SPIRA_KERNEL_MEGA ? Org::Mega : kern == SPIRA_KERNEL_BOUNCE ? Org::Bounce : Org::Path;
+    const bool persistent = pl.org == Org::Path;                  // k_path: one launch per pass
+    pl.R = (k.R == 1 && !ext) ? 1 : 2;                            // (the extension instantiations exist for R = 2 only)
+    pl.mesh_scene = in.n_triangles > SPIRA_LDS_TRIANGLES;
+    pl.defer_mesh = persistent && pl.mesh_scene && in.max_depth <= 128 && k.defer_mesh != 0;
+    pl.two_pass = pl.defer_mesh && k.mesh_two_pass != 0;
+
+    // ---- launch geometry: NW = 4*G autonomous waves per wavefront kernel, each owning `cap` rays of both queues
+    // workgroups per CU: the persistent kernel runs a whole pass per launch, so its launch tail is one workgroup's share of the
+    // pass: 32 per CU (8 rounds of resident workgroups) measured best on S1 (16: -3.5 %, 64: -1 %, 128: -5 %; S3 likes 64-128, +1.7 %)
+    // Mesh scenes want fewer, fatter waves: a wave's round ends with the dense traversal of the rays it parked at the mesh's box, and a
+    // traversal batch costs its slowest ray's chain of dependent node fetches whether it holds 64 rays or 10 (config 5, 81 920 triangles:
+    // f32 32 per CU 7.54 ms, 16: 6.78, 8: 7.29, 4: 7.04; f64 32: 11.67, 8: 10.29, 4: 9.68; re-measured with the round's final kernels: f32 16: 6.83, 8: 7.02, 32: 7.39,
+    // f64 4: 9.54, 8: 10.13, 16: 10.49 — and counts that are not powers of two lose 10-40 %: the grid no longer divides evenly over 8 XCDs x 32 CUs).
+    const uint32_t blocks_per_cu = k.blocks_per_cu ? k.blocks_per_cu : !persistent ? 16 : (pl.mesh_scene && !pl.two_pass) ? 4 : 32;
+    pl.max_blocks = (uint32_t)std::min<uint64_t>((uint64_t)in.num_cus * blocks_per_cu, 0x7FFFFFFFull);
+    pl.wpb = in.block / 64;
+    pl.sub = 64 * pl.R;
+    // pixel-owning passes (PathArgs::accum): each wave sums its own 64 pixels at its end instead of k_resolve streaming the whole of L after the
+    // launch — S1 Float64 -1.5 … -4.5 %.  Only where that was measured to pay: Float64 scenes of spheres alone, no extension, at most 64 slots per pass.
+    // In Float32 the end-of-wave sum costs k_path what k_resolve costs (S1 +0.30 / 0.29 ms); in the kernels with the LDS triangle scan or the
+    // extensions its code costs spilled registers (glass scene Float64 +15 %, S2 +4 %).  SPIRA_FUSED_RESOLVE=0: round-robin dealing + k_resolve (A/B, tests).
+    // (R = 2 too: the instantiation of SPIRA_R=1 is compiled with the triangle scan.)
+    pl.fused = persistent && in.prec == 8 && pl.R == 2 && in.n_triangles == 0 && !ext && pl.slots <= 64 && k.fused_resolve != 0;
+    const Geometry g = pl.geometry(pl.batch);
+    pl.G_max = g.G; pl.cap_max = g.cap;
+    const uint64_t waves = (uint64_t)g.G * pl.wpb;
+    // ... and keep the radiance of their paths in one contiguous block per wave (PathArgs::l_private) wherever the queue word is free to address it: the
+    // RNG key is carried through the queue for max_depth <= 128 (deeper renders derive it from the path index and keep the slot-major L), and the
+    // queue word has 31 bits for the entry of L.  SPIRA_PRIVATE_L=0: the slot-major layout (A/B).
+    pl.l_private = pl.fused && in.carry_key && in.max_depth <= 128 && k.private_l != 0 && 64ull * waves * pl.slots <= 0x7FFFFFFFull;
+    pl.q_rays = (uint64_t)g.cap * waves;
+    if (pl.q_rays > 0xFFFFFFFFull) return bad("pass too large");
+    // the speculative launch: fresh renders only (a progressive SPIRA_SEM_METAL call updates sums and states in place), R = 2 instantiations only
+    pl.spec_allowed = pl.org == Org::Cpu || (pl.org == Org::Metal && !in.progressive) || (pl.org == Org::MetalWavefront && !in.progressive && pl.R == 2) ||
+                      (persistent && pl.R == 2);
+    if (in.max_depth == 0) pl.org = Org::Black;
+
+    // ---- workspaces (cached per device, grown on demand; sized for 288 GB HBM: no chunking of a pass)
+    Workspace &w = pl.ws;
+    const uint64_t redo_per_wave = (pl.spec_allowed && k.spec_div) ? sizeof(uint32_t) : 0, stat_row = 4 * sizeof(uint32_t);
+    w.accum = tp * in.pack4;
+    w.out_tmp = in.out_on_device ? 0 : 2 * 3 * tp * in.prec;
+    if (in.caller_rng && !in.out_on_device) w.rng = tp * sizeof(uint32_t);
+    switch (pl.org) {
+    case Org::Black: break;
+    case Org::Hybrid:                      // per-pixel ray state between its launches, one flag per launch
+        if (tp > 0xFFFFFFFFull / 2) return bad("image too large for SPIRA_SEM_HYBRID");
+        w.hyb_state = 12 * tp * in.prec; w.hyb_mat = w.rng = tp * sizeof(uint32_t);
+        w.hyb_flags = (uint64_t)in.spp * (in.max_depth + 1) * sizeof(uint32_t);
+        break;
+    case Org::MetalWavefront: {            // every wave owns a block of ppw pixels: one resident round of workgroups
+        const uint64_t nw0 = (uint64_t)in.num_cus * in.waves_per_simd * pl.wpb;
+        pl.ppw = (uint32_t)((((tp + nw0 - 1) / nw0) + 63) / 64 * 64);
+        pl.G_metal = (uint32_t)((tp + (uint64_t)pl.ppw * pl.wpb - 1) / ((uint64_t)pl.ppw * pl.wpb));
+        const uint64_t nw = (uint64_t)pl.G_metal * pl.wpb, n = nw * pl.ppw;
+        w.queue4 = n * in.pack4; w.queue2 = n * in.pack2; w.q_x = n * 2 * sizeof(uint32_t); w.L = n * in.pack3;
+        if (!in.caller_rng) w.rng = tp * sizeof(uint32_t);
+        w.blkstats = nw * stat_row; w.redo = nw * redo_per_wave;
+        break;
+    }
+    case Org::Metal: case Org::Cpu: case Org::Mega:
+        w.L = pl.batch * in.pack3; w.blkstats = waves * stat_row;
+        w.redo = (pl.org == Org::Metal ? pl.blocks(tp) : pl.org == Org::Cpu ? pl.max_blocks : 0) * (uint64_t)pl.wpb * redo_per_wave;
+        break;
+    case Org::Bounce:                      // per-wave survivor counts and one row of statistics per wave per launch
+        if (in.max_depth > 1) { w.queue4 = pl.q_rays * in.pack4; w.queue2 = pl.q_rays * in.pack2; }
+        w.L = pl.batch * in.pack3;
+        w.counts = (uint64_t)(in.max_depth + 2) * waves * sizeof(uint32_t); w.blkstats = (uint64_t)(in.max_depth + 1) * waves * stat_row;
+        break;
+    case Org::Path:
+        // hit queues, one entry per ray of the largest pass (worst case: every path queued / parked once).  max_depth == 1 needs none — except on a
+        // mesh scene: a parked camera ray's hit comes back from its traversal session as a packet.
+        if (in.max_depth > 1 || pl.mesh_scene) {
+            w.queue4 = pl.q_rays * in.pack4; w.queue2 = pl.q_rays * in.pack2;
+            if (in.prec == 4) w.q_ref = pl.q_rays * sizeof(uint32_t);
+            if (!pl.defer_mesh) w.q_key = pl.q_rays * 2 * sizeof(uint32_t);      // carried RNG keys (sphere scenes; the extension launches leave them unused)
+        }
+        if (pl.defer_mesh) w.mesh_list = 3 * pl.q_rays * in.pack4;               // the wave-owned lists of rays waiting for their dense traversal batch
+        if (pl.two_pass) w.mesh_count = waves * sizeof(uint32_t);                // per-wave parked counts, from the parking launch to the fat-wave launch
+        w.redo = waves * redo_per_wave; w.blkstats = waves * stat_row;
+        // (a pixel-owning grid depends on the pixel count alone: G_max workgroups in every pass, each wave with a block of 64 * slots entries)
+        w.L = (pl.l_private ? std::max<uint64_t>(pl.batch, 64ull * waves * pl.slots) : pl.batch) * in.pack3;
+        break;
+    }
+    return 0;
+}
+
+// ---- what a k_path launch needs of the workspaces, on counts: verify_path_args() (spira_hip.hip) compares these with the buffers behind the
+// pointers of the PathArgs about to be launched; the sanitizer harness with Plan::ws, for every pass of every plan of its sweep.
+struct PathLaunch {
+    uint32_t blocks = 0, cap = 0, n_first = 0, k_eff = 0;      // blocks: of the pass's first launch (a fat wave of the second owns the regions of the waves it takes over)
+    uint32_t tile_pixels = 0, max_depth = 0, flags = 0, n_lds_triangles = 0;
+    uint32_t mesh_mode = 0, resume_k = 1, resume_nw = 0;
+    bool mesh = false, pixel_owning = false, l_private = false;
+    uint32_t prec = 0, wpb = 0, carry_key = 0;
+};
+struct PathNeed {
+    uint64_t nw, packets, l_entries;       // waves; entries of every per-packet array; entries of L
+    bool fits, resume_ok, owning_ok, private_ok;
+};
+inline PathNeed path_need(const PathLaunch &a) {
+    PathNeed n{};
+    n.nw = (uint64_t)a.blocks * a.wpb;
+    n.packets = n.nw * a.cap;
+    n.fits = a.n_first <= n.packets;
+    n.resume_ok = a.resume_k != 0 && a.resume_k <= 16 && n.nw % a.resume_k == 0 && a.resume_nw == n.nw;
+    // (wave-private radiance blocks: 64 k_eff entries for every wave of the grid, more than n_first when the tile's pixel count is no multiple of 64 * waves per workgroup)
+    n.l_entries = a.l_private ? std::max<uint64_t>(a.n_first, 64ull * n.nw * a.k_eff) : a.n_first;
+    // pixel-owning pass: an instantiation that resolves, a wave for every pixel, every wave's paths in its region
+    const uint64_t tp = a.tile_pixels;
+    n.owning_ok = a.prec == 8 && !a.n_lds_triangles && !a.mesh && !(a.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) && a.k_eff != 0 && a.k_eff <= 64 &&
+                  (uint64_t)a.k_eff * tp == a.n_first && 64 * n.nw >= tp && a.cap >= 64ull * a.k_eff;
+    // wave-private radiance blocks: pixel-owning passes whose queue word need not be the path index (the RNG key is carried: max_depth <= 128)
+    n.private_ok = a.pixel_owning && a.carry_key && a.max_depth <= 128 && n.l_entries <= 0x80000000ull;
+    return n;
+}
+
+}  // namespace spira

@@ -1,7 +1,8 @@
 // host_sanitize.cpp — host-only harness built with -fsanitize=address,undefined (tests/test_native_sanitize.py).
 // GPU AddressSanitizer is not available on the pool, so everything of the product that runs on the HOST is exercised here
 // under ASan + UBSan: the BVH builder (spira_bvh.h) over degenerate meshes, the scene validation (spira_validate.h), the
-// magic-number division (spira_fastdiv.h) and the triangle hash; the CPU oracle is linked in and run under the sanitizers too.
+// magic-number division (spira_fastdiv.h), the triangle hash and the launch plan of a render call (spira_plan.h), swept over the parameter space;
+// the CPU oracle is linked in and run under the sanitizers too.
 // The tree is checked semantically: a host traversal with the kernels' rules (8-wide quantised nodes, Float32 slab tests in the mesh's
 // normalised frame, octant-ordered descent, leaf = Moller-Trumbore in T, ties to the later triangle) must return exactly what a
 // linear scan over the caller's array returns.
@@ -15,6 +16,7 @@
 #include "../../julia-spira_amd/csrc/spira_bvh.h"
 #include "../../julia-spira_amd/csrc/spira_fastdiv.h"
 #include "../../julia-spira_amd/csrc/spira_validate.h"
+#include "../../julia-spira_amd/csrc/spira_plan.h"
 #include "../../include/spira_hip.h"
 
 #ifndef SPIRA_NO_ORACLE
@@ -307,6 +309,158 @@ static void validation_checks() {
     CHECK(!spira::bvh_build<float>(nullptr, (1u << 24) + 1, nodes, tris, fr));                    // over the 2^24 limit: rejected before any read
 }
 
+// ---- the launch plan (spira_plan.h) with the constants of spira_device.h on gfx950: workgroups of 256, 5 / 4 waves per SIMD, carried RNG keys,
+// 16- / 32-byte packets.  Every accepted plan must give each launch of each pass what verify_path_args() would ask of the workspaces at run time.
+static spira::PlanIn plan_in(uint32_t prec, uint32_t w, uint32_t rows, uint32_t spp, uint32_t depth, uint32_t flags, uint32_t batch, uint32_t nt, uint32_t cus) {
+    spira::PlanIn in;
+    in.width = w; in.rows = rows; in.spp = spp; in.max_depth = depth; in.flags = flags; in.batch_rays = batch; in.n_triangles = nt; in.num_cus = cus;
+    in.prec = prec; in.block = 256; in.waves_per_simd = prec == 8 ? 4 : 5; in.carry_key = 1;
+    in.pack4 = 4 * prec; in.pack3 = 3 * prec; in.pack2 = 2 * prec;
+    return in;
+}
+
+static uint64_t g_plans = 0, g_refused = 0, g_launches = 0, g_org[8] = {0};
+
+static void check_path_pass(const spira::Plan &pl, uint32_t pass) {
+    const spira::PlanIn &in = pl.in;
+    const spira::Workspace &w = pl.ws;
+    const uint32_t n_first = pl.n_first(pass);
+    const spira::Geometry g = pl.geometry(n_first);
+    spira::PathLaunch l;
+    l.blocks = g.G; l.cap = g.cap; l.n_first = n_first; l.k_eff = pl.fused ? pl.k_eff(pass) : 0;
+    l.tile_pixels = (uint32_t)pl.tile_pixels; l.max_depth = in.max_depth; l.flags = in.flags; l.n_lds_triangles = pl.mesh_scene ? 0 : in.n_triangles;
+    l.mesh = pl.mesh_scene; l.pixel_owning = pl.fused; l.l_private = pl.l_private;
+    l.prec = in.prec; l.wpb = pl.wpb; l.carry_key = in.carry_key;
+    if (pl.two_pass) { l.mesh_mode = 1; l.resume_nw = g.G * pl.wpb; l.resume_k = pl.fat_k(l.resume_nw); }
+    const spira::PathNeed n = spira::path_need(l);
+    CHECK(g.G >= 1 && n.nw <= 0xFFFFFFFFull && n.packets <= pl.q_rays && n.fits);
+    if (in.max_depth > 1 || l.mesh) {
+        CHECK(w.queue4 >= n.packets * in.pack4 && w.queue2 >= n.packets * in.pack2);
+        CHECK(in.prec != 4 || w.q_ref >= n.packets * 4);
+        CHECK(l.mesh || w.q_key >= n.packets * 8);
+    }
+    CHECK(!pl.defer_mesh || w.mesh_list >= 3 * n.packets * in.pack4);
+    if (l.mesh_mode) CHECK(pl.defer_mesh && w.mesh_count >= n.nw * 4 && n.resume_ok && l.resume_k <= 16 && n.nw % l.resume_k == 0);
+    CHECK(!pl.spec(true) || w.redo >= n.nw * 4);
+    CHECK(w.blkstats >= n.nw * 16 && w.L >= n.l_entries * in.pack3 && w.accum >= pl.tile_pixels * in.pack4);
+    if (pl.fused) CHECK(n.owning_ok && 64 * n.nw >= pl.tile_pixels);
+    if (pl.l_private) CHECK(pl.fused && n.private_ok && n.l_entries <= 0x80000000ull);
+    ++g_launches;
+}
+
+static void check_plan(const spira::PlanIn &in) {
+    using spira::Org;
+    spira::Plan pl;
+    const char *msg = nullptr;
+    const int rc = spira::make_plan(in, pl, &msg);
+    const uint64_t tp = (uint64_t)in.rows * in.width;
+    ++g_plans;
+    if (rc) { CHECK(rc == SPIRA_E_LIMIT && msg != nullptr); ++g_refused; return; }
+    const spira::Workspace &w = pl.ws;
+    ++g_org[(int)pl.org];
+    // the pass split, in 64 bits: equal passes that add up to spp, none of them beyond 2^31 - 1 paths
+    CHECK(pl.tile_pixels == tp && pl.slots >= 1 && pl.slots <= in.spp && (uint64_t)pl.slots * tp <= 0x7FFFFFFFull && pl.batch == (uint64_t)pl.slots * tp);
+    CHECK(pl.n_pass >= 1 && (uint64_t)pl.n_pass * pl.slots >= in.spp && (uint64_t)(pl.n_pass - 1) * pl.slots < in.spp);
+    CHECK(pl.k_eff(pl.n_pass - 1) == in.spp - (uint64_t)(pl.n_pass - 1) * pl.slots);      // (every earlier pass: `slots`, so the sum is spp)
+    CHECK((in.max_depth == 0) == (pl.org == Org::Black) && (pl.R == 1 || pl.R == 2) && pl.wpb == 4 && pl.sub == 64 * pl.R && pl.max_blocks >= 1);
+    CHECK((uint64_t)pl.G_max * pl.wpb * pl.cap_max == pl.q_rays && pl.q_rays <= 0xFFFFFFFFull && pl.q_rays >= pl.batch);
+    CHECK(!pl.l_private || 64ull * pl.G_max * pl.wpb * pl.slots <= 0x7FFFFFFFull);
+    for (bool moderate : {false, true}) { const int s = pl.spec(moderate); CHECK(s >= 0 && s <= 2 && (s == 0 || pl.spec_allowed) && (moderate || s != 1 || in.k.spec_div != 1)); }
+    CHECK(w.accum == tp * in.pack4 && (in.out_on_device ? w.out_tmp == 0 : w.out_tmp == 6 * tp * in.prec));
+    CHECK(!(in.caller_rng && !in.out_on_device) || w.rng >= tp * 4);
+    const uint32_t probes[] = {0, 1, pl.n_pass / 2, pl.n_pass - 1};
+    uint64_t sum = 0;
+    if (pl.n_pass <= 4096) { for (uint32_t p = 0; p < pl.n_pass; ++p) sum += pl.k_eff(p); CHECK(sum == in.spp); }
+    for (uint32_t pass : probes) {
+        if (pass >= pl.n_pass) continue;
+        const uint64_t n_first = (uint64_t)pl.k_eff(pass) * tp;
+        CHECK(pl.k_eff(pass) >= 1 && pl.k_eff(pass) <= pl.slots && n_first == pl.n_first(pass) && n_first <= pl.batch);
+        const uint64_t lane_blocks = pl.blocks(n_first);
+        switch (pl.org) {
+        case Org::Path: check_path_pass(pl, pass); break;
+        case Org::Bounce: {
+            const spira::Geometry g = pl.geometry(n_first);
+            const uint64_t nw = (uint64_t)g.G * pl.wpb;
+            CHECK(g.G >= 1 && g.G <= pl.max_blocks && nw * g.cap >= n_first && nw * g.cap <= pl.q_rays);
+            CHECK(in.max_depth == 1 || (w.queue4 >= nw * g.cap * in.pack4 && w.queue2 >= nw * g.cap * in.pack2));
+            CHECK(w.counts >= (uint64_t)(in.max_depth + 1) * nw * 4 && w.blkstats >= (uint64_t)in.max_depth * nw * 16 && w.L >= n_first * in.pack3);
+            break;
+        }
+        case Org::Cpu: case Org::Mega:
+            CHECK(lane_blocks >= 1 && lane_blocks <= pl.max_blocks && w.L >= n_first * in.pack3);
+            CHECK(pl.org != Org::Cpu || !pl.spec(true) || w.redo >= lane_blocks * pl.wpb * 4);
+            break;
+        default: break;
+        }
+    }
+    if (pl.org == Org::Metal) CHECK(w.L >= tp * in.pack3 && (!pl.spec(true) || w.redo >= (uint64_t)pl.blocks(tp) * pl.wpb * 4));
+    if (pl.org == Org::MetalWavefront) {
+        const uint64_t nw = (uint64_t)pl.G_metal * pl.wpb, n = nw * pl.ppw;
+        CHECK(pl.ppw >= 64 && pl.ppw % 64 == 0 && pl.G_metal >= 1 && n >= tp && (nw - pl.wpb) * pl.ppw < tp && n <= 0xFFFFFFFFull);      // a wave for every pixel, no workgroup without one
+        CHECK(w.queue4 >= n * in.pack4 && w.queue2 >= n * in.pack2 && w.q_x >= n * 8 && w.L >= n * in.pack3 && w.blkstats >= nw * 16);
+        CHECK((in.caller_rng || w.rng >= tp * 4) && (!pl.spec(true) || w.redo >= nw * 4));
+    }
+    if (pl.org == Org::Hybrid) CHECK(w.hyb_state == 12 * tp * in.prec && w.hyb_mat == tp * 4 && w.rng == tp * 4 && w.hyb_flags == (uint64_t)in.spp * (in.max_depth + 1) * 4);
+}
+
+static void plan_checks() {
+    using spira::Org;
+    {   // plans the code's comments and tests name
+        const char *msg = nullptr;
+        spira::Plan pl;
+        CHECK(spira::make_plan(plan_in(8, 1920, 1080, 64, 8, 0, 0, 0, 256), pl, &msg) == 0);         // S1 Float64 at 1080p: one pixel-owning pass of 64 slots
+        CHECK(pl.org == Org::Path && pl.slots == 64 && pl.n_pass == 1 && pl.fused && pl.l_private && pl.G_max == (1920 * 1080 + 255) / 256 && pl.cap_max == 64 * 64);
+        CHECK(pl.geometry(pl.n_first(0)).G == 8100 && pl.spec(true) == 1 && pl.spec(false) == 0);
+        CHECK(spira::make_plan(plan_in(8, 1920, 1080, 256, 8, 0, 80u * 1920 * 1080, 0, 256), pl, &msg) == 0);      // spp 256 at 80 slots: 4 x 64, not 3 x 80 + 16
+        CHECK(pl.slots == 64 && pl.n_pass == 4 && pl.k_eff(3) == 64);
+        CHECK(spira::make_plan(plan_in(4, 1920, 1080, 64, 8, 0, 0, 0, 256), pl, &msg) == 0);         // Float32: round-robin dealing, 32 workgroups per CU
+        CHECK(pl.slots == 64 && !pl.fused && !pl.l_private && pl.G_max == 256 * 32 && (uint64_t)pl.G_max * 4 * pl.cap_max >= pl.batch);
+        CHECK(spira::make_plan(plan_in(8, 1920, 1080, 64, 12, 0, 0, 81920, 256), pl, &msg) == 0);     // config 5: parking launch + fat waves, 16 per CU
+        CHECK(pl.mesh_scene && pl.defer_mesh && pl.two_pass && !pl.fused && pl.G_max == 256 * 32 && pl.fat_k(pl.G_max * 4) == 8);
+        CHECK(spira::make_plan(plan_in(8, 1920, 1080, 64, 200, 0, 0, 81920, 256), pl, &msg) == 0 && !pl.defer_mesh && pl.G_max == 256 * 4);      // too deep to carry the key
+        CHECK(spira::make_plan(plan_in(8, 0x7FFFFFFFu, 1, 1, 8, 0, 0, 0, 256), pl, &msg) == SPIRA_E_LIMIT && std::strcmp(msg, "pass too large") == 0);
+        CHECK(spira::sample_range_check(true, (1u << 24) - 3, 4, &msg) == SPIRA_E_LIMIT && spira::sample_range_check(true, (1u << 24) - 4, 4, &msg) == 0 &&
+              spira::sample_range_check(false, 0xFFFFFFFFu, 4, &msg) == 0);
+    }
+    spira::Knobs off;       // every switch at its off value
+    off.R = 1; off.defer_mesh = off.mesh_two_pass = off.fused_resolve = off.private_l = off.spec_div = off.cam_consts = 0; off.dense_pct = 0; off.mesh_min_batch = off.mesh_refill = 1;
+    spira::Knobs lo, hi;    // every number at an extreme
+    lo.batch_rays = 1; lo.blocks_per_cu = 1; lo.mesh_fat_waves_per_cu = 0; lo.spec_div = 2; lo.R = 0;
+    hi.batch_rays = 0xFFFFFFFFu; hi.blocks_per_cu = 1024; hi.mesh_fat_waves_per_cu = 1u << 20; hi.spec_div = 3; hi.R = 7; hi.dense_pct = 100; hi.mesh_min_batch = 0xFFFFFFFFu; hi.mesh_refill = 64;
+    spira::Knobs odd;
+    odd.blocks_per_cu = 7; odd.mesh_two_pass = 0; odd.spec_div = 77; odd.private_l = 0; odd.mesh_fat_waves_per_cu = 3;
+    const spira::Knobs knobs[] = {spira::Knobs{}, off, lo, hi, odd};
+    const uint32_t tiles[][2] = {{2, 2}, {3, 2}, {96, 54}, {257, 63}, {1920, 1080}, {46340, 46340}, {65536, 32767}, {0x7FFFFFFFu, 1}, {2, 0x3FFFFFFFu}};
+    const uint32_t spps[] = {1, 2, 64, 65, 256, 4099, 1u << 24};
+    const uint32_t depths[] = {0, 1, 128, 129, 255};
+    const uint32_t cus[] = {1, 8, 256, 304};
+    const uint32_t tris[] = {0, 12, 32, 33, 81920, 1u << 24};      // spheres alone, LDS-resident triangles, a BVH mesh
+    const uint32_t orgs[] = {SPIRA_SEM_A, SPIRA_SEM_A | SPIRA_KERNEL_WAVEFRONT, SPIRA_SEM_A | SPIRA_KERNEL_MEGA, SPIRA_SEM_A | SPIRA_KERNEL_BOUNCE, SPIRA_SEM_CPU,
+                             SPIRA_SEM_METAL, SPIRA_SEM_METAL | SPIRA_KERNEL_WAVEFRONT, SPIRA_SEM_HYBRID};
+    const uint32_t exts[] = {0, SPIRA_EXT_DIELECTRIC, SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL};
+    uint32_t turn = 0;
+    for (uint32_t prec : {4u, 8u}) for (const auto &t : tiles) for (uint32_t spp : spps) for (uint32_t depth : depths) for (uint32_t nc : cus)
+    for (uint32_t nt : tris) for (uint32_t org : orgs) for (uint32_t ext : exts) {
+        const uint32_t sem = org & SPIRA_SEM_MASK;          // (what validate_params lets through)
+        if (sem != SPIRA_SEM_A && (nt || ext)) continue;
+        if (ext && (org & SPIRA_KERNEL_MASK) == SPIRA_KERNEL_BOUNCE) continue;
+        const uint64_t tp = (uint64_t)t[0] * t[1];
+        // batch_rays from 1 up: one path, a few pixels' worth, 80 slots, everything; 0: the knob.  The knob sets and the call kinds take turns.
+        const uint32_t batches[] = {0, 1, (uint32_t)std::min<uint64_t>(3 * tp + 1, 0xFFFFFFFFu), (uint32_t)std::min<uint64_t>(80 * tp, 0xFFFFFFFFu), 0xFFFFFFFFu};
+        for (int b = 0; b < 2; ++b) {
+            ++turn;
+            spira::PlanIn in = plan_in(prec, t[0], t[1], spp, depth, org | ext, b ? batches[turn % 5] : 0, nt, nc);
+            in.k = knobs[b ? turn % 5 : 0];
+            in.progressive = sem != SPIRA_SEM_HYBRID && turn % 3 == 0; in.caller_rng = in.progressive && turn % 2 == 0; in.out_on_device = turn % 7 < 3;
+            check_plan(in);
+        }
+    }
+    for (int o = 0; o < 8; ++o) CHECK(g_org[o] > 0);          // every organisation was planned
+    CHECK(g_refused > 0 && g_launches > 100000);
+    std::printf("launch plans: %llu swept, %llu refused (limits), %llu k_path passes checked against their workspaces\n", (unsigned long long)g_plans,
+                (unsigned long long)g_refused, (unsigned long long)g_launches);
+}
+
 #ifndef SPIRA_NO_ORACLE
 static void oracle_checks() {   // the checker itself under ASan/UBSan: S2-like scene, all estimators, extensions, tilings, row orders
     const double sph[25] = {0, -100.5, -1, 100, 1, 0, 0, -1, 0.5, 2, 1, 0, -1, 0.5, 3, -1, 0, -1, 0.5, 4, 0, 2, 0, 0.5, 5};
@@ -354,6 +508,7 @@ int main(int argc, char **argv) {
     meshes<double>();
     fastdiv_checks();
     validation_checks();
+    plan_checks();
 #ifndef SPIRA_NO_ORACLE
     oracle_checks();
 #endif
