@@ -16,6 +16,10 @@
  * (tests/test_oracle_kat.py): the analytic known answers derivable from the cited formulae
  *  and the one property the reference's own test pins (output size).
  *
+ * One estimator IS pinned: SPIRA_SEM_METAL (sample_pixel_metal) is held, pixel for pixel, to the reference's own
+ * src/spira_path_trace_kernel.metal compiled for the CPU (oracle/Makefile `_ref`, oracle/ref_metal/,
+ * tests/test_ref_metal_cpu.py).
+ *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off -fopenmp).
  */
 #include <math.h>

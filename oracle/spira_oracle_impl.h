@@ -6,7 +6,8 @@
  * REAL = float (same statements, Float32 arithmetic: the "bit mirror" the f32 HIP kernels are
  * compared with).  Line numbers cite /root/reference (jenkinsm13/julia-spira @ 2025-09-05).
  *
- * PARITY UNPINNED: the reference holds no golden vectors, known-answer tests or fixtures for
+ * PARITY UNPINNED (all but SPIRA_SEM_METAL, which is held to the reference's own .metal kernel compiled for the
+ * CPU: see "Variant METAL" below): the reference holds no golden vectors, known-answer tests or fixtures for
  * this path (its only assertion is size(image) == (64,64), tests/bunny-test.jl:59), it cannot
  * be executed in this pipeline (no Julia), and it never seeds its RNG, so its random stream is
  * not reproducible.  This file follows the reference statement by statement in everything
@@ -533,6 +534,11 @@ static V3 SUF(sample_pixel_cpu)(const World *w, const spira_params *p, uint32_t 
 /* Variant "METAL": path_trace of src/spira_path_trace_kernel.metal:140-269 (+ helpers       */
 /* :52-136).  The file is HTML-escaped and nothing loads it; this restates what  */
 /* it says, in IEEE arithmetic in the written order (Metal's fast-math is unknowable).       */
+/* PINNED: tests/test_ref_metal_cpu.py compares this function, per pixel (final LCG state     */
+/* and radiance), with the file itself compiled for the CPU (oracle/Makefile `_ref`).         */
+/* Known, tested departure, Float64 only: the file's PI is a Float32 literal (2.0f * PI * r1  */
+/* is off by 2.8e-8 relative), sincos_turn below takes exact quarter turns; and the literals  */
+/* 0.7f (sky) and 0.1f (:88) are read as Float64 0.7 and 0.1.  DESIGN.md section 5.           */
 /* RNG: the kernel's own LCG (:52-58), state per pixel carried from sample to sample (:268); */
 /* the initial states, which the reference's host would draw at random, come from the seed.  */
 /* sin/cos: a fixed polynomial evaluated in plain arithmetic (the kernels use the same one). */
@@ -663,9 +669,13 @@ static V3 SUF(sample_pixel_metal)(const World *w, const spira_params *p, uint32_
  * src/spira-metal-optimized.jl:1258): derived from the seed */
 static inline uint32_t SUF(metal_state0)(const World *w, uint32_t pixel) { return oracle_mix32(oracle_mix32(w->sA + pixel) ^ w->sB); }
 
-/* Render with one of the secondary variants (flags & SPIRA_SEM_MASK = SPIRA_SEM_CPU | SPIRA_SEM_METAL). */
-int SUF(oracle_render_variant)(const REAL *spheres5, const REAL *materials8, const REAL *camera12, const spira_params *p,
-                               REAL *out_hdr, REAL *out_img, int n_threads, uint64_t *segments_out) {
+/* Render with one of the secondary variants (flags & SPIRA_SEM_MASK = SPIRA_SEM_CPU | SPIRA_SEM_METAL).
+ * Two entries: oracle_render_variant keeps the eight arguments it always had (a caller built against the earlier declaration must not
+ * have a ninth read from whatever lies on its stack); oracle_render_variant_states (below it) is the same with states_out.
+ * states_out (rows*width words, or NULL; SPIRA_SEM_METAL only): each pixel's LCG state after its last sample, in output order like out_hdr:
+ * what the ABI's `rng_states` holds after spira_accumulate_* (.metal :268). */
+int SUF(oracle_render_variant_states)(const REAL *spheres5, const REAL *materials8, const REAL *camera12, const spira_params *p,
+                                      REAL *out_hdr, REAL *out_img, int n_threads, uint64_t *segments_out, uint32_t *states_out) {
     if (!spheres5 || !materials8 || !camera12 || !p) return -1;
     const uint32_t sem = p->flags & SPIRA_SEM_MASK;
     if (sem != SPIRA_SEM_CPU && sem != SPIRA_SEM_METAL) return -5;
@@ -693,6 +703,7 @@ int SUF(oracle_render_variant)(const REAL *spheres5, const REAL *materials8, con
             }
             color = SUF(divs)(color, (REAL)p->spp);                           /* :1438 */
             size_t o = (size_t)r * W + (i - 1);
+            if (states_out && sem == SPIRA_SEM_METAL) states_out[o] = st;
             if (out_hdr) { out_hdr[o] = color.x; out_hdr[plane + o] = color.y; out_hdr[2 * plane + o] = color.z; }
             if (out_img) {
                 out_img[o] = SUF(post1)(color.x, post); out_img[plane + o] = SUF(post1)(color.y, post);
@@ -702,6 +713,10 @@ int SUF(oracle_render_variant)(const REAL *spheres5, const REAL *materials8, con
     }
     if (segments_out) *segments_out = segments;
     return 0;
+}
+int SUF(oracle_render_variant)(const REAL *spheres5, const REAL *materials8, const REAL *camera12, const spira_params *p,
+                               REAL *out_hdr, REAL *out_img, int n_threads, uint64_t *segments_out) {
+    return SUF(oracle_render_variant_states)(spheres5, materials8, camera12, p, out_hdr, out_img, n_threads, segments_out, NULL);
 }
 
 /* Trace one path of a secondary variant (METAL: the `sample`-th path of the pixel, replaying the earlier ones

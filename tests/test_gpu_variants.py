@@ -1,7 +1,9 @@
 """GPU (MI355X): the two secondary integrator variants of the reference against their CPU restatements.
 SPIRA_SEM_CPU   = trace_ray of render_with_cpu  (src/spira-metal-optimized.jl:1346-1450)
 SPIRA_SEM_METAL = path_trace                     (src/spira_path_trace_kernel.metal:140-269)
-Geometry bit-exact (incl. the shared polynomial sin/cos and the per-pixel LCG streams), images 1e-5."""
+Geometry bit-exact (incl. the shared polynomial sin/cos and the per-pixel LCG streams), images 1e-5.
+SPIRA_SEM_METAL also against the reference's own kernel compiled for the CPU (oracle/_ref, tests/test_ref_metal_cpu.py): final LCG states
+and radiance."""
 import numpy as np
 import pytest
 
@@ -182,3 +184,29 @@ def test_hybrid_estimator_fuzz(gpu, oracle):
         want, seg = oracle.render_hybrid(s["spheres5"], s["materials8"], s["camera12"], oracle.make_params(W, H, spp, depth, ns, nm, 0, flags=fl, seed=seed), prec)
         assert np.array_equal(hdr, want), (it, W, H, spp, depth, prec, float(np.abs(hdr - want).max()))
         assert gpu.counters()["segments"] == seg, it
+
+
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_metal_kernels_equal_the_reference_kernel(gpu, oracle, prec):
+    """The kernels' returned rng_states and sums against the reference's .metal kernel compiled for the CPU (oracle/_ref; only the libraries
+    are loaded, never a checkout), pixel for pixel: the state cap and the radiance tolerances of tests/test_ref_metal_cpu.py (the reference's own
+    floors).  Every organisation of the estimator (the default, the wavefront k_path_metal, the one-lane-per-pixel k_variant_metal), one call of
+    8 samples and two calls of 4 that hand sums and states over."""
+    import ref_metal_support as R
+    R.need_ref(oracle)
+    npdt = np.float32 if prec == "f32" else np.float64
+    cases = [dict(R.scene_emitter(oracle), W=75, H=41, spp=8, depth=8, seed=1033), dict(R.scene_closed(oracle), W=61, H=35, spp=8, depth=24, seed=1046)]
+    for c in cases:
+        sp, ma, cam, W, H = c["spheres5"], c["materials8"], c["camera12"], c["W"], c["H"]
+        ns, nm = len(sp), len(ma)
+        assert R.reference_floor(oracle, c, "f64")[0] == 0          # an input whose control flow the file's Float32 PI does not decide
+        for kernel in (0, gpu.KERNEL_WAVEFRONT, gpu.KERNEL_MEGA):
+            fl = gpu.SEM_METAL | kernel | gpu.ROWS_BOTTOM_UP
+            for calls in ((8,), (4, 4)):
+                sums = np.zeros((3, H, W), dtype=npdt)
+                states = np.zeros(H * W, dtype=np.uint32)
+                s0 = 0
+                for n in calls:
+                    gpu.accumulate(sp, ma, None, cam, gpu.make_params(W, H, n, c["depth"], ns, nm, 0, flags=fl, seed=c["seed"]), s0, sums, states, prec)
+                    s0 += n
+                R.hold_to_reference(oracle, c, prec, sums.astype(np.float64) / 8.0, states, "kernel 0x%02x calls %s" % (kernel, calls))
