@@ -284,6 +284,52 @@ int spira_accumulate_device_f64(const double *spheres5, const double *materials8
                                 const double camera12[12], const spira_params *params, uint32_t sample0,
                                 double *d_sum_rgb, uint32_t *d_rng_states, void *stream);
 
+/* ---- adaptive sampling: render to a noise target, per-pixel sample counts ----
+ * params->spp is the CAP.  Round 0 gives every pixel of the tile min_spp samples; every later round gives each pixel still active
+ * min(batch_spp, spp - n) more; a pixel leaves the active set the first time the rule below holds at the end of a round, or at the cap,
+ * so a pixel ends with one of the counts min_spp, min_spp + batch_spp, ..., spp; the render ends when the set is empty.  Every adaptive
+ * render starts at sample 0 (there is no sample0), and "pixel p received its first n samples" means what it means everywhere else in
+ * this library: the RNG is keyed by (global pixel, sample) and sums run in sample order, so out_hdr at a pixel with out_spp == n is, bit
+ * for bit, the plain render of spp = n there, whatever the tiling (rows / row0 / stripe_* as in every entry), list order or scheduling.
+ * The rule, per pixel, evaluated in the render precision T in exactly this order, nothing fused: with sum = the RGB sums and
+ * Q = the sum over the samples, in order, of y*y, y = (0.2126 r + 0.7152 g) + 0.0722 b the luminance of ONE sample, after n samples
+ *     Y = (0.2126 sum.r + 0.7152 sum.g) + 0.0722 sum.b,   V = max(n Q - Y Y, 0),   rhs = ((tol (Y + n floor)) (tol (Y + n floor))) (n - 1)
+ *     converged  <=>  tolerance > 0  and  V <= rhs            (any NaN in V or rhs: not converged; tolerance == 0: never)
+ * i.e. "standard error of the mean luminance <= tolerance * (mean + floor)" multiplied through by n^2 (n - 1).  tolerance and floor are
+ * rounded to T once.  The cancellation in n Q - Y Y costs about 1e-7 Y^2 in Float32 against a threshold of about tolerance^2 Y^2 n:
+ * harmless for tolerance >= 1e-3.  A per-pixel stopping rule biases the estimate slightly downward in noisy pixels (a pixel whose
+ * first samples happen to agree stops before it meets its rare bright ones); min_spp exists to bound that.
+ * Limits: min_spp >= 2, batch_spp >= 1, min_spp <= params->spp, tolerance >= 0, floor >= 0, max_depth >= 1, else SPIRA_E_INVALID.
+ * Scope: SPIRA_SEM_A with SPIRA_KERNEL_DEFAULT, both precisions, spheres, LDS triangles and BVH meshes; any other estimator or
+ * organisation and the SPIRA_EXT_* flags are SPIRA_E_UNSUPPORTED.
+ * Outputs (any may be NULL, not all): out_hdr / out_img as in every entry (the mean over the pixel's OWN count, then the display
+ * transform); out_spp rows*width samples taken; out_q rows*width the final Q.  Afterwards spira_counters.samples is the sum of out_spp,
+ * and launches, passes (round 0's passes + the refinement rounds) and kernel_ms cover the whole call.
+ * The host reads the length of the active list once per round to size the next launch: these entries SYNCHRONISE their stream once per
+ * round — the *_device_* form too, which is otherwise asynchronous like the other device entries. */
+typedef struct spira_adaptive {
+    uint32_t min_spp, batch_spp;
+    double   tolerance, floor;
+} spira_adaptive;            /* 24 bytes */
+int spira_render_adaptive_f32(const float *spheres5, const float *materials8, const float *triangles10,
+                              const float camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                              float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q);
+int spira_render_adaptive_f64(const double *spheres5, const double *materials8, const double *triangles10,
+                              const double camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                              double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q);
+int spira_render_adaptive_scene_f32(const spira_scene *scene, const float camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                                    float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q);
+int spira_render_adaptive_scene_f64(const spira_scene *scene, const double camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                                    double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q);
+int spira_render_adaptive_scene_device_f32(const spira_scene *scene, const float camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                                           float *d_out_hdr, float *d_out_img, uint32_t *d_out_spp, float *d_out_q, void *stream);
+int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const double camera12[12], const spira_params *params, const spira_adaptive *adaptive,
+                                           double *d_out_hdr, double *d_out_img, uint32_t *d_out_spp, double *d_out_q, void *stream);
+/* The rule as host arithmetic (the same inline function the kernels call; no device needed): 1 converged, 0 not, or a negative
+ * SPIRA_E_* code (sum3 NULL, n outside 1 .. 2^24, tolerance or floor negative or NaN). */
+int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor);
+int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, double tolerance, double floor);
+
 /* ---- diagnostics: per-segment trace of chosen paths (parity tests compare geometry bitwise) ----
  * ijs: n_paths x [i, j, sample] with i in 1..width, j in 1..height (the loop indices of
  * examples/julia-raytracer.jl:392-397) and sample in 0..spp-1.  Outputs, per path and bounce b <

@@ -35,6 +35,7 @@
 #include "spira_bvh.h"
 #include "spira_validate.h"
 #include "spira_plan.h"
+#include "spira_adaptive.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -59,6 +60,8 @@ int render_impl_f32(const spira_scene *h, const float *spheres5, const float *ma
                     float *out_hdr, float *out_img, bool out_on_device, void *user_stream, bool progressive, uint32_t sample0, uint32_t *rng_states, const SlabCtl *slab);
 int trace_impl_f32(const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
                    uint32_t n_paths, const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance);
+int render_adaptive_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
+                             const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 void launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -115,6 +118,8 @@ struct Ctx {
     DevBuf hyb_state, hyb_mat, hyb_flags;          // SPIRA_SEM_HYBRID: per-pixel ray state between its launches
     DevBuf spd32, spd64;                          // SPIRA_EXT_SPECTRAL: the SPD table, uploaded once per precision
     DevBuf multi_tile, multi_stack, multi_full;   // spira_render_multi_*: this device's tile; device 0: the gathered tiles, the frame
+    DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
+    uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     SceneStore scene;                         // the scene of the current call (host-array entry points)
     spira::Stats *h_stats = nullptr;          // pinned
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging of a host-output frame (copy_out below)
@@ -1196,6 +1201,176 @@ int render_entry(const spira_scene *h, const T *spheres5, const T *materials8, c
     return render_entry_plain<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states);
 }
 
+// ---- adaptive sampling (spira_render_adaptive_*; spira_adaptive.h).  Round 0 is a plain render of min_spp samples on the slot-major plan (PlanIn::adaptive)
+// whose resolve launches are k_resolve_adaptive; every later round is one k_refine launch over the active list, sized by the list length the host reads
+// back — ONE stream synchronisation per round, the device-output entries included; then k_finalize_adaptive.
+template <class T, bool BVH>
+int enqueue_refine(hipStream_t st, const spira::AdaptiveRound &g, size_t lds, const spira::RefineArgs<T> &ra) {
+    // the launch against what the kernel assumes of it: its LDS block holds ppw * chunk entries per wave, a lane per owned pixel, a wave for every list entry
+    if (g.ppw == 0 || g.chunk == 0 || (uint64_t)g.ppw * g.chunk > spira::kAdaptiveItems || g.ppw > 64 || g.waves * g.ppw < ra.n_active ||
+        (uint64_t)g.grid * spira::kAdaptiveWpb < g.waves || spira::kAdaptiveWpb != spira::kBlock / 64)
+        return fail(SPIRA_E_LIMIT, "internal: a refinement launch does not cover its list");
+    launch_lds(spira::k_refine<T, BVH>, dim3(g.grid), dim3(spira::kBlock), lds, st, ra);
+    return lds_optin_failed();
+}
+
+template <class T>
+int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                         const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream) {
+    using spira::Org;
+    using P4 = spira::Pack4<T>;
+    uint32_t rows = 0;
+    tl_lds_optin = hipSuccess;
+    if (!ad) return fail(SPIRA_E_INVALID, "adaptive is NULL");
+    // (any one of the four outputs will do: validate_call asks for one of its two)
+    const T *some_out = out_hdr ? out_hdr : out_img ? out_img : (out_spp || out_q) ? camera12 : nullptr;
+    if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, some_out, (const T *)nullptr, false, 0, nullptr, &rows)) return rc;
+    if ((p->flags & SPIRA_SEM_MASK) != SPIRA_SEM_A) return fail(SPIRA_E_UNSUPPORTED, "adaptive sampling is built for SPIRA_SEM_A only");
+    if ((p->flags & SPIRA_KERNEL_MASK) != SPIRA_KERNEL_DEFAULT) return fail(SPIRA_E_UNSUPPORTED, "adaptive sampling has one kernel organisation: SPIRA_KERNEL_DEFAULT");
+    if (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) return fail(SPIRA_E_UNSUPPORTED, "SPIRA_EXT_* extensions are not built into the adaptive kernels");
+    const char *msg = nullptr;
+    spira::AdaptiveIn ain;
+    ain.min_spp = ad->min_spp; ain.batch_spp = ad->batch_spp; ain.spp = p->spp; ain.tolerance = ad->tolerance; ain.floor = ad->floor;
+    ain.tile_pixels = (uint64_t)rows * p->width; ain.prec = sizeof(T); ain.pack3 = sizeof(spira::Pack3<T>);
+    if (int rc = spira::adaptive_check(ain.min_spp, ain.batch_spp, ain.spp, ain.tolerance, ain.floor, &msg)) return fail(rc, msg);
+    if (p->max_depth < 1) return fail(SPIRA_E_INVALID, "max_depth must be >= 1");
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    Ctx &c = *cp;
+    std::lock_guard<std::recursive_mutex> lock(c.mu);
+    hipStream_t st = out_on_device ? (hipStream_t)user_stream : c.stream;
+    if (int rc = order_after_previous(c, st)) return rc;
+
+    ain.num_cus = (uint32_t)c.num_cus;
+    spira::AdaptivePlan ap;
+    if (int rc = spira::make_adaptive_plan(ain, ap, &msg)) return fail(rc, msg);
+    spira_params p0 = *p;                // round 0: min_spp samples of every pixel
+    p0.spp = ad->min_spp;
+    spira::Plan plan;
+    const uint32_t nt_scene = h ? h->store.nt : (triangles10 ? p->n_triangles : 0);
+    spira::PlanIn pin = plan_input<T>(c, &p0, rows, nt_scene, false, false, out_on_device);
+    pin.adaptive = true;
+    if (int rc = spira::make_plan(pin, plan, &msg)) return fail(rc, msg);
+    if (plan.org != Org::Path || plan.fused) return fail(SPIRA_E_LIMIT, "internal: round 0 of an adaptive render is not a slot-major k_path plan");
+    if (int rc = ensure_workspaces(c, plan.ws)) return rc;
+    if (int rc = c.ad_q.ensure(ap.q_bytes)) return rc;
+    if (int rc = c.ad_n.ensure(ap.n_bytes)) return rc;
+    for (int i = 0; i < 2; ++i) if (int rc = c.ad_list[i].ensure(ap.list_bytes)) return rc;
+    if (int rc = c.ad_count.ensure(ap.count_bytes)) return rc;
+    if (!c.h_ad_count) HIP_TRY(hipHostMalloc((void **)&c.h_ad_count, sizeof(uint32_t), hipHostMallocDefault));
+
+    Call<T> k{c, st, &p0, plan};
+    const uint64_t tile_pixels = plan.tile_pixels;
+    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, &p0, k.a.scene)) return rc;
+    if (int rc = attach_spd<T>(c, st, &p0, k.a.scene)) return rc;
+    k.spec = plan.spec((h ? h->store.moderate : c.scene.moderate) && spira::camera_scale_moderate<T>(camera12));
+    fill_const<T>(k.a.rc, camera12, &p0, rows, plan.slots);
+    if (!fastdiv_selfcheck(k.a.rc.tile_pixels, (uint32_t)plan.batch) || !fastdiv_selfcheck(k.a.rc.width, k.a.rc.tile_pixels) ||
+        !fastdiv_selfcheck(k.a.rc.stripe_h ? k.a.rc.stripe_h : 1, rows))
+        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+    k.a.L = (spira::Pack3<T> *)c.L.p;
+    k.a.stats = k.stats();
+    k.lds = spira::scene_lds_bytes<T>(k.a.scene.n_spheres, k.a.scene.n_materials, k.a.scene.n_triangles);
+    k.profile = true;
+    T *d_hdr = out_hdr, *d_img = out_img;
+    if (!out_on_device) {
+        d_hdr = out_hdr ? (T *)c.out_tmp.p : nullptr;
+        d_img = out_img ? (T *)((char *)c.out_tmp.p + 3 * tile_pixels * sizeof(T)) : nullptr;
+    }
+    if (int rc = profile_events(c, (size_t)plan.n_pass * 2)) return rc;
+    c.ev_used = 0;
+    c.ev_mid_used = 0;
+    HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), st));
+    HIP_TRY(hipMemsetAsync(c.ad_count.p, 0, ap.count_bytes, st));
+    HIP_TRY(hipEventRecord(c.ev_start, st));
+
+    spira::AdaptiveArgs<T> aa{};
+    aa.accum = k.accum(); aa.Q = (T *)c.ad_q.p; aa.npix = (uint32_t *)c.ad_n.p;
+    aa.tol = (T)ad->tolerance; aa.floor = (T)ad->floor; aa.cap = p->spp;
+    uint32_t *const lists[2] = {(uint32_t *)c.ad_list[0].p, (uint32_t *)c.ad_list[1].p};
+    uint32_t *const counts = (uint32_t *)c.ad_count.p;
+    for (uint32_t pass = 0; pass < plan.n_pass; ++pass) {
+        uint32_t stat_rows = 0;
+        k.a.pass = pass;
+        k.a.n_first = plan.n_first(pass);
+        if (int rc = enqueue_path_pass(k, &stat_rows)) return rc;
+        hipLaunchKernelGGL((spira::k_resolve_adaptive<T>), dim3(plan.blocks(tile_pixels)), k.block(), 0, st, (const spira::Pack3<T> *)c.L.p, (uint32_t)tile_pixels,
+                           plan.k_eff(pass), pass == 0 ? 1 : 0, pass + 1 == plan.n_pass ? 1 : 0, ad->min_spp,
+                           stat_rows ? (const uint32_t *)c.blkstats.p : (const uint32_t *)nullptr, stat_rows, k.stats(), aa, lists[0], counts);
+        ++k.launches;
+    }
+    // rounds >= 1: the list the previous round left, until it is empty or every pixel on it has reached the cap
+    uint64_t samples = tile_pixels * ad->min_spp, rounds = 0;
+    int cur = 0;
+    for (uint32_t r = 1; r < ap.levels; ++r) {
+        HIP_TRY(hipMemcpyAsync(c.h_ad_count, counts + cur, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t n_active = *c.h_ad_count;
+        if (!n_active) break;
+        if (n_active > ap.list_cap) return fail(SPIRA_E_LIMIT, "internal: the active list is longer than the tile");
+        HIP_TRY(hipMemsetAsync(counts + (cur ^ 1), 0, sizeof(uint32_t), st));
+        const spira::AdaptiveRound g = ap.round(r, n_active);
+        spira::RefineArgs<T> ra{};
+        ra.scene = k.a.scene; ra.rc = k.a.rc; ra.ad = aa;
+        ra.list_in = lists[cur]; ra.n_active = n_active; ra.list_out = lists[cur ^ 1]; ra.count_out = counts + (cur ^ 1);
+        ra.sample_first = ap.level(r - 1); ra.samples = g.samples; ra.chunk = g.chunk; ra.ppw = g.ppw;
+        ra.stats = k.stats();
+        const size_t lds_r = k.lds + (size_t)ap.lds_round;
+        if (int rc = k.a.scene.n_bvh_tris ? enqueue_refine<T, true>(st, g, lds_r, ra) : enqueue_refine<T, false>(st, g, lds_r, ra)) return rc;
+        ++k.launches; ++rounds;
+        samples += (uint64_t)n_active * g.samples;
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL((spira::k_finalize_adaptive<T>), dim3(plan.blocks(tile_pixels)), k.block(), 0, st, (const P4 *)k.accum(), (const uint32_t *)c.ad_n.p, (const T *)c.ad_q.p,
+                       (uint32_t)tile_pixels, p->flags & SPIRA_POST_MASK, d_hdr, d_img, out_on_device ? out_spp : (uint32_t *)nullptr, out_on_device ? out_q : (T *)nullptr);
+    ++k.launches;
+    if (int rc = lds_optin_failed()) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c.ev_stop, st));
+    HIP_TRY(hipMemcpyAsync(c.h_stats, c.stats.p, sizeof(spira::Stats), hipMemcpyDeviceToHost, st));
+
+    c.last = spira_counters{};
+    c.last.samples = samples;
+    c.last.passes = plan.n_pass + rounds;
+    c.last.launches = k.launches;
+    c.last.bounce_launches = plan.n_pass;
+    c.last_valid = true;
+    c.last_pending = true;
+    c.last_stream = st;
+
+    if (!out_on_device) {
+        void *const dst[2] = {out_hdr, out_img};
+        const void *const src[2] = {d_hdr, d_img};
+        if (int rc = copy_out(c, st, dst, src, 3 * tile_pixels * sizeof(T))) return rc;
+        if (out_spp) HIP_TRY(hipMemcpyAsync(out_spp, c.ad_n.p, tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (out_q) HIP_TRY(hipMemcpyAsync(out_q, c.ad_q.p, tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+    if (int rc = mark_done(c, st)) return rc;
+    if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// render_adaptive_impl<T> of whichever translation unit holds the kernels of T
+template <class T>
+int render_adaptive_entry(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                          const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::render_adaptive_impl_f32(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
+    else
+#endif
+        return render_adaptive_impl<T>(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
+}
+
+// The rule as host arithmetic: 1 converged, 0 not, or a negative code
+template <class T>
+int adaptive_converged_host(const T *sum3, T q, uint32_t n, double tolerance, double floor) {
+    if (!sum3) return fail(SPIRA_E_INVALID, "sum3 is NULL");
+    if (n < 1 || n > SPIRA_MAX_SPP) return fail(SPIRA_E_INVALID, "n out of range [1, 2^24]");
+    if (!(tolerance >= 0) || !(floor >= 0)) return fail(SPIRA_E_INVALID, "tolerance and floor must be >= 0");
+    return spira::adaptive_converged<T>(sum3[0], sum3[1], sum3[2], q, n, (T)tolerance, (T)floor) ? 1 : 0;
+}
+
 template <class T>
 int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
                uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance) {
@@ -1587,6 +1762,10 @@ int spira_tu::trace_impl_f32(const float *spheres5, const float *materials8, con
                              uint32_t n_paths, const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance) {
     return trace_impl<float>(spheres5, materials8, triangles10, camera12, p, n_paths, ijs, prims, ts, dirs, radiance);
 }
+int spira_tu::render_adaptive_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
+                                       const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream) {
+    return render_adaptive_impl<float>(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
+}
 #else
 // ======================================================================= C ABI (SPIRA_TU_MAIN, or the single translation unit)
 extern "C" {
@@ -1674,6 +1853,8 @@ void spira_shutdown(void) {
         for (int i = 0; i < 2; ++i) { c.qA[i].release(); c.qB[i].release(); c.qC[i].release(); c.qR[i].release(); c.qK[i].release(); c.qX[i].release(); }
         c.mesh_list.release(); c.mesh_count.release();
         c.redo.release(); c.L.release(); c.accum.release(); c.counts.release(); c.blkstats.release(); c.stats.release(); c.scene.release(); c.out_tmp.release(); c.trace.release(); c.rng.release(); c.multi_tile.release(); c.multi_stack.release(); c.multi_full.release(); c.spd32.release(); c.spd64.release(); c.hyb_state.release(); c.hyb_mat.release(); c.hyb_flags.release();
+        c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
+        if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
         c.ev_pool.clear();
         for (hipEvent_t e : c.ev_mid) (void)hipEventDestroy(e);
@@ -1796,6 +1977,42 @@ int spira_render_scene_device_f32(const spira_scene *scene, const float cam[12],
 int spira_render_scene_device_f64(const spira_scene *scene, const double cam[12], const spira_params *p, double *d_hdr, double *d_img, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
     return render_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, d_hdr, d_img, true, stream);
+}
+
+// ---- adaptive sampling: render to a noise target (host arrays; a handle; a handle and device outputs on the caller's stream)
+int spira_render_adaptive_f32(const float *s, const float *m, const float *t, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                              float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q) {
+    return render_adaptive_entry<float>(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+}
+int spira_render_adaptive_f64(const double *s, const double *m, const double *t, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                              double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q) {
+    return render_adaptive_entry<double>(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+}
+int spira_render_adaptive_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                                    float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return render_adaptive_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+}
+int spira_render_adaptive_scene_f64(const spira_scene *scene, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                                    double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return render_adaptive_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+}
+int spira_render_adaptive_scene_device_f32(const spira_scene *scene, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                                           float *d_hdr, float *d_img, uint32_t *d_spp, float *d_q, void *stream) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return render_adaptive_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
+}
+int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
+                                           double *d_hdr, double *d_img, uint32_t *d_spp, double *d_q, void *stream) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return render_adaptive_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
+}
+int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor) {
+    return adaptive_converged_host<float>(sum3, q, n, tolerance, floor);
+}
+int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, double tolerance, double floor) {
+    return adaptive_converged_host<double>(sum3, q, n, tolerance, floor);
 }
 
 // ---- multi-device render on one node: interleaved 8-row stripes, one host thread + stream per device, one RCCL gather

@@ -26,6 +26,7 @@ struct PlanIn {
     uint32_t n_triangles = 0;                  // of the scene
     uint32_t num_cus = 0;
     bool progressive = false, caller_rng = false, out_on_device = false;      // (caller_rng: a progressive call that hands LCG states in and out)
+    bool adaptive = false;                     // round 0 of an adaptive render: slot-major L and a resolve launch of its own (k_resolve_adaptive), never pixel-owning passes
     // the constants of spira_device.h the arithmetic needs (gfx950: 256, 5 / 4, 1, 16- and 32-byte packets)
     uint32_t prec = 0, block = 0, waves_per_simd = 0, carry_key = 0;          // sizeof(T), kBlock, SPIRA_WAVES_F32 / F64, SPIRA_CARRY_KEY
     uint32_t pack4 = 0, pack3 = 0, pack2 = 0;                                 // sizeof(Pack4<T>), ...
@@ -136,7 +137,7 @@ inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
     // In Float32 the end-of-wave sum costs k_path what k_resolve costs (S1 +0.30 / 0.29 ms); in the kernels with the LDS triangle scan or the
     // extensions its code costs spilled registers (glass scene Float64 +15 %, S2 +4 %).  SPIRA_FUSED_RESOLVE=0: round-robin dealing + k_resolve (A/B, tests).
     // (R = 2 too: the instantiation of SPIRA_R=1 is compiled with the triangle scan.)
-    pl.fused = persistent && in.prec == 8 && pl.R == 2 && in.n_triangles == 0 && !ext && pl.slots <= 64 && k.fused_resolve != 0;
+    pl.fused = persistent && in.prec == 8 && pl.R == 2 && in.n_triangles == 0 && !ext && pl.slots <= 64 && k.fused_resolve != 0 && !in.adaptive;
     const Geometry g = pl.geometry(pl.batch);
     pl.G_max = g.G; pl.cap_max = g.cap;
     const uint64_t waves = (uint64_t)g.G * pl.wpb;
@@ -229,6 +230,62 @@ inline PathNeed path_need(const PathLaunch &a) {
     // wave-private radiance blocks: pixel-owning passes whose queue word need not be the path index (the RNG key is carried: max_depth <= 128)
     n.private_ok = a.pixel_owning && a.carry_key && a.max_depth <= 128 && n.l_entries <= 0x80000000ull;
     return n;
+}
+
+// ---- adaptive sampling (spira_render_adaptive_*; kernels in spira_adaptive.h): the sample schedule of a call and what its rounds need, as arithmetic.
+// Round 0 gives every pixel of the tile min_spp samples (a plan of its own: make_plan with PlanIn::adaptive and spp = min_spp); round r >= 1 gives every
+// pixel still active level(r) - level(r - 1) more, where level(r) = min(min_spp + r * batch_spp, spp): the levels min, min + batch, ..., spp.
+struct AdaptiveIn {
+    uint32_t min_spp = 0, batch_spp = 0, spp = 0;          // spira_adaptive + the cap (spira_params::spp)
+    double tolerance = 0, floor = 0;
+    uint64_t tile_pixels = 0;
+    uint32_t prec = 0, pack3 = 0, num_cus = 0;             // sizeof(T), sizeof(Pack3<T>)
+};
+// a refinement launch: every wave owns `ppw` consecutive entries of the active list and walks their samples `chunk` at a time, ppw * chunk <= kAdaptiveItems
+// radiance entries of LDS per wave; `grid` workgroups of kAdaptiveWpb waves
+constexpr uint32_t kAdaptiveItems = 256, kAdaptiveWpb = 4;
+struct AdaptiveRound { uint32_t samples, chunk, ppw, grid; uint64_t waves; };
+struct AdaptivePlan {
+    AdaptiveIn in;
+    uint32_t levels = 0;                       // distinct sample counts a pixel can end with; rounds = levels (round 0 included)
+    uint64_t list_cap = 0;                     // entries of each of the two active lists
+    uint64_t list_bytes = 0, q_bytes = 0, n_bytes = 0, count_bytes = 0;      // per list; Q (one T per pixel); samples taken (one word per pixel); the two list lengths
+    uint64_t lds_round = 0;                    // LDS a refinement workgroup adds to the scene's
+    uint32_t level(uint32_t r) const { return (uint32_t)std::min<uint64_t>((uint64_t)in.min_spp + (uint64_t)r * in.batch_spp, in.spp); }
+    // geometry of round r >= 1 over n_active list entries (n_active >= 1)
+    AdaptiveRound round(uint32_t r, uint64_t n_active) const {
+        AdaptiveRound a{};
+        a.samples = level(r) - level(r - 1);
+        a.chunk = std::min(a.samples, kAdaptiveItems);
+        // small lists: fewer pixels per wave, so that the launch still has a few waves for every SIMD (the result does not depend on it)
+        const uint64_t want_waves = std::max<uint64_t>(1, (uint64_t)in.num_cus * 16);
+        const uint64_t spread = (n_active + want_waves - 1) / want_waves;
+        a.ppw = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(64, kAdaptiveItems / a.chunk), spread));
+        a.waves = (n_active + a.ppw - 1) / a.ppw;
+        a.grid = (uint32_t)((a.waves + kAdaptiveWpb - 1) / kAdaptiveWpb);
+        return a;
+    }
+};
+inline int adaptive_check(uint32_t min_spp, uint32_t batch_spp, uint32_t spp, double tolerance, double floor, const char **msg) {
+    if (min_spp < 2) { *msg = "spira_adaptive: min_spp must be >= 2 (a variance needs two samples)"; return SPIRA_E_INVALID; }
+    if (batch_spp < 1) { *msg = "spira_adaptive: batch_spp must be >= 1"; return SPIRA_E_INVALID; }
+    if (min_spp > spp) { *msg = "spira_adaptive: min_spp exceeds params->spp (the cap)"; return SPIRA_E_INVALID; }
+    if (!(tolerance >= 0) || !(floor >= 0)) { *msg = "spira_adaptive: tolerance and floor must be >= 0"; return SPIRA_E_INVALID; }
+    return 0;
+}
+inline int make_adaptive_plan(const AdaptiveIn &in, AdaptivePlan &ap, const char **msg) {
+    ap = AdaptivePlan{};
+    ap.in = in;
+    if (int rc = adaptive_check(in.min_spp, in.batch_spp, in.spp, in.tolerance, in.floor, msg)) return rc;
+    if (in.tile_pixels == 0 || in.tile_pixels > 0x7FFFFFFFull) { *msg = "tile too large: rows*width must be < 2^31"; return SPIRA_E_LIMIT; }
+    ap.levels = 1 + (uint32_t)(((uint64_t)(in.spp - in.min_spp) + in.batch_spp - 1) / in.batch_spp);
+    ap.list_cap = in.tile_pixels;              // a list never holds a pixel twice
+    ap.list_bytes = ap.list_cap * sizeof(uint32_t);
+    ap.q_bytes = in.tile_pixels * in.prec;
+    ap.n_bytes = in.tile_pixels * sizeof(uint32_t);
+    ap.count_bytes = 2 * sizeof(uint32_t);
+    ap.lds_round = (uint64_t)kAdaptiveWpb * kAdaptiveItems * in.pack3;
+    return 0;
 }
 
 }  // namespace spira

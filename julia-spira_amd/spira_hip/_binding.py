@@ -33,6 +33,8 @@ EXPORTS = [
     "spira_render_scene_f32", "spira_render_scene_f64", "spira_render_scene_device_f32", "spira_render_scene_device_f64",
     "spira_render_multi_f32", "spira_render_multi_f64", "spira_scene_create_multi_f32", "spira_scene_create_multi_f64",
     "spira_render_multi_scene_f32", "spira_render_multi_scene_f64",
+    "spira_render_adaptive_f32", "spira_render_adaptive_f64", "spira_render_adaptive_scene_f32", "spira_render_adaptive_scene_f64",
+    "spira_render_adaptive_scene_device_f32", "spira_render_adaptive_scene_device_f64", "spira_adaptive_converged_f32", "spira_adaptive_converged_f64",
 ]
 
 
@@ -56,6 +58,11 @@ class Counters(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Adaptive(C.Structure):
+    """spira_adaptive: the schedule of an adaptive render (params.spp is the cap)."""
+    _fields_ = [("min_spp", C.c_uint32), ("batch_spp", C.c_uint32), ("tolerance", C.c_double), ("floor", C.c_double)]
 
 
 _lib = None
@@ -258,6 +265,61 @@ class Scene:
         c, cp = _arr(camera12, npdt)
         fn = lib().spira_render_scene_device_f32 if self.prec == "f32" else lib().spira_render_scene_device_f64
         _check(fn(self._h, cp, C.byref(params), C.c_void_p(d_hdr_ptr or None), C.c_void_p(d_img_ptr or None), C.c_void_p(stream_ptr or None)))
+
+    def render_adaptive(self, camera12, params, adaptive, want_hdr=True, want_img=False, want_spp=True, want_q=True):
+        """spira_render_adaptive_scene_*: returns (hdr, img, spp, q) — [3, rows, W], [3, rows, W], uint32 [rows, W], [rows, W] or None."""
+        npdt, _ = _dt(self.prec)
+        c, cp = _arr(camera12, npdt)
+        outs, ptrs = _adaptive_outputs(params, npdt, want_hdr, want_img, want_spp, want_q)
+        fn = lib().spira_render_adaptive_scene_f32 if self.prec == "f32" else lib().spira_render_adaptive_scene_f64
+        _check(fn(self._h, cp, C.byref(params), C.byref(adaptive), *ptrs))
+        return outs
+
+    def render_adaptive_device(self, camera12, params, adaptive, d_hdr_ptr, d_img_ptr, d_spp_ptr, d_q_ptr, stream_ptr):
+        """spira_render_adaptive_scene_device_*: DEVICE output addresses (0 / None: not wanted); synchronises the stream once per round."""
+        npdt, _ = _dt(self.prec)
+        c, cp = _arr(camera12, npdt)
+        fn = lib().spira_render_adaptive_scene_device_f32 if self.prec == "f32" else lib().spira_render_adaptive_scene_device_f64
+        _check(fn(self._h, cp, C.byref(params), C.byref(adaptive), C.c_void_p(d_hdr_ptr or None), C.c_void_p(d_img_ptr or None),
+                  C.c_void_p(d_spp_ptr or None), C.c_void_p(d_q_ptr or None), C.c_void_p(stream_ptr or None)))
+
+
+def make_adaptive(min_spp, batch_spp, tolerance, floor=0.0):
+    return Adaptive(min_spp, batch_spp, tolerance, floor)
+
+
+def _adaptive_outputs(params, npdt, want_hdr, want_img, want_spp, want_q):
+    rows = params.rows if params.rows else params.height
+    outs = (np.empty((3, rows, params.width), dtype=npdt) if want_hdr else None, np.empty((3, rows, params.width), dtype=npdt) if want_img else None,
+            np.empty((rows, params.width), dtype=np.uint32) if want_spp else None, np.empty((rows, params.width), dtype=npdt) if want_q else None)
+    return outs, [o.ctypes.data_as(C.c_void_p) if o is not None else None for o in outs]
+
+
+def render_adaptive(spheres5, materials8, triangles10, camera12, params, adaptive, prec="f32", want_hdr=True, want_img=False, want_spp=True, want_q=True):
+    """spira_render_adaptive_*: host arrays, host outputs.  params.spp is the cap.  Returns (hdr, img, spp, q): the mean over each pixel's own
+    sample count [3, rows, W], its display transform, the samples taken (uint32 [rows, W]) and the final Q [rows, W]; None where not wanted."""
+    npdt, _ = _dt(prec)
+    s, sp = _arr(spheres5, npdt)
+    m, mp = _arr(materials8, npdt)
+    t, tp = _arr(triangles10, npdt)
+    c, cp = _arr(camera12, npdt)
+    outs, ptrs = _adaptive_outputs(params, npdt, want_hdr, want_img, want_spp, want_q)
+    fn = lib().spira_render_adaptive_f32 if prec == "f32" else lib().spira_render_adaptive_f64
+    _check(fn(sp, mp, tp, cp, C.byref(params), C.byref(adaptive), *ptrs))
+    return outs
+
+
+def adaptive_converged(sum3, q, n, tolerance, floor, prec="f32"):
+    """spira_adaptive_converged_*: the stopping rule as the library's host arithmetic, for ONE pixel (1, 0; raises on an error code)."""
+    npdt, cdt = _dt(prec)
+    s = np.ascontiguousarray(sum3, dtype=npdt)
+    assert s.shape == (3,)
+    fn = lib().spira_adaptive_converged_f32 if prec == "f32" else lib().spira_adaptive_converged_f64
+    fn.argtypes = [C.c_void_p, cdt, C.c_uint32, C.c_double, C.c_double]
+    rc = fn(s.ctypes.data_as(C.c_void_p), cdt(q), C.c_uint32(n), C.c_double(tolerance), C.c_double(floor))
+    if rc < 0:
+        _check(rc)
+    return rc
 
 
 def accumulate(spheres5, materials8, triangles10, camera12, params, sample0, sum_rgb, rng_states=None, prec="f32"):
