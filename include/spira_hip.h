@@ -330,6 +330,70 @@ int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const doubl
 int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor);
 int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, double tolerance, double floor);
 
+/* ---- first-hit feature buffers: per-pixel albedo, normal and depth, the guides of the denoiser below ----
+ * For samples 0 .. params->spp - 1 of each pixel: the camera ray every render entry takes (RNG key: global pixel, sample, bounce 0) and its closest
+ * hit as the renderer finds it (t_min 0.001, the later object wins ties, the BVH walk for meshes).  A hit on an object at distance t contributes
+ * albedo = the material's albedo triple, normal = the shading code's geometric normal (outward normalize(pos - centre) for a sphere, the unflipped
+ * unit normalize(cross(e1, e2)) for a triangle) and depth = t; a miss contributes albedo (1, 1, 1), normal 0 and depth 0.  Each output is the sum
+ * over the samples in sample order divided once by spp, in the call's precision, nothing fused; so depth > 0 exactly where some sample hit.
+ * out_albedo, out_normal: 3 planes, out_depth: 1 plane, all planar rows*width; any may be NULL, not all.  Tiling (rows / row0 / stripe_*) and
+ * SPIRA_ROWS_BOTTOM_UP as in every entry; max_depth is not used.  Scope: SPIRA_SEM_A with SPIRA_KERNEL_DEFAULT, both precisions, spheres, LDS
+ * triangles and BVH meshes; any other estimator or organisation and the SPIRA_EXT_* flags are SPIRA_E_UNSUPPORTED.  The *_device_* form is
+ * asynchronous on `stream` and ordered like every device entry.  spira_get_counters is not affected by these entries. */
+int spira_render_features_f32(const float *spheres5, const float *materials8, const float *triangles10,
+                              const float camera12[12], const spira_params *params,
+                              float *out_albedo, float *out_normal, float *out_depth);
+int spira_render_features_f64(const double *spheres5, const double *materials8, const double *triangles10,
+                              const double camera12[12], const spira_params *params,
+                              double *out_albedo, double *out_normal, double *out_depth);
+int spira_render_features_scene_f32(const spira_scene *scene, const float camera12[12], const spira_params *params,
+                                    float *out_albedo, float *out_normal, float *out_depth);
+int spira_render_features_scene_f64(const spira_scene *scene, const double camera12[12], const spira_params *params,
+                                    double *out_albedo, double *out_normal, double *out_depth);
+int spira_render_features_scene_device_f32(const spira_scene *scene, const float camera12[12], const spira_params *params,
+                                           float *d_out_albedo, float *d_out_normal, float *d_out_depth, void *stream);
+int spira_render_features_scene_device_f64(const spira_scene *scene, const double camera12[12], const spira_params *params,
+                                           double *d_out_albedo, double *d_out_normal, double *d_out_depth, void *stream);
+
+/* ---- denoiser: a variance-guided, feature-guided a-trous filter on a WHOLE frame ----
+ * color: 3 planes height*width (the out_hdr of a whole frame), required.  Optional guides, each independent of the others: variance (1 plane: the
+ * variance of the pixel's MEAN luminance), albedo (3 planes), normal (3 planes), depth (1 plane).  out_hdr / out_img: 3 planes each, either may be
+ * NULL, not both; out_hdr may alias color.  Limits: iterations 1 .. 6, sigma_l > 0, sigma_z > 0, post one of SPIRA_POST_*, width, height >= 1, else
+ * SPIRA_E_INVALID.  Defaults that work: sigma_l = 4, sigma_z = 0.1, iterations = 5.
+ * Arithmetic, all in the call's precision T in the written order, nothing fused, constants rounded to T once; luma(r, g, b) = (0.2126 r + 0.7152 g)
+ * + 0.0722 b; k = [1/16, 1/4, 3/8, 1/4, 1/16]; max(x, 0) is x > 0 ? x : 0:
+ *   prepare  albedo given: a = albedo + 0.001 per channel, c = color / a, ya = luma(a); else a = 1, c = color, ya = 1.
+ *            variance given: v = variance / (ya * ya) with albedo, else v = variance.
+ *   for it = 0 .. iterations - 1, s = 1 << it, at every pixel p:
+ *            y_p = luma(c_p).  variance given: g_p = the 3x3 blur of v around p (taps in row-major order, coordinates clamped to the image, weights
+ *            (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4), g = g + w_k * v_k), den = (sigma_l * sigma_l) * g_p + 1e-12.
+ *            The 25 taps q = p + s (dx, dy), dy = -2..2 outer, dx = -2..2 inner, taps outside the image skipped: w = k[dy+2] * k[dx+2];
+ *            depth given: hit_p = z_p > 0, hit_q = z_q > 0; hit_p != hit_q: w = 0; both hit: the normal factor when normal is given, then
+ *            t = max(1 - |z_p - z_q| / (sigma_z * max(z_p, z_q)), 0), w = w * (t * t); both miss: w as it is.
+ *            depth NULL and normal given: the normal factor alone, at every tap.
+ *            normal factor: e = max((n_p.x n_q.x + n_p.y n_q.y) + n_p.z n_q.z, 0), e squared six times, w = w * e.
+ *            variance given: dl = y_p - y_q, t = max(1 - (dl * dl) / den, 0), w = w * (t * t).
+ *            sw = sw + w, sc = sc + w * c_q per channel, sv = sv + (w * w) * v_q;  then c'_p = sc / sw, v'_p = sv / (sw * sw).
+ *   finish   out_hdr = c * a, out_img = post(out_hdr).
+ * The centre tap (dx = dy = 0) takes none of the depth, normal and luminance factors: it always weighs 9/64, so sw >= 9/64 for finite inputs.  (Its
+ * depth and luminance factors are 1 in any case; its normal factor would be |n_p|^128, and a normal averaged over samples that partly missed is short
+ * enough for that to underflow in Float32 and leave a silhouette pixel with 0 / 0.)  Non-finite inputs give unspecified values at the pixels they
+ * reach, never a fault.
+ * The host form copies in and out.  The *_device_* form takes DEVICE pointers and a stream, is ordered like every device entry, does not synchronise,
+ * and allocates only on its first call at a given size (the workspaces stay in the device context until spira_shutdown). */
+typedef struct spira_denoise {
+    uint32_t width, height, iterations, post;
+    double   sigma_l, sigma_z;
+} spira_denoise;             /* 32 bytes */
+int spira_denoise_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth,
+                      const spira_denoise *dn, float *out_hdr, float *out_img);
+int spira_denoise_f64(const double *color, const double *variance, const double *albedo, const double *normal, const double *depth,
+                      const spira_denoise *dn, double *out_hdr, double *out_img);
+int spira_denoise_device_f32(const float *d_color, const float *d_variance, const float *d_albedo, const float *d_normal, const float *d_depth,
+                             const spira_denoise *dn, float *d_out_hdr, float *d_out_img, void *stream);
+int spira_denoise_device_f64(const double *d_color, const double *d_variance, const double *d_albedo, const double *d_normal, const double *d_depth,
+                             const spira_denoise *dn, double *d_out_hdr, double *d_out_img, void *stream);
+
 /* ---- diagnostics: per-segment trace of chosen paths (parity tests compare geometry bitwise) ----
  * ijs: n_paths x [i, j, sample] with i in 1..width, j in 1..height (the loop indices of
  * examples/julia-raytracer.jl:392-397) and sample in 0..spp-1.  Outputs, per path and bounce b <

@@ -36,6 +36,7 @@
 #include "spira_validate.h"
 #include "spira_plan.h"
 #include "spira_adaptive.h"
+#include "spira_denoise.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -62,6 +63,10 @@ int trace_impl_f32(const float *spheres5, const float *materials8, const float *
                    uint32_t n_paths, const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance);
 int render_adaptive_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
                              const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream);
+int features_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
+                      float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream);
+int denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
+                     float *out_hdr, float *out_img, bool on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 void launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -120,6 +125,7 @@ struct Ctx {
     DevBuf multi_tile, multi_stack, multi_full;   // spira_render_multi_*: this device's tile; device 0: the gathered tiles, the frame
     DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
+    DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
     SceneStore scene;                         // the scene of the current call (host-array entry points)
     spira::Stats *h_stats = nullptr;          // pinned
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging of a host-output frame (copy_out below)
@@ -1371,6 +1377,146 @@ int adaptive_converged_host(const T *sum3, T q, uint32_t n, double tolerance, do
     return spira::adaptive_converged<T>(sum3[0], sum3[1], sum3[2], q, n, (T)tolerance, (T)floor) ? 1 : 0;
 }
 
+// ---- first-hit feature buffers (spira_render_features_*; spira_denoise.h, k_features): one launch over the tile, one lane per pixel walking its samples.
+// Asynchronous in the device-output form like every device entry; the counters of the last render are left as they are.
+template <class T>
+int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                  T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
+    uint32_t rows = 0;
+    tl_lds_optin = hipSuccess;
+    const T *some_out = out_albedo ? out_albedo : out_normal ? out_normal : out_depth;
+    if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, some_out, (const T *)nullptr, false, 0, nullptr, &rows)) return rc;
+    const char *msg = nullptr;
+    if (int rc = spira::features_check(p->flags, some_out != nullptr, &msg)) return fail(rc, msg);
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    Ctx &c = *cp;
+    std::lock_guard<std::recursive_mutex> lock(c.mu);
+    hipStream_t st = out_on_device ? (hipStream_t)user_stream : c.stream;
+    if (int rc = order_after_previous(c, st)) return rc;
+
+    spira::FeatureArgs<T> fa{};
+    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, p, fa.scene)) return rc;
+    fa.scene.spd = nullptr;
+    fill_const<T>(fa.rc, camera12, p, rows, 1);
+    const uint64_t tile_pixels = (uint64_t)rows * p->width;
+    if (!fastdiv_selfcheck(fa.rc.width, fa.rc.tile_pixels) || !fastdiv_selfcheck(fa.rc.stripe_h ? fa.rc.stripe_h : 1, rows))
+        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+    fa.albedo = out_albedo; fa.normal = out_normal; fa.depth = out_depth;
+    if (!out_on_device) {
+        if (int rc = c.out_tmp.ensure(7 * tile_pixels * sizeof(T))) return rc;
+        T *base = (T *)c.out_tmp.p;
+        fa.albedo = out_albedo ? base : nullptr;
+        fa.normal = out_normal ? base + 3 * tile_pixels : nullptr;
+        fa.depth = out_depth ? base + 6 * tile_pixels : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(fa.scene.n_spheres, fa.scene.n_materials, fa.scene.n_triangles);
+    const dim3 grid(spira::features_grid(tile_pixels, spira::kBlock, (uint32_t)c.num_cus)), block(spira::kBlock);
+    if (fa.scene.n_bvh_tris) launch_lds(spira::k_features<T, true, false>, grid, block, lds, st, fa);
+    else if (fa.scene.n_triangles) launch_lds(spira::k_features<T, false, true>, grid, block, lds, st, fa);
+    else launch_lds(spira::k_features<T, false, false>, grid, block, lds, st, fa);
+    if (int rc = lds_optin_failed()) return rc;
+    HIP_TRY(hipGetLastError());
+    if (!out_on_device) {
+        if (out_albedo) HIP_TRY(hipMemcpyAsync(out_albedo, fa.albedo, 3 * tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
+        if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal, fa.normal, 3 * tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
+        if (out_depth) HIP_TRY(hipMemcpyAsync(out_depth, fa.depth, tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+    if (int rc = mark_done(c, st)) return rc;
+    if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <class T>
+int features_entry(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                   T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::features_impl_f32(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
+    else
+#endif
+        return features_impl<T>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
+}
+
+// ---- the a-trous denoiser (spira_denoise_*; spira_denoise.h): prepare, then one launch per iteration between the context's two record buffers, the last
+// one writing the outputs.  The device form enqueues and returns; it allocates only when a workspace has to grow (a first call at a size).
+template <class T>
+int denoise_impl(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
+                 T *out_hdr, T *out_img, bool on_device, void *user_stream) {
+    using P4 = spira::Pack4<T>;
+    if (!dn) return fail(SPIRA_E_INVALID, "dn is NULL");
+    if (!color) return fail(SPIRA_E_INVALID, "color is NULL");
+    spira::DenoiseIn in;
+    in.width = dn->width; in.height = dn->height; in.iterations = dn->iterations; in.post = dn->post; in.sigma_l = dn->sigma_l; in.sigma_z = dn->sigma_z;
+    in.guides = (variance ? spira::kDenoiseVariance : 0u) | (albedo ? spira::kDenoiseAlbedo : 0u) | (normal ? spira::kDenoiseNormal : 0u) | (depth ? spira::kDenoiseDepth : 0u);
+    in.want_hdr = out_hdr != nullptr; in.want_img = out_img != nullptr; in.host = !on_device;
+    in.prec = sizeof(T); in.pack4 = sizeof(P4);
+    spira::DenoisePlan dp;
+    const char *msg = nullptr;
+    if (int rc = spira::make_denoise_plan(in, dp, &msg)) return fail(rc, msg);
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    Ctx &c = *cp;
+    std::lock_guard<std::recursive_mutex> lock(c.mu);
+    hipStream_t st = on_device ? (hipStream_t)user_stream : c.stream;
+    if (int rc = order_after_previous(c, st)) return rc;
+    for (int i = 0; i < 2; ++i) if (int rc = c.dn_rec[i].ensure(dp.rec_bytes)) return rc;
+    if (int rc = c.dn_guide.ensure(dp.guide_bytes)) return rc;
+    if (int rc = c.dn_io.ensure(dp.io_bytes)) return rc;
+
+    spira::DenoiseArgs<T> a{};
+    a.color = color; a.variance = variance; a.albedo = albedo; a.normal = normal; a.depth = depth;
+    a.out_hdr = out_hdr; a.out_img = out_img;
+    const size_t npix = (size_t)dp.npix;
+    if (!on_device) {                    // stage the given planes in, the wanted ones out
+        T *base = (T *)c.dn_io.p;
+        const T *host_in[5] = {color, variance, albedo, normal, depth};
+        const T **dev_in[5] = {&a.color, &a.variance, &a.albedo, &a.normal, &a.depth};
+        const size_t planes[5] = {3, 1, 3, 3, 1};
+        for (int k = 0; k < 5; ++k)
+            if (dp.in_off[k] >= 0) {
+                T *d = base + (size_t)dp.in_off[k] * npix;
+                HIP_TRY(hipMemcpyAsync(d, host_in[k], planes[k] * npix * sizeof(T), hipMemcpyHostToDevice, st));
+                *dev_in[k] = d;
+            }
+        T *o = base + (size_t)dp.in_planes * npix;
+        a.out_hdr = out_hdr ? o : nullptr;
+        a.out_img = out_img ? o + (out_hdr ? 3 * npix : 0) : nullptr;
+    }
+    a.rec[0] = (P4 *)c.dn_rec[0].p; a.rec[1] = (P4 *)c.dn_rec[1].p;
+    a.guide = dp.guide_bytes ? (P4 *)c.dn_guide.p : nullptr;
+    a.width = dn->width; a.height = dn->height; a.npix = (uint32_t)dp.npix; a.tiles_x = dp.tiles_x;
+    a.post = dn->post;
+    a.sigma_l = (T)dn->sigma_l; a.sigma_z = (T)dn->sigma_z;
+    if (!(a.sigma_l > (T)0) || !(a.sigma_z > (T)0)) return fail(SPIRA_E_INVALID, "spira_denoise: a sigma rounds to zero in the call's precision");
+    const dim3 block(spira::kBlock);
+    hipLaunchKernelGGL((spira::k_denoise_prepare<T>), dim3(dp.grid_flat), block, 0, st, a);
+    int src = 0;
+    for (uint32_t it = 0; it < dn->iterations; ++it, src ^= 1) {
+        if (it + 1 < dn->iterations) hipLaunchKernelGGL((spira::k_denoise_iter<T, false>), dim3(dp.grid), block, 0, st, a, dp.step(it), src);
+        else hipLaunchKernelGGL((spira::k_denoise_iter<T, true>), dim3(dp.grid), block, 0, st, a, dp.step(it), src);
+    }
+    HIP_TRY(hipGetLastError());
+    if (!on_device) {
+        if (out_hdr) HIP_TRY(hipMemcpyAsync(out_hdr, a.out_hdr, 3 * npix * sizeof(T), hipMemcpyDeviceToHost, st));
+        if (out_img) HIP_TRY(hipMemcpyAsync(out_img, a.out_img, 3 * npix * sizeof(T), hipMemcpyDeviceToHost, st));
+    }
+    if (int rc = mark_done(c, st)) return rc;
+    if (!on_device) HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+template <class T>
+int denoise_entry(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
+                  T *out_hdr, T *out_img, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::denoise_impl_f32(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
+    else
+#endif
+        return denoise_impl<T>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
+}
+
 template <class T>
 int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
                uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance) {
@@ -1766,6 +1912,14 @@ int spira_tu::render_adaptive_impl_f32(const spira_scene *h, const float *sphere
                                        const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream) {
     return render_adaptive_impl<float>(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
 }
+int spira_tu::features_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
+                                float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream) {
+    return features_impl<float>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
+}
+int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
+                               float *out_hdr, float *out_img, bool on_device, void *user_stream) {
+    return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
+}
 #else
 // ======================================================================= C ABI (SPIRA_TU_MAIN, or the single translation unit)
 extern "C" {
@@ -1855,6 +2009,7 @@ void spira_shutdown(void) {
         c.redo.release(); c.L.release(); c.accum.release(); c.counts.release(); c.blkstats.release(); c.stats.release(); c.scene.release(); c.out_tmp.release(); c.trace.release(); c.rng.release(); c.multi_tile.release(); c.multi_stack.release(); c.multi_full.release(); c.spd32.release(); c.spd64.release(); c.hyb_state.release(); c.hyb_mat.release(); c.hyb_flags.release();
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
+        c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
         for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
         c.ev_pool.clear();
         for (hipEvent_t e : c.ev_mid) (void)hipEventDestroy(e);
@@ -2013,6 +2168,52 @@ int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, doubl
 }
 int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, double tolerance, double floor) {
     return adaptive_converged_host<double>(sum3, q, n, tolerance, floor);
+}
+
+// ---- first-hit feature buffers (host arrays; a handle; a handle and device outputs on the caller's stream)
+int spira_render_features_f32(const float *s, const float *m, const float *t, const float cam[12], const spira_params *p,
+                              float *out_albedo, float *out_normal, float *out_depth) {
+    return features_entry<float>(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+}
+int spira_render_features_f64(const double *s, const double *m, const double *t, const double cam[12], const spira_params *p,
+                              double *out_albedo, double *out_normal, double *out_depth) {
+    return features_entry<double>(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+}
+int spira_render_features_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, float *out_albedo, float *out_normal, float *out_depth) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return features_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+}
+int spira_render_features_scene_f64(const spira_scene *scene, const double cam[12], const spira_params *p, double *out_albedo, double *out_normal, double *out_depth) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return features_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+}
+int spira_render_features_scene_device_f32(const spira_scene *scene, const float cam[12], const spira_params *p,
+                                           float *d_albedo, float *d_normal, float *d_depth, void *stream) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return features_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
+}
+int spira_render_features_scene_device_f64(const spira_scene *scene, const double cam[12], const spira_params *p,
+                                           double *d_albedo, double *d_normal, double *d_depth, void *stream) {
+    if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    return features_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
+}
+
+// ---- the a-trous denoiser (host planes; device planes on the caller's stream)
+int spira_denoise_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
+                      float *out_hdr, float *out_img) {
+    return denoise_entry<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
+}
+int spira_denoise_f64(const double *color, const double *variance, const double *albedo, const double *normal, const double *depth, const spira_denoise *dn,
+                      double *out_hdr, double *out_img) {
+    return denoise_entry<double>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
+}
+int spira_denoise_device_f32(const float *d_color, const float *d_variance, const float *d_albedo, const float *d_normal, const float *d_depth, const spira_denoise *dn,
+                             float *d_out_hdr, float *d_out_img, void *stream) {
+    return denoise_entry<float>(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
+}
+int spira_denoise_device_f64(const double *d_color, const double *d_variance, const double *d_albedo, const double *d_normal, const double *d_depth, const spira_denoise *dn,
+                             double *d_out_hdr, double *d_out_img, void *stream) {
+    return denoise_entry<double>(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
 }
 
 // ---- multi-device render on one node: interleaved 8-row stripes, one host thread + stream per device, one RCCL gather

@@ -288,4 +288,75 @@ inline int make_adaptive_plan(const AdaptiveIn &in, AdaptivePlan &ap, const char
     return 0;
 }
 
+// ---- first-hit feature buffers (spira_render_features_*) and the a-trous denoiser (spira_denoise_*); kernels in spira_denoise.h.
+// The scope of the feature entries: SPIRA_SEM_A with SPIRA_KERNEL_DEFAULT, no extension.
+inline int features_check(uint32_t flags, bool any_output, const char **msg) {
+    if (!any_output) { *msg = "all three feature outputs are NULL"; return SPIRA_E_INVALID; }
+    if ((flags & SPIRA_SEM_MASK) != SPIRA_SEM_A) { *msg = "feature buffers are built for SPIRA_SEM_A only"; return SPIRA_E_UNSUPPORTED; }
+    if ((flags & SPIRA_KERNEL_MASK) != SPIRA_KERNEL_DEFAULT) { *msg = "feature buffers have one kernel organisation: SPIRA_KERNEL_DEFAULT"; return SPIRA_E_UNSUPPORTED; }
+    if (flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) { *msg = "SPIRA_EXT_* extensions are not built into the feature kernel"; return SPIRA_E_UNSUPPORTED; }
+    return 0;
+}
+// one lane per pixel of the tile, workgroups of `block` lanes, at most max_blocks of them (the kernel strides)
+inline uint32_t features_grid(uint64_t tile_pixels, uint32_t block, uint32_t num_cus) {
+    const uint64_t cap = std::max<uint64_t>(1, (uint64_t)num_cus * 64);
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tile_pixels + block - 1) / block, cap));
+}
+
+// The denoiser works on whole frames.  A workgroup of kDenoiseTileH waves covers a tile of kDenoiseTileW x kDenoiseTileH pixels, a wave 64 contiguous
+// pixels of one row; iteration `it` reaches 2 << it pixels to every side.  Per pixel: one colour record {c.rgb, v} in each of two ping-pong buffers and,
+// when a normal or a depth plane is given, one guide record {n.xyz, z}, each a Pack4<T>.  The host form stages its planes in one input and one output block.
+constexpr uint32_t kDenoiseTileW = 64, kDenoiseTileH = 4, kDenoiseMaxIter = 6;
+enum : uint32_t { kDenoiseVariance = 1, kDenoiseAlbedo = 2, kDenoiseNormal = 4, kDenoiseDepth = 8 };
+struct DenoiseIn {
+    uint32_t width = 0, height = 0, iterations = 0, post = 0;
+    double sigma_l = 0, sigma_z = 0;
+    uint32_t guides = 0;                       // kDenoise* bits: the planes given
+    bool want_hdr = false, want_img = false, host = false;
+    uint32_t prec = 0, pack4 = 0;              // sizeof(T), sizeof(Pack4<T>)
+};
+struct DenoisePlan {
+    DenoiseIn in;
+    uint64_t npix = 0;
+    uint32_t tiles_x = 0, tiles_y = 0, grid = 0;           // grid = tiles_x * tiles_y workgroups of kDenoiseTileW * kDenoiseTileH lanes
+    uint32_t grid_flat = 0;                                // prepare: one lane per pixel
+    uint64_t rec_bytes = 0, guide_bytes = 0;               // each ping-pong buffer; the guide records (0: no normal and no depth)
+    uint64_t in_planes = 0, out_planes = 0, io_bytes = 0;  // host form: planes staged in, planes staged out, the block that holds both
+    // host form: plane offset (in planes) of each input inside the staging block, in the order color, variance, albedo, normal, depth; -1: not given
+    int64_t in_off[5] = {-1, -1, -1, -1, -1};
+    uint32_t step(uint32_t it) const { return 1u << it; }
+    uint32_t reach(uint32_t it) const { return 2u << it; }
+};
+inline int denoise_check(uint32_t width, uint32_t height, uint32_t iterations, uint32_t post, double sigma_l, double sigma_z, const char **msg) {
+    if (width < 1 || height < 1) { *msg = "spira_denoise: width and height must be >= 1"; return SPIRA_E_INVALID; }
+    if (iterations < 1 || iterations > kDenoiseMaxIter) { *msg = "spira_denoise: iterations must be 1 .. 6"; return SPIRA_E_INVALID; }
+    if (!(sigma_l > 0) || !(sigma_z > 0)) { *msg = "spira_denoise: sigma_l and sigma_z must be > 0"; return SPIRA_E_INVALID; }
+    if (post != SPIRA_POST_ACES && post != SPIRA_POST_ACES_GAMMA && post != SPIRA_POST_CLAMP_GAMMA && post != SPIRA_POST_NONE) {
+        *msg = "spira_denoise: post must be one of SPIRA_POST_*"; return SPIRA_E_INVALID;
+    }
+    return 0;
+}
+inline int make_denoise_plan(const DenoiseIn &in, DenoisePlan &dp, const char **msg) {
+    dp = DenoisePlan{};
+    dp.in = in;
+    if (int rc = denoise_check(in.width, in.height, in.iterations, in.post, in.sigma_l, in.sigma_z, msg)) return rc;
+    if (!in.want_hdr && !in.want_img) { *msg = "both outputs are NULL"; return SPIRA_E_INVALID; }
+    dp.npix = (uint64_t)in.width * in.height;
+    if (dp.npix > 0x7FFFFFFFull) { *msg = "image larger than 2^31 pixels"; return SPIRA_E_LIMIT; }
+    dp.tiles_x = (in.width + kDenoiseTileW - 1) / kDenoiseTileW;
+    dp.tiles_y = (in.height + kDenoiseTileH - 1) / kDenoiseTileH;
+    dp.grid = (uint32_t)((uint64_t)dp.tiles_x * dp.tiles_y);               // <= npix
+    dp.grid_flat = (uint32_t)((dp.npix + kDenoiseTileW * kDenoiseTileH - 1) / (kDenoiseTileW * kDenoiseTileH));
+    dp.rec_bytes = dp.npix * in.pack4;
+    dp.guide_bytes = (in.guides & (kDenoiseNormal | kDenoiseDepth)) ? dp.npix * in.pack4 : 0;
+    if (in.host) {
+        const uint32_t bit[5] = {0, kDenoiseVariance, kDenoiseAlbedo, kDenoiseNormal, kDenoiseDepth}, planes[5] = {3, 1, 3, 3, 1};
+        for (int k = 0; k < 5; ++k)
+            if (k == 0 || (in.guides & bit[k])) { dp.in_off[k] = (int64_t)dp.in_planes; dp.in_planes += planes[k]; }
+        dp.out_planes = (in.want_hdr ? 3 : 0) + (in.want_img ? 3 : 0);
+        dp.io_bytes = (dp.in_planes + dp.out_planes) * dp.npix * in.prec;
+    }
+    return 0;
+}
+
 }  // namespace spira

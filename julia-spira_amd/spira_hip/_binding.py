@@ -35,6 +35,9 @@ EXPORTS = [
     "spira_render_multi_scene_f32", "spira_render_multi_scene_f64",
     "spira_render_adaptive_f32", "spira_render_adaptive_f64", "spira_render_adaptive_scene_f32", "spira_render_adaptive_scene_f64",
     "spira_render_adaptive_scene_device_f32", "spira_render_adaptive_scene_device_f64", "spira_adaptive_converged_f32", "spira_adaptive_converged_f64",
+    "spira_render_features_f32", "spira_render_features_f64", "spira_render_features_scene_f32", "spira_render_features_scene_f64",
+    "spira_render_features_scene_device_f32", "spira_render_features_scene_device_f64",
+    "spira_denoise_f32", "spira_denoise_f64", "spira_denoise_device_f32", "spira_denoise_device_f64",
 ]
 
 
@@ -63,6 +66,12 @@ class Counters(C.Structure):
 class Adaptive(C.Structure):
     """spira_adaptive: the schedule of an adaptive render (params.spp is the cap)."""
     _fields_ = [("min_spp", C.c_uint32), ("batch_spp", C.c_uint32), ("tolerance", C.c_double), ("floor", C.c_double)]
+
+
+class Denoise(C.Structure):
+    """spira_denoise: the frame size and the settings of a denoise call."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("post", C.c_uint32),
+                ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
 
 
 _lib = None
@@ -282,6 +291,76 @@ class Scene:
         fn = lib().spira_render_adaptive_scene_device_f32 if self.prec == "f32" else lib().spira_render_adaptive_scene_device_f64
         _check(fn(self._h, cp, C.byref(params), C.byref(adaptive), C.c_void_p(d_hdr_ptr or None), C.c_void_p(d_img_ptr or None),
                   C.c_void_p(d_spp_ptr or None), C.c_void_p(d_q_ptr or None), C.c_void_p(stream_ptr or None)))
+
+
+    def render_features(self, camera12, params, want_albedo=True, want_normal=True, want_depth=True):
+        """spira_render_features_scene_*: returns (albedo [3, rows, W], normal [3, rows, W], depth [rows, W]); None where not wanted."""
+        npdt, _ = _dt(self.prec)
+        c, cp = _arr(camera12, npdt)
+        outs, ptrs = _feature_outputs(params, npdt, want_albedo, want_normal, want_depth)
+        fn = lib().spira_render_features_scene_f32 if self.prec == "f32" else lib().spira_render_features_scene_f64
+        _check(fn(self._h, cp, C.byref(params), *ptrs))
+        return outs
+
+    def render_features_device(self, camera12, params, d_albedo_ptr, d_normal_ptr, d_depth_ptr, stream_ptr):
+        """spira_render_features_scene_device_*: DEVICE output addresses (0 / None: not wanted), asynchronous on the stream."""
+        npdt, _ = _dt(self.prec)
+        c, cp = _arr(camera12, npdt)
+        fn = lib().spira_render_features_scene_device_f32 if self.prec == "f32" else lib().spira_render_features_scene_device_f64
+        _check(fn(self._h, cp, C.byref(params), C.c_void_p(d_albedo_ptr or None), C.c_void_p(d_normal_ptr or None), C.c_void_p(d_depth_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
+
+def _feature_outputs(params, npdt, want_albedo, want_normal, want_depth):
+    rows = params.rows if params.rows else params.height
+    outs = (np.empty((3, rows, params.width), dtype=npdt) if want_albedo else None, np.empty((3, rows, params.width), dtype=npdt) if want_normal else None,
+            np.empty((rows, params.width), dtype=npdt) if want_depth else None)
+    return outs, [o.ctypes.data_as(C.c_void_p) if o is not None else None for o in outs]
+
+
+def render_features(spheres5, materials8, triangles10, camera12, params, prec="f32", want_albedo=True, want_normal=True, want_depth=True):
+    """spira_render_features_*: host arrays, host outputs.  Returns (albedo, normal, depth): the first-hit features averaged over params.spp camera
+    rays per pixel ([3, rows, W], [3, rows, W], [rows, W]); None where not wanted."""
+    npdt, _ = _dt(prec)
+    s, sp = _arr(spheres5, npdt)
+    m, mp = _arr(materials8, npdt)
+    t, tp = _arr(triangles10, npdt)
+    c, cp = _arr(camera12, npdt)
+    outs, ptrs = _feature_outputs(params, npdt, want_albedo, want_normal, want_depth)
+    fn = lib().spira_render_features_f32 if prec == "f32" else lib().spira_render_features_f64
+    _check(fn(sp, mp, tp, cp, C.byref(params), *ptrs))
+    return outs
+
+
+def make_denoise(width, height, iterations=5, post=POST_ACES, sigma_l=4.0, sigma_z=0.1):
+    return Denoise(width, height, iterations, post, sigma_l, sigma_z)
+
+
+def denoise(color, dn, variance=None, albedo=None, normal=None, depth=None, prec="f32", want_hdr=True, want_img=False, in_place=False):
+    """spira_denoise_*: host planes in, host planes out.  color [3, H, W]; variance / depth [H, W] and albedo / normal [3, H, W] or None.
+    Returns (hdr, img); in_place: out_hdr is `color` itself (it must then be a contiguous array of the call's precision, and is overwritten)."""
+    npdt, _ = _dt(prec)
+    if in_place:
+        assert want_hdr and color.dtype == npdt and color.flags["C_CONTIGUOUS"]
+    c, cp = _arr(color, npdt)
+    arrs = [_arr(x, npdt) for x in (variance, albedo, normal, depth)]
+    shape = (3, dn.height, dn.width)
+    assert c.shape == shape
+    for (x, _), want in zip(arrs, (shape[1:], shape, shape, shape[1:])):
+        assert x is None or x.shape == want
+    hdr = c if in_place else (np.empty(shape, dtype=npdt) if want_hdr else None)
+    img = np.empty(shape, dtype=npdt) if want_img else None
+    fn = lib().spira_denoise_f32 if prec == "f32" else lib().spira_denoise_f64
+    _check(fn(cp, arrs[0][1], arrs[1][1], arrs[2][1], arrs[3][1], C.byref(dn), hdr.ctypes.data_as(C.c_void_p) if hdr is not None else None,
+              img.ctypes.data_as(C.c_void_p) if img is not None else None))
+    return hdr, img
+
+
+def denoise_device(d_color_ptr, dn, d_out_hdr_ptr, d_out_img_ptr, stream_ptr, d_variance_ptr=0, d_albedo_ptr=0, d_normal_ptr=0, d_depth_ptr=0, prec="f32"):
+    """spira_denoise_device_*: DEVICE plane addresses (0 / None: not given / not wanted); enqueues on the stream and returns."""
+    fn = lib().spira_denoise_device_f32 if prec == "f32" else lib().spira_denoise_device_f64
+    _check(fn(C.c_void_p(d_color_ptr or None), C.c_void_p(d_variance_ptr or None), C.c_void_p(d_albedo_ptr or None), C.c_void_p(d_normal_ptr or None),
+              C.c_void_p(d_depth_ptr or None), C.byref(dn), C.c_void_p(d_out_hdr_ptr or None), C.c_void_p(d_out_img_ptr or None), C.c_void_p(stream_ptr or None)))
 
 
 def make_adaptive(min_spp, batch_spp, tolerance, floor=0.0):
