@@ -1235,7 +1235,147 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Per-bounce wavefront kernel.  FIRST generates the camera ray in registers (no queue read)
+// ------------------------------------------------------------------ the wave's random-vector list (phase 2 of k_bounce / k_path)
+// Phase 1 leaves n_list RNG keys in the wave's LDS slots (words 0, 1 of slot e); drain_unit_sphere_list() replaces each by
+// random_in_unit_sphere() of that key; phase 3 reads the vector of its entry with RndTry<T>::load().  Whether try t of a key is accepted is
+// a pure function of (key, t), so WHICH lane evaluates it does not matter: the vector is that of the lowest accepted t <= MAXT, or zero.
+//   SPIRA_RND_TAIL  1: once no unclaimed entry is left and at most 32 are pending, idle lanes evaluate LATER tries of the pending entries
+//                      (groups of g lanes per entry) instead of waiting for each entry's own lane;  0: one lane per entry to the end.
+//   SPIRA_RND_INT   1: Float64 accepts by an exact integer test and keeps the accepted draw as its two hash words;  0: the floating-point test
+//                      and a Pack4 result in both precisions.  (Float32 always: its squares round, the test has to be the floating-point one.)
+#ifndef SPIRA_RND_TAIL
+#define SPIRA_RND_TAIL 1
+#endif
+#ifndef SPIRA_RND_INT
+#define SPIRA_RND_INT 1
+#endif
+template <class T> constexpr bool kRndPacked = SPIRA_RND_INT && sizeof(T) == 8;
+
+// One try of random_in_unit_sphere (:311-312) and the list slot's result format.
+template <class T, bool PACKED = kRndPacked<T>> struct RndTry {
+    Vec<T> c;
+    __device__ __forceinline__ bool draw(const RngKey &k, uint32_t t) {
+        T u0, u1, u2;
+        rng3<T>(k, t, u0, u1, u2, (T)(1.0 / 1048576.0));                // 2*u: the doubling of :311 is exact, folded into the scale
+        c = mk<T>(u0, u1, u2) - mk<T>(1, 1, 1);                         // :311
+        return dot(c, c) < (T)1.0;                                      // :312
+    }
+    __device__ __forceinline__ void zero() { c = mk<T>(0, 0, 0); }
+    __device__ __forceinline__ void store(Pack4<T> *slot) const { Pack4<T> w; w.x = c.x; w.y = c.y; w.z = c.z; w.w = 0; *slot = w; }
+    static __device__ __forceinline__ Vec<T> load(const Pack4<T> *slot) { const Pack4<T> w = *slot; return mk<T>(w.x, w.y, w.z); }
+};
+// Float64.  rng3 makes the three uniforms from the hash words a, b as m * 2^-20 with integers m < 2^21 (m0 = a >> 11, m1 = b >> 11,
+// m2 = (a & 0x7FF) << 10 | (b & 0x3FF)), exactly.  Then c = m * 2^-20 - 1 = (m - 2^20) * 2^-20 is exact; with k = m - 2^20, |k| <= 2^20,
+// every c*c = k*k * 2^-40 has at most 41 significant bits and is exact; the partial sums of dot(c, c) are multiples of 2^-40 below 3, at
+// most 42 bits, exact.  So `dot(c, c) < 1.0` of :312 is true exactly when k0*k0 + k1*k1 + k2*k2 < 2^40 in 64-bit integers: no conversion,
+// no ldexp, no Float64 arithmetic per try.  The accepted draw is kept as (a, b) — the three m are bit fields of them — and load() makes
+// the doubles with rng3's own statements and :311, once per entry.  The zero vector of an exhausted entry is the pair with every m = 2^20.
+template <class T> struct RndTry<T, true> {
+    uint32_t a, b;
+    __device__ __forceinline__ bool draw(const RngKey &k, uint32_t t) {
+        a = mix32((k.hA + t * 0x9E3779B9u) ^ k.hBr);                    // rng3's two words
+        b = mix32(a + k.hB);
+        const int32_t k0 = (int32_t)(a >> 11) - (1 << 20), k1 = (int32_t)(b >> 11) - (1 << 20);
+        const int32_t k2 = (int32_t)(((a & 0x7FFu) << 10) | (b & 0x3FFu)) - (1 << 20);
+        const uint64_t s = (uint64_t)((int64_t)k0 * k0) + (uint64_t)((int64_t)k1 * k1) + (uint64_t)((int64_t)k2 * k2);
+        return s < (1ull << 40);
+    }
+    __device__ __forceinline__ void zero() { a = 0x80000400u; b = 0x80000000u; }
+    __device__ __forceinline__ void store(Pack4<T> *slot) const { *reinterpret_cast<uint2 *>(slot) = make_uint2(a, b); }
+    static __device__ __forceinline__ Vec<T> load(const Pack4<T> *slot) {
+        const uint2 w = *reinterpret_cast<const uint2 *>(slot);
+        const T s = (T)(1.0 / 1048576.0);
+        const T u0 = (T)(w.x >> 11) * s, u1 = (T)(w.y >> 11) * s, u2 = (T)(((w.x & 0x7FFu) << 10) | (w.y & 0x3FFu)) * s;      // rng3
+        return mk<T>(u0, u1, u2) - mk<T>(1, 1, 1);                      // :311
+    }
+};
+
+// Main phase: lane l starts on entry l and keeps trying it; a lane that finishes claims the next unclaimed entry (ballot prefix).
+// Tail phase (SPIRA_RND_TAIL), from the iteration at which no unclaimed entry is left and p <= 32 entries are pending: the pending
+// (entry, next try t0) pairs are compacted into a table (the LAST word of list slots 0 .. p-1: the unread half of a result's w, so
+// no LDS beyond the list), lanes form groups of g = the largest power of two with g*p <= 64 (at most 32: a group then lies in one half of the
+// ballot), lane j of a group evaluates try t0 + j if that is <= MAXT, and the lane of the lowest accepted try writes the result.  A group
+// without an accept advances t0 by g; when that passes MAXT every allowed try has failed and the entry gets the zero vector, as in
+// random_in_unit_sphere.  Groups are formed again whenever enough entries have finished for g to double (re-forming with the same g would give
+// no entry more tries).  Every iteration ends an entry or raises its t0, which MAXT bounds: the loop ends on any input.
+template <class T, uint32_t MAXT = kMaxTries>
+__device__ __forceinline__ void drain_unit_sphere_list(Pack4<T> *s_rnd, uint32_t n_list, uint32_t lane) {
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    uint32_t e = lane, t = 1, next = 64;
+    bool have = e < n_list;
+    RngKey k; k.hA = 0; k.hB = 0; k.hBr = 0;
+    if (have) {
+        const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
+        k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
+    }
+#if SPIRA_RND_TAIL
+    unsigned long long pm = __ballot(have);
+    while (pm != 0 && (next < n_list || __popcll(pm) > 32)) {
+#else
+    while (__any(have)) {
+#endif
+        bool done = false;
+        if (have) {
+            RndTry<T> r;
+            done = r.draw(k, t);
+            if (!done && t == MAXT) { r.zero(); done = true; }
+            if (done) r.store(&s_rnd[e]);
+            ++t;
+        }
+        const unsigned long long m = __ballot(done);
+        if (done) {                                   // take the next unclaimed entry
+            e = next + __popcll(m & lt_mask); t = 1;
+            have = e < n_list;
+            if (have) {
+                const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
+                k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
+            }
+        }
+        next += (uint32_t)__popcll(m);
+#if SPIRA_RND_TAIL
+        pm = __ballot(have);
+#endif
+    }
+#if SPIRA_RND_TAIL
+    constexpr uint32_t kSlotWords = sizeof(Pack4<T>) / 4;
+    uint32_t *tab = reinterpret_cast<uint32_t *>(s_rnd) + (kSlotWords - 1);
+    uint32_t p = (uint32_t)__popcll(pm), lg = ~0u;
+    bool lead = have;                                 // the lanes that hold a pending (e, t): the entry's own lane, later its group's first
+    while (p != 0) {                                  // wave-uniform
+        const uint32_t lg_new = min(5u, 6u - (32u - (uint32_t)__clz((int)(p - 1))));
+        if (lg_new != lg) {                           // (wave-uniform) form groups of 1 << lg lanes
+            lg = lg_new;
+            if (lead) tab[kSlotWords * (uint32_t)__popcll(pm & lt_mask)] = e | (t << 16);
+            wave_lds_sync();
+            const uint32_t grp = lane >> lg;
+            have = grp < p;
+            if (have) {
+                const uint32_t w = tab[kSlotWords * grp];
+                e = w & 0xFFFFu; t = w >> 16;
+                const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
+                k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
+            }
+        }
+        const uint32_t g = 1u << lg, j = lane & (g - 1u);
+        RndTry<T> r;
+        bool acc = false;
+        if (have && t + j <= MAXT) acc = r.draw(k, t + j);
+        const unsigned long long m = __ballot(acc);
+        const uint32_t half = lane < 32u ? (uint32_t)m : (uint32_t)(m >> 32);
+        const uint32_t field = (half >> ((lane & 31u) - j)) & (0xFFFFFFFFu >> (32u - g));        // the accepts of this lane's group
+        if (acc && (field & ((1u << j) - 1u)) == 0u) r.store(&s_rnd[e]);                         // the lowest accepted try
+        const bool over = field == 0u && t + g > MAXT;                                           // tries 1 .. MAXT all failed
+        if (have && over && j == 0u) { r.zero(); r.store(&s_rnd[e]); }
+        have = have && field == 0u && !over;          // a finished group idles until groups are formed again
+        t += g;
+        lead = have && j == 0u;
+        pm = __ballot(lead);
+        p = (uint32_t)__popcll(pm);
+    }
+#endif
+}
+
+// Per-bounce wavefront kernel. FIRST generates the camera ray in registers (no queue read)
 // and stores the path's first radiance term; later bounces read compacted rays, RMW the path
 // radiance only when the segment contributes, and append survivors to the other queue.
 //
@@ -1356,37 +1496,7 @@ __global__ __launch_bounds__(kBlock, SPIRA_WAVES_PER_SIMD(T)) void k_bounce(cons
         if (!scatter) continue;        // uniform: the last bounce neither scatters nor enqueues
         wave_lds_sync();
         // ---------------- phase 2: cooperative random_in_unit_sphere() over the wave's work list
-        {
-            uint32_t e = lane, t = 1, next = 64;
-            bool have = e < n_list;
-            RngKey k; k.hA = 0; k.hB = 0; k.hBr = 0;
-            if (have) {
-                const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
-                k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
-            }
-            while (__any(have)) {
-                bool done = false;
-                if (have) {
-                    T u0, u1, u2;
-                    rng3<T>(k, t, u0, u1, u2, (T)(1.0 / 1048576.0));
-                    Vec<T> c = mk<T>(u0, u1, u2) - mk<T>(1, 1, 1);                   // :311
-                    done = dot(c, c) < (T)1.0;                                      // :312
-                    if (!done && t == kMaxTries) { c = mk<T>(0, 0, 0); done = true; }
-                    if (done) { Pack4<T> w; w.x = c.x; w.y = c.y; w.z = c.z; w.w = 0; s_rnd[e] = w; }
-                    ++t;
-                }
-                const unsigned long long m = __ballot(done);
-                if (done) {                                   // take the next unclaimed entry
-                    e = next + __popcll(m & lt_mask); t = 1;
-                    have = e < n_list;
-                    if (have) {
-                        const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
-                        k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
-                    }
-                }
-                next += (uint32_t)__popcll(m);
-            }
-        }
+        drain_unit_sphere_list<T>(s_rnd, n_list, lane);
         wave_lds_sync();
         // ---------------- phase 3: directions, compaction into this wave's region of the out queue
 #pragma unroll
@@ -1395,7 +1505,7 @@ __global__ __launch_bounds__(kBlock, SPIRA_WAVES_PER_SIMD(T)) void k_bounce(cons
             const unsigned long long m = __ballot(alive);
             if (alive) {
                 Vec<T> rnd = mk<T>(0, 0, 0);
-                if (pend[r].kind != kMirror) { const Pack4<T> w = s_rnd[ent[r]]; rnd = mk<T>(w.x, w.y, w.z); }
+                if (pend[r].kind != kMirror) rnd = RndTry<T>::load(&s_rnd[ent[r]]);
                 const Vec<T> nd = segment_back<T>(o[r], pend[r], rnd);
                 const uint32_t dst = region + fill + __popcll(m & lt_mask);
                 Pack4<T> A, B; Pack2<T> C;
@@ -1817,37 +1927,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                 if (n_valid == 0) break;           // wave-uniform: nobody scatters (last segments, or an empty tail)
                 wave_lds_sync();
                 // ---- phase 2: cooperative random_in_unit_sphere() over the wave's work list
-                {
-                    uint32_t e = lane, t = 1, next = 64;
-                    bool have = e < n_list;
-                    RngKey k; k.hA = 0; k.hB = 0; k.hBr = 0;
-                    if (have) {
-                        const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
-                        k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
-                    }
-                    while (__any(have)) {
-                        bool done = false;
-                        if (have) {
-                            T u0, u1, u2;
-                            rng3<T>(k, t, u0, u1, u2, (T)(1.0 / 1048576.0));
-                            Vec<T> c = mk<T>(u0, u1, u2) - mk<T>(1, 1, 1);                   // :311
-                            done = dot(c, c) < (T)1.0;                                      // :312
-                            if (!done && t == kMaxTries) { c = mk<T>(0, 0, 0); done = true; }
-                            if (done) { Pack4<T> w; w.x = c.x; w.y = c.y; w.z = c.z; w.w = 0; s_rnd[e] = w; }
-                            ++t;
-                        }
-                        const unsigned long long m = __ballot(done);
-                        if (done) {                                   // take the next unclaimed entry
-                            e = next + __popcll(m & lt_mask); t = 1;
-                            have = e < n_list;
-                            if (have) {
-                                const uint32_t *kw = reinterpret_cast<const uint32_t *>(&s_rnd[e]);
-                                k.hA = kw[0]; k.hB = kw[1]; k.hBr = (k.hB << 16) | (k.hB >> 16);
-                            }
-                        }
-                        next += (uint32_t)__popcll(m);
-                    }
-                }
+                drain_unit_sphere_list<T>(s_rnd, n_list, lane);
                 wave_lds_sync();
                 // ---- phase 3: direction, closest hit of segment stg[r] + 1
                 uint32_t n_hit = 0;
@@ -1857,7 +1937,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                     T park_t3 = 0; int park_prim3 = -1;
                     if (pend[r].kind != kDead) {
                         Vec<T> rnd = mk<T>(0, 0, 0);
-                        if (pend[r].kind != kMirror) { const Pack4<T> w = s_rnd[ent[r]]; rnd = mk<T>(w.x, w.y, w.z); }
+                        if (pend[r].kind != kMirror) rnd = RndTry<T>::load(&s_rnd[ent[r]]);
                         const Vec<T> nd = segment_back<T>(o[r], pend[r], rnd, pol);
                         T t; uint32_t slot = 0;
                         int prim;
