@@ -10,6 +10,9 @@
 // What a call launches and how large its workspaces are is decided in spira_plan.h (make_plan: pure arithmetic, swept on the CPU under sanitizers);
 // here render_impl<T> validates, plans, sizes the workspaces from the plan and calls the organisation's enqueue_* function, and verify_path_args
 // checks every k_path launch against the buffers actually allocated.
+// Every entry point that enqueues on a context runs inside a Session: open (context, lock, stream, ordered after the previous call's end) ... close
+// (launch errors, the end event, a host caller's wait); render and adaptive render share prepare_path_call, FrameOut and begin/end_counters.  A launch
+// that the device refuses its LDS for is a return code (launch_lds) which the launch helpers and enqueue_* functions hand up at the first refusal.
 #include <hip/hip_runtime.h>
 #include <sys/mman.h>
 #include <rccl/rccl.h>      // types and prototypes only: librccl is opened at run time (dlopen), never linked
@@ -69,14 +72,13 @@ int denoise_impl_f32(const float *color, const float *variance, const float *alb
                      float *out_hdr, float *out_img, bool on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
-void launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
+int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
 }
 
 namespace spira_host {
 
 inline thread_local std::string tl_err;
 inline thread_local int tl_device = 0;
-inline thread_local hipError_t tl_lds_optin = hipSuccess;      // a refused LDS opt-in of this thread's call (launch_lds / lds_optin_failed), whichever unit launched
 
 inline int fail(int code, const std::string &msg) { tl_err = msg; return code; }
 
@@ -401,33 +403,29 @@ int scene_upload(SceneStore &s, hipStream_t st, hipEvent_t prev_done, const T *s
 }
 
 // Launch with a dynamic LDS block; above 64 KB the function has to be told first (up to the CU's 160 KB).
-// A refused opt-in is remembered (thread-local) and turned into SPIRA_E_LIMIT by lds_optin_failed() before the call returns.
+// A refused opt-in launches nothing and is the call's error (SPIRA_E_LIMIT): every launch helper and enqueue function hands it up at once.
 template <class K, class... Args>
-void launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+int launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { tl_lds_optin = e; return; }          // do not launch a kernel that cannot get its LDS
+        if (e != hipSuccess)          // do not launch a kernel that cannot get its LDS
+            return fail(SPIRA_E_LIMIT, std::string("the device refused the kernel's dynamic LDS size (hipFuncSetAttribute): ") + hipGetErrorString(e));
     }
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
-}
-int lds_optin_failed() {
-    if (tl_lds_optin == hipSuccess) return 0;
-    const hipError_t e = tl_lds_optin;
-    tl_lds_optin = hipSuccess;
-    return fail(SPIRA_E_LIMIT, std::string("the device refused the kernel's dynamic LDS size (hipFuncSetAttribute): ") + hipGetErrorString(e));
+    return 0;
 }
 
 template <class T, bool FIRST, bool BVH>
-void launch_bounce_r(int R, dim3 grid, size_t lds, hipStream_t st, const spira::BounceArgs<T> &a) {
+int launch_bounce_r(int R, dim3 grid, size_t lds, hipStream_t st, const spira::BounceArgs<T> &a) {
     switch (R) {
-    case 2: launch_lds(spira::k_bounce<T, FIRST, 2, BVH>, grid, dim3(spira::kBlock), lds, st, a); break;
-    default: launch_lds(spira::k_bounce<T, FIRST, 1, BVH>, grid, dim3(spira::kBlock), lds, st, a); break;
+    case 2: return launch_lds(spira::k_bounce<T, FIRST, 2, BVH>, grid, dim3(spira::kBlock), lds, st, a);
+    default: return launch_lds(spira::k_bounce<T, FIRST, 1, BVH>, grid, dim3(spira::kBlock), lds, st, a);
     }
 }
 template <class T, bool FIRST>
-void launch_bounce(int R, dim3 grid, size_t lds, hipStream_t st, const spira::BounceArgs<T> &a) {
-    if (a.scene.n_bvh_tris) launch_bounce_r<T, FIRST, true>(R, grid, lds, st, a);
-    else launch_bounce_r<T, FIRST, false>(R, grid, lds, st, a);
+int launch_bounce(int R, dim3 grid, size_t lds, hipStream_t st, const spira::BounceArgs<T> &a) {
+    if (a.scene.n_bvh_tris) return launch_bounce_r<T, FIRST, true>(R, grid, lds, st, a);
+    return launch_bounce_r<T, FIRST, false>(R, grid, lds, st, a);
 }
 
 // k_path.  `spec`: the speculative-division instantiation first (PathArgs::redo = its per-wave report), then the exact one over the
@@ -443,28 +441,26 @@ int launch_path_mode(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathAr
     if (ext) {           // extension instantiations (R = 2 only); like the default kernels, without the LDS triangle scan where the scene has none
         if (spec) {
             a.redo_only = spec == 2 ? 2 : 0;          // (2: every wave will be rendered again, whatever it reports)
-            if (tri) launch_lds(spira::k_path<T, 2, BVH, true, true, MODE, true>, grid, blk, lds, st, a);
-            else launch_lds(spira::k_path<T, 2, BVH, true, true, MODE, false>, grid, blk, lds, st, a);
+            if (int rc = tri ? launch_lds(spira::k_path<T, 2, BVH, true, true, MODE, true>, grid, blk, lds, st, a)
+                             : launch_lds(spira::k_path<T, 2, BVH, true, true, MODE, false>, grid, blk, lds, st, a)) return rc;
             if (spec == 2) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.redo, 1, (size_t)grid.x * (spira::kBlock / 64), st));
             a.redo_only = 1;
         } else { a.redo = nullptr; a.redo_only = 0; }
-        if (tri) launch_lds(spira::k_path<T, 2, BVH, true, false, MODE, true>, grid, blk, lds, st, a);
-        else launch_lds(spira::k_path<T, 2, BVH, true, false, MODE, false>, grid, blk, lds, st, a);
+        return tri ? launch_lds(spira::k_path<T, 2, BVH, true, false, MODE, true>, grid, blk, lds, st, a)
+                   : launch_lds(spira::k_path<T, 2, BVH, true, false, MODE, false>, grid, blk, lds, st, a);
     } else if (R == 2) {
         if (spec) {
             a.redo_only = spec == 2 ? 2 : 0;
-            if (tri) launch_lds(spira::k_path<T, 2, BVH, false, true, MODE, true>, grid, blk, lds, st, a);
-            else launch_lds(spira::k_path<T, 2, BVH, false, true, MODE, false>, grid, blk, lds, st, a);
+            if (int rc = tri ? launch_lds(spira::k_path<T, 2, BVH, false, true, MODE, true>, grid, blk, lds, st, a)
+                             : launch_lds(spira::k_path<T, 2, BVH, false, true, MODE, false>, grid, blk, lds, st, a)) return rc;
             if (spec == 2) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.redo, 1, (size_t)grid.x * (spira::kBlock / 64), st));
             a.redo_only = 1;
         } else { a.redo = nullptr; a.redo_only = 0; }
-        if (tri) launch_lds(spira::k_path<T, 2, BVH, false, false, MODE, true>, grid, blk, lds, st, a);
-        else launch_lds(spira::k_path<T, 2, BVH, false, false, MODE, false>, grid, blk, lds, st, a);
-    } else {
-        a.redo = nullptr; a.redo_only = 0;
-        launch_lds(spira::k_path<T, 1, BVH, false, false, MODE>, grid, blk, lds, st, a);
+        return tri ? launch_lds(spira::k_path<T, 2, BVH, false, false, MODE, true>, grid, blk, lds, st, a)
+                   : launch_lds(spira::k_path<T, 2, BVH, false, false, MODE, false>, grid, blk, lds, st, a);
     }
-    return 0;
+    a.redo = nullptr; a.redo_only = 0;
+    return launch_lds(spira::k_path<T, 1, BVH, false, false, MODE>, grid, blk, lds, st, a);
 }
 template <class T>
 int launch_path(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<T> &a, int spec) {
@@ -482,25 +478,25 @@ int launch_path(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathA
 // the second launch of a mesh pass (PathArgs::mesh_mode 2): the exact instantiation — its waves add to radiance the first launch
 // already stored, so they could not be rendered again, and its divisions are a small share of the frame's
 template <class T>
-void launch_path_resume(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathArgs<T> a) {
+int launch_path_resume(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathArgs<T> a) {
     const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
     const dim3 blk(spira::kBlock);
     a.redo = nullptr; a.redo_only = 0;
-    if (ext && a.scene.n_triangles) launch_lds(spira::k_path<T, 2, true, true, false, 2, true>, grid, blk, lds, st, a);
-    else if (ext) launch_lds(spira::k_path<T, 2, true, true, false, 2, false>, grid, blk, lds, st, a);
-    else if (R == 2 && a.scene.n_triangles) launch_lds(spira::k_path<T, 2, true, false, false, 2, true>, grid, blk, lds, st, a);
-    else if (R == 2) launch_lds(spira::k_path<T, 2, true, false, false, 2, false>, grid, blk, lds, st, a);
-    else launch_lds(spira::k_path<T, 1, true, false, false, 2>, grid, blk, lds, st, a);
+    if (ext && a.scene.n_triangles) return launch_lds(spira::k_path<T, 2, true, true, false, 2, true>, grid, blk, lds, st, a);
+    if (ext) return launch_lds(spira::k_path<T, 2, true, true, false, 2, false>, grid, blk, lds, st, a);
+    if (R == 2 && a.scene.n_triangles) return launch_lds(spira::k_path<T, 2, true, false, false, 2, true>, grid, blk, lds, st, a);
+    if (R == 2) return launch_lds(spira::k_path<T, 2, true, false, false, 2, false>, grid, blk, lds, st, a);
+    return launch_lds(spira::k_path<T, 1, true, false, false, 2>, grid, blk, lds, st, a);
 }
 
 // launch_path_resume<T> of whichever translation unit holds the mesh kernels of T
 template <class T>
-void launch_path_resume_entry(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<T> &a) {
+int launch_path_resume_entry(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<T> &a) {
 #ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 8) spira_tu::launch_path_resume_f64(R, grid, lds, st, a);
+    if constexpr (sizeof(T) == 8) return spira_tu::launch_path_resume_f64(R, grid, lds, st, a);
     else
 #endif
-        launch_path_resume<T>(R, grid, lds, st, a);
+        return launch_path_resume<T>(R, grid, lds, st, a);
 }
 
 int profile_events(Ctx &c, size_t need) {
@@ -523,6 +519,30 @@ int mark_done(Ctx &c, hipStream_t st) {
     c.have_done = true;
     return 0;
 }
+
+// One call on the calling thread's device context.  open: the context exists, its lock is held until the Session dies, `st` is the caller's stream
+// (device outputs) or the context's own, and `st` already waits for the end of the last call that used the workspaces — whatever is enqueued on it
+// from here on may use them.  close: after the call's LAST enqueue on `st` (a host caller's copies out included): launch errors, the event the next
+// call will wait for, and for a host caller the wait for its outputs.  An entry point validates its arguments, opens, sizes what it needs, enqueues, closes.
+struct Session {
+    Ctx *cp = nullptr;
+    std::unique_lock<std::recursive_mutex> lock;
+    hipStream_t st = nullptr;
+    bool host_out = false;
+    static int open(Session &s, bool out_on_device, void *user_stream) {
+        if (int rc = get_ctx(&s.cp)) return rc;
+        s.lock = std::unique_lock<std::recursive_mutex>(s.cp->mu);
+        s.host_out = !out_on_device;
+        s.st = out_on_device ? (hipStream_t)user_stream : s.cp->stream;
+        return order_after_previous(*s.cp, s.st);
+    }
+    int close() {
+        HIP_TRY(hipGetLastError());
+        if (int rc = mark_done(*cp, st)) return rc;
+        if (host_out) HIP_TRY(hipStreamSynchronize(st));
+        return 0;
+    }
+};
 
 // The caller's output buffer is usually fresh from the allocator (`render` of either reference surface returns a new array): its pages do not exist yet,
 // and the first touch of 12 000 of them inside the copy costs 2-3 ms.  The threads that will move the frame in ask the kernel for the pages (writable,
@@ -793,9 +813,8 @@ int enqueue_hybrid(Call<T> &k) {
     for (uint32_t smp = 1; smp <= p->spp; ++smp)
         for (uint32_t ph = 0; ph <= p->max_depth; ++ph) {
             ha.sample = smp; ha.phase = ph;
-            launch_lds(spira::k_hybrid<T>, dim3(hblocks), k.block(), k.lds, k.st, ha);
+            if (int rc = launch_lds(spira::k_hybrid<T>, dim3(hblocks), k.block(), k.lds, k.st, ha)) return rc;
         }
-    if (int rc = lds_optin_failed()) return rc;
     k.launches += 1 + (uint64_t)p->spp * (p->max_depth + 1);
     return 0;
 }
@@ -819,13 +838,12 @@ int enqueue_metal_wavefront(Call<T> &k) {
     if (k.spec) {                          // speculative division as in k_path
         ma.redo = k.redo();
         ma.redo_only = k.spec == 2 ? 2 : 0;
-        launch_lds(spira::k_path_metal<T, 2, true>, grid, k.block(), k.lds, k.st, ma);
+        if (int rc = launch_lds(spira::k_path_metal<T, 2, true>, grid, k.block(), k.lds, k.st, ma)) return rc;
         ma.redo_only = 1;
         ++k.launches;
     }
-    if (plan.R == 2) launch_lds(spira::k_path_metal<T, 2, false>, grid, k.block(), k.lds, k.st, ma);
-    else launch_lds(spira::k_path_metal<T, 1, false>, grid, k.block(), k.lds, k.st, ma);
-    if (int rc = lds_optin_failed()) return rc;
+    if (int rc = plan.R == 2 ? launch_lds(spira::k_path_metal<T, 2, false>, grid, k.block(), k.lds, k.st, ma)
+                             : launch_lds(spira::k_path_metal<T, 1, false>, grid, k.block(), k.lds, k.st, ma)) return rc;
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
     hipLaunchKernelGGL(spira::k_fold_stats, dim3(1), dim3(64), 0, k.st, (const uint32_t *)c.blkstats.p, plan.G_metal * plan.wpb, k.stats());
     k.launches += 2;
@@ -840,10 +858,10 @@ int enqueue_metal(Call<T> &k) {
     const dim3 grid(k.plan.blocks(k.plan.tile_pixels));
     k.a.pass = 0; k.a.n_first = (uint32_t)k.plan.tile_pixels;
     if (k.spec) {
-        launch_lds(spira::k_variant_metal<T, true>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), k.spec == 2 ? 2 : 0);
-        launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), 1);
-    } else
-        launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), (uint32_t *)nullptr, 0);
+        if (int rc = launch_lds(spira::k_variant_metal<T, true>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), k.spec == 2 ? 2 : 0)) return rc;
+        if (int rc = launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), k.redo(), 1)) return rc;
+    } else if (int rc = launch_lds(spira::k_variant_metal<T, false>, grid, k.block(), k.lds, k.st, k.a, k.accum(), k.d_rng, k.resume(), (uint32_t *)nullptr, 0))
+        return rc;
     k.launches += k.spec ? 2 : 1;
     return 0;
 }
@@ -853,10 +871,10 @@ template <class T>
 int enqueue_cpu_pass(Call<T> &k) {
     const dim3 grid(k.plan.blocks(k.a.n_first));
     if (k.spec) {                          // speculative division as in k_path / k_variant_metal
-        launch_lds(spira::k_variant_cpu<T, true>, grid, k.block(), k.lds, k.st, k.a, k.redo(), k.spec == 2 ? 2 : 0);
-        launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, k.redo(), 1);
-    } else
-        launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, (uint32_t *)nullptr, 0);
+        if (int rc = launch_lds(spira::k_variant_cpu<T, true>, grid, k.block(), k.lds, k.st, k.a, k.redo(), k.spec == 2 ? 2 : 0)) return rc;
+        if (int rc = launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, k.redo(), 1)) return rc;
+    } else if (int rc = launch_lds(spira::k_variant_cpu<T, false>, grid, k.block(), k.lds, k.st, k.a, (uint32_t *)nullptr, 0))
+        return rc;
     k.launches += k.spec ? 2 : 1;
     return 0;
 }
@@ -865,10 +883,11 @@ template <class T>
 int enqueue_mega_pass(Call<T> &k) {
     const dim3 grid(k.plan.blocks(k.a.n_first));
     const bool ext = (k.p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
-    if (k.a.scene.n_bvh_tris) { if (ext) launch_lds(spira::k_mega<T, true, true>, grid, k.block(), k.lds, k.st, k.a); else launch_lds(spira::k_mega<T, true, false>, grid, k.block(), k.lds, k.st, k.a); }
-    else { if (ext) launch_lds(spira::k_mega<T, false, true>, grid, k.block(), k.lds, k.st, k.a); else launch_lds(spira::k_mega<T, false, false>, grid, k.block(), k.lds, k.st, k.a); }
+    int rc;
+    if (k.a.scene.n_bvh_tris) rc = ext ? launch_lds(spira::k_mega<T, true, true>, grid, k.block(), k.lds, k.st, k.a) : launch_lds(spira::k_mega<T, true, false>, grid, k.block(), k.lds, k.st, k.a);
+    else rc = ext ? launch_lds(spira::k_mega<T, false, true>, grid, k.block(), k.lds, k.st, k.a) : launch_lds(spira::k_mega<T, false, false>, grid, k.block(), k.lds, k.st, k.a);
     ++k.launches;
-    return 0;
+    return rc;
 }
 
 // k_path, one launch: every wave walks all max_depth stages on its own region of the hit queues (mesh scenes: a parking launch + a fat-wave launch)
@@ -912,8 +931,7 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
     }
     if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
-    if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec)) return rc;
-    if (int rc = lds_optin_failed()) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
+    if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec)) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
     k.launches += k.spec ? 2 : 1;      // the speculative launch and its exact follow-up
     if (pa.mesh_mode == 1) {           // second launch: nw / k fat waves
         if (c.ev_mid.size() <= c.ev_mid_used) {
@@ -926,8 +944,7 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
         spira::PathArgs<T> pb = pa;
         pb.mesh_mode = 2; pb.n_first = 0;
         const uint32_t nwb = pa.resume_nw / pa.resume_k;
-        launch_path_resume_entry<T>((int)plan.R, dim3((nwb + plan.wpb - 1) / plan.wpb), lds_a, k.st, pb);
-        if (int rc = lds_optin_failed()) return rc;
+        if (int rc = launch_path_resume_entry<T>((int)plan.R, dim3((nwb + plan.wpb - 1) / plan.wpb), lds_a, k.st, pb)) return rc;
         ++k.launches;
     }
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
@@ -953,9 +970,7 @@ int enqueue_bounce_pass(Call<T> &k, uint32_t *stat_rows) {
         k.a.blk_stats = (uint32_t *)c.blkstats.p + (size_t)b * nw * 4;
         if (k.profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
         const size_t lds_b = k.lds + (size_t)plan.wpb * plan.sub * sizeof(P4);   // + one work list per wave (one slot per ray of a sub-chunk)
-        if (b == 0) launch_bounce<T, true>((int)plan.R, dim3(g.G), lds_b, k.st, k.a);
-        else launch_bounce<T, false>((int)plan.R, dim3(g.G), lds_b, k.st, k.a);
-        if (int rc = lds_optin_failed()) return rc;
+        if (int rc = b == 0 ? launch_bounce<T, true>((int)plan.R, dim3(g.G), lds_b, k.st, k.a) : launch_bounce<T, false>((int)plan.R, dim3(g.G), lds_b, k.st, k.a)) return rc;
         if (k.profile) HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
         ++k.launches;
     }
@@ -985,7 +1000,67 @@ void enqueue_finalize(Call<T> &k, T *d_hdr, T *d_img) {
     ++k.launches;
 }
 
-// Validation -> plan -> workspaces -> scene -> prologue (events, a progressive call's running sums) -> the organisation's launches -> epilogue.
+// What render and adaptive render share of a k_path call between the workspaces and the first launch: the scene, the constants and what
+// every organisation's arguments start from (k.p: the parameters the plan was made from).
+template <class T>
+int prepare_path_call(Call<T> &k, const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, uint32_t rows, bool reuse_scene) {
+    Ctx &c = k.c;
+    if (int rc = acquire_scene<T>(c, k.st, h, spheres5, materials8, triangles10, k.p, k.a.scene, reuse_scene)) return rc;
+    if (int rc = attach_spd<T>(c, k.st, k.p, k.a.scene)) return rc;
+    k.spec = k.plan.spec((h ? h->store.moderate : c.scene.moderate) && spira::camera_scale_moderate<T>(camera12));
+    fill_const<T>(k.a.rc, camera12, k.p, rows, k.plan.slots);
+    if (!fastdiv_selfcheck(k.a.rc.tile_pixels, (uint32_t)k.plan.batch) || !fastdiv_selfcheck(k.a.rc.width, k.a.rc.tile_pixels) ||
+        !fastdiv_selfcheck(k.a.rc.stripe_h ? k.a.rc.stripe_h : 1, rows))
+        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+    k.a.L = (spira::Pack3<T> *)c.L.p;
+    k.a.stats = k.stats();
+    k.lds = spira::scene_lds_bytes<T>(k.a.scene.n_spheres, k.a.scene.n_materials, k.a.scene.n_triangles);
+    return 0;
+}
+
+// Where the kernels write a call's two frames: the caller's device memory, or the two halves of out_tmp, which copy() then hands to the host caller.
+template <class T> struct FrameOut {
+    T *hdr, *img;
+    FrameOut(const Session &s, T *out_hdr, T *out_img, uint64_t tile_pixels) : hdr(out_hdr), img(out_img) {
+        if (!s.host_out) return;
+        hdr = out_hdr ? (T *)s.cp->out_tmp.p : nullptr;
+        img = out_img ? (T *)((char *)s.cp->out_tmp.p + 3 * tile_pixels * sizeof(T)) : nullptr;
+    }
+    int copy(const Session &s, T *out_hdr, T *out_img, uint64_t tile_pixels) const {
+        if (!s.host_out) return 0;
+        void *const dst[2] = {out_hdr, out_img};
+        const void *const src[2] = {hdr, img};
+        return copy_out(*s.cp, s.st, dst, src, 3 * tile_pixels * sizeof(T));
+    }
+};
+
+// The bracket spira_get_counters reads: device counters and event brackets start from nothing (cont, a later slab: they go on from slab 0's) ...
+int begin_counters(Session &s, bool cont) {
+    Ctx &c = *s.cp;
+    if (cont) return 0;
+    c.ev_used = 0;
+    c.ev_mid_used = 0;
+    HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), s.st));
+    HIP_TRY(hipEventRecord(c.ev_start, s.st));
+    return 0;
+}
+// ... and after the call's last kernel the device counters are read back and the host's share (`delta`) becomes, or with cont adds to, the context's
+int end_counters(Session &s, const spira_counters &delta, bool cont) {
+    Ctx &c = *s.cp;
+    HIP_TRY(hipEventRecord(c.ev_stop, s.st));
+    HIP_TRY(hipMemcpyAsync(c.h_stats, c.stats.p, sizeof(spira::Stats), hipMemcpyDeviceToHost, s.st));
+    if (!cont) c.last = spira_counters{};
+    c.last.samples += delta.samples;
+    c.last.passes += delta.passes;
+    c.last.launches += delta.launches;
+    c.last.bounce_launches += delta.bounce_launches;
+    c.last_valid = true;
+    c.last_pending = true;
+    c.last_stream = s.st;
+    return 0;
+}
+
+// Validation -> session -> plan -> workspaces -> scene -> prologue (events, a progressive call's running sums) -> the organisation's launches -> epilogue.
 // (The kernels of a translation unit come out in the order in which their launches are first named from here, enqueue function by enqueue function:
 // keep that order, and every launch but k_load_accum's inside one of them, and the code object does not change when this function does.)
 template <class T>
@@ -997,17 +1072,14 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     using P4 = spira::Pack4<T>;
     uint32_t rows = 0;
     const bool cont = slab && slab->index > 0;      // a later slab of a host-output frame: continues slab 0's call (SlabCtl)
-    tl_lds_optin = hipSuccess;           // (a flag an earlier call of this thread left behind by returning early must not fail this one)
     Lap lap("render");
     if (slab) rows = p->rows;            // (render_host_slabs validated the frame its slabs are cut from)
     else if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, progressive, sample0, rng_states, &rows)) return rc;
     lap("validate");
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    hipStream_t st = out_on_device ? (hipStream_t)user_stream : c.stream;
-    if (int rc = order_after_previous(c, st)) return rc;
+    Session s;
+    if (int rc = Session::open(s, out_on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
     lap("context");
 
     spira::Plan plan;
@@ -1019,36 +1091,19 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
 
     Call<T> k{c, st, p, plan};
     const uint64_t tile_pixels = plan.tile_pixels;
-    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, p, k.a.scene, cont)) return rc;
-    if (int rc = attach_spd<T>(c, st, p, k.a.scene)) return rc;
+    if (int rc = prepare_path_call<T>(k, h, spheres5, materials8, triangles10, camera12, rows, cont)) return rc;
     lap("scene");
-    k.spec = plan.spec((h ? h->store.moderate : c.scene.moderate) && spira::camera_scale_moderate<T>(camera12));
-    fill_const<T>(k.a.rc, camera12, p, rows, plan.slots);
-    if (!fastdiv_selfcheck(k.a.rc.tile_pixels, (uint32_t)plan.batch) || !fastdiv_selfcheck(k.a.rc.width, k.a.rc.tile_pixels) ||
-        !fastdiv_selfcheck(k.a.rc.stripe_h ? k.a.rc.stripe_h : 1, rows))
-        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-    k.a.L = (spira::Pack3<T> *)c.L.p;
-    k.a.stats = k.stats();
-    k.lds = spira::scene_lds_bytes<T>(k.a.scene.n_spheres, k.a.scene.n_materials, k.a.scene.n_triangles);
     k.progressive = progressive; k.sample0 = sample0;
     // k_path launches are always bracketed (2 events per pass); the per-bounce ones on request
     k.profile = plan.org == Org::Path || (plan.org == Org::Bounce && (p->flags & SPIRA_FLAG_PROFILE) != 0);
 
-    T *d_hdr = out_hdr, *d_img = out_img;
-    if (!out_on_device) {
-        d_hdr = out_hdr ? (T *)c.out_tmp.p : nullptr;
-        d_img = out_img ? (T *)((char *)c.out_tmp.p + 3 * tile_pixels * sizeof(T)) : nullptr;
-    }
+    const FrameOut<T> out(s, out_hdr, out_img, tile_pixels);
+    T *const d_hdr = out.hdr, *const d_img = out.img;
     if (k.profile) {
         const size_t n_prof = (size_t)plan.n_pass * (plan.org == Org::Path ? 1 : p->max_depth) * 2;
         if (int rc = profile_events(c, (cont ? c.ev_used : 0) + n_prof)) return rc;
     }
-    if (!cont) {                         // (a later slab adds its brackets and device counters to slab 0's)
-        c.ev_used = 0;
-        c.ev_mid_used = 0;
-        HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), st));
-        HIP_TRY(hipEventRecord(c.ev_start, st));
-    }
+    if (int rc = begin_counters(s, cont)) return rc;      // (a later slab adds its brackets and device counters to slab 0's)
 
     // progressive accumulation: the caller's running sums (and, METAL, LCG states) seed the accumulator
     k.a.rc.sample0 = progressive ? sample0 : 0;
@@ -1080,31 +1135,19 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     enqueue_finalize(k, d_hdr, d_img);
     if (progressive && rng_states && !out_on_device)
         HIP_TRY(hipMemcpyAsync(rng_states, k.d_rng, tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (int rc2 = lds_optin_failed()) return rc2;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.ev_stop, st));
-    HIP_TRY(hipMemcpyAsync(c.h_stats, c.stats.p, sizeof(spira::Stats), hipMemcpyDeviceToHost, st));
+    const bool bounce_kernels = plan.org == Org::Path || plan.org == Org::Bounce;
+    spira_counters delta{};
+    delta.samples = (uint64_t)p->spp * tile_pixels;
+    delta.passes = p->max_depth ? plan.n_pass : 0;
+    delta.launches = k.launches;
+    delta.bounce_launches = k.metal_launches ? k.metal_launches : !bounce_kernels ? 0 : (uint64_t)plan.n_pass * (plan.org == Org::Path ? 1 : p->max_depth);
+    if (int rc2 = end_counters(s, delta, cont)) return rc2;
     lap("enqueue");
 
-    const bool bounce_kernels = plan.org == Org::Path || plan.org == Org::Bounce;
-    if (!cont) c.last = spira_counters{};
-    c.last.samples += (uint64_t)p->spp * tile_pixels;
-    c.last.passes += p->max_depth ? plan.n_pass : 0;
-    c.last.launches += k.launches;
-    c.last.bounce_launches += k.metal_launches ? k.metal_launches : !bounce_kernels ? 0 : (uint64_t)plan.n_pass * (plan.org == Org::Path ? 1 : p->max_depth);
-    c.last_valid = true;
-    c.last_pending = true;
-    c.last_stream = st;
-
-    if (!out_on_device) {
-        void *const dst[2] = {out_hdr, out_img};
-        const void *const src[2] = {d_hdr, d_img};
-        if (int rc2 = copy_out(c, st, dst, src, 3 * tile_pixels * sizeof(T))) return rc2;
-    }
-    if (int rc2 = mark_done(c, st)) return rc2;
-    if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
+    if (int rc2 = out.copy(s, out_hdr, out_img, tile_pixels)) return rc2;
+    rc = s.close();
     lap("copy_out+sync");
-    return 0;
+    return rc;
 }
 
 // render_impl<T> of whichever translation unit holds the kernels of T
@@ -1147,14 +1190,12 @@ int render_host_slabs(const spira_scene *h, const T *spheres5, const T *material
     // the frame will be rendered as slabs: the whole call is validated here, once, before anything is sized or allocated (its slabs skip it: SlabCtl)
     uint32_t rows_checked = 0;
     if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, false, 0, nullptr, &rows_checked)) return rc;
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
+    Session ss;                          // (on the context's stream; out_tmp may still be read by the previous call.  The ending is this function's own: two streams)
+    if (int rc = Session::open(ss, false, nullptr)) return rc;
+    Ctx &c = *ss.cp;
     if (!stage_reserve(c, total)) return 0;
     if (!c.copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c.copy_stream, hipStreamNonBlocking));
     if (!c.ev_slab) HIP_TRY(hipEventCreateWithFlags(&c.ev_slab, hipEventDisableTiming));
-    if (int rc = order_after_previous(c, c.stream)) return rc;                       // (out_tmp may still be read by the previous call)
     if (int rc = c.out_tmp.ensure(2 * plane3)) return rc;
     *done = true;
     Lap lap("host slabs");
@@ -1216,8 +1257,7 @@ int enqueue_refine(hipStream_t st, const spira::AdaptiveRound &g, size_t lds, co
     if (g.ppw == 0 || g.chunk == 0 || (uint64_t)g.ppw * g.chunk > spira::kAdaptiveItems || g.ppw > 64 || g.waves * g.ppw < ra.n_active ||
         (uint64_t)g.grid * spira::kAdaptiveWpb < g.waves || spira::kAdaptiveWpb != spira::kBlock / 64)
         return fail(SPIRA_E_LIMIT, "internal: a refinement launch does not cover its list");
-    launch_lds(spira::k_refine<T, BVH>, dim3(g.grid), dim3(spira::kBlock), lds, st, ra);
-    return lds_optin_failed();
+    return launch_lds(spira::k_refine<T, BVH>, dim3(g.grid), dim3(spira::kBlock), lds, st, ra);
 }
 
 template <class T>
@@ -1226,7 +1266,6 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
     using spira::Org;
     using P4 = spira::Pack4<T>;
     uint32_t rows = 0;
-    tl_lds_optin = hipSuccess;
     if (!ad) return fail(SPIRA_E_INVALID, "adaptive is NULL");
     // (any one of the four outputs will do: validate_call asks for one of its two)
     const T *some_out = out_hdr ? out_hdr : out_img ? out_img : (out_spp || out_q) ? camera12 : nullptr;
@@ -1240,12 +1279,10 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
     ain.tile_pixels = (uint64_t)rows * p->width; ain.prec = sizeof(T); ain.pack3 = sizeof(spira::Pack3<T>);
     if (int rc = spira::adaptive_check(ain.min_spp, ain.batch_spp, ain.spp, ain.tolerance, ain.floor, &msg)) return fail(rc, msg);
     if (p->max_depth < 1) return fail(SPIRA_E_INVALID, "max_depth must be >= 1");
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    hipStream_t st = out_on_device ? (hipStream_t)user_stream : c.stream;
-    if (int rc = order_after_previous(c, st)) return rc;
+    Session s;
+    if (int rc = Session::open(s, out_on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
 
     ain.num_cus = (uint32_t)c.num_cus;
     spira::AdaptivePlan ap;
@@ -1267,28 +1304,12 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
 
     Call<T> k{c, st, &p0, plan};
     const uint64_t tile_pixels = plan.tile_pixels;
-    if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, &p0, k.a.scene)) return rc;
-    if (int rc = attach_spd<T>(c, st, &p0, k.a.scene)) return rc;
-    k.spec = plan.spec((h ? h->store.moderate : c.scene.moderate) && spira::camera_scale_moderate<T>(camera12));
-    fill_const<T>(k.a.rc, camera12, &p0, rows, plan.slots);
-    if (!fastdiv_selfcheck(k.a.rc.tile_pixels, (uint32_t)plan.batch) || !fastdiv_selfcheck(k.a.rc.width, k.a.rc.tile_pixels) ||
-        !fastdiv_selfcheck(k.a.rc.stripe_h ? k.a.rc.stripe_h : 1, rows))
-        return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-    k.a.L = (spira::Pack3<T> *)c.L.p;
-    k.a.stats = k.stats();
-    k.lds = spira::scene_lds_bytes<T>(k.a.scene.n_spheres, k.a.scene.n_materials, k.a.scene.n_triangles);
+    if (int rc = prepare_path_call<T>(k, h, spheres5, materials8, triangles10, camera12, rows, false)) return rc;
     k.profile = true;
-    T *d_hdr = out_hdr, *d_img = out_img;
-    if (!out_on_device) {
-        d_hdr = out_hdr ? (T *)c.out_tmp.p : nullptr;
-        d_img = out_img ? (T *)((char *)c.out_tmp.p + 3 * tile_pixels * sizeof(T)) : nullptr;
-    }
+    const FrameOut<T> out(s, out_hdr, out_img, tile_pixels);
     if (int rc = profile_events(c, (size_t)plan.n_pass * 2)) return rc;
-    c.ev_used = 0;
-    c.ev_mid_used = 0;
-    HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), st));
     HIP_TRY(hipMemsetAsync(c.ad_count.p, 0, ap.count_bytes, st));
-    HIP_TRY(hipEventRecord(c.ev_start, st));
+    if (int rc = begin_counters(s, false)) return rc;
 
     spira::AdaptiveArgs<T> aa{};
     aa.accum = k.accum(); aa.Q = (T *)c.ad_q.p; aa.npix = (uint32_t *)c.ad_n.p;
@@ -1328,32 +1349,21 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
         cur ^= 1;
     }
     hipLaunchKernelGGL((spira::k_finalize_adaptive<T>), dim3(plan.blocks(tile_pixels)), k.block(), 0, st, (const P4 *)k.accum(), (const uint32_t *)c.ad_n.p, (const T *)c.ad_q.p,
-                       (uint32_t)tile_pixels, p->flags & SPIRA_POST_MASK, d_hdr, d_img, out_on_device ? out_spp : (uint32_t *)nullptr, out_on_device ? out_q : (T *)nullptr);
+                       (uint32_t)tile_pixels, p->flags & SPIRA_POST_MASK, out.hdr, out.img, out_on_device ? out_spp : (uint32_t *)nullptr, out_on_device ? out_q : (T *)nullptr);
     ++k.launches;
-    if (int rc = lds_optin_failed()) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c.ev_stop, st));
-    HIP_TRY(hipMemcpyAsync(c.h_stats, c.stats.p, sizeof(spira::Stats), hipMemcpyDeviceToHost, st));
+    spira_counters delta{};
+    delta.samples = samples;
+    delta.passes = plan.n_pass + rounds;
+    delta.launches = k.launches;
+    delta.bounce_launches = plan.n_pass;
+    if (int rc = end_counters(s, delta, false)) return rc;
 
-    c.last = spira_counters{};
-    c.last.samples = samples;
-    c.last.passes = plan.n_pass + rounds;
-    c.last.launches = k.launches;
-    c.last.bounce_launches = plan.n_pass;
-    c.last_valid = true;
-    c.last_pending = true;
-    c.last_stream = st;
-
+    if (int rc = out.copy(s, out_hdr, out_img, tile_pixels)) return rc;
     if (!out_on_device) {
-        void *const dst[2] = {out_hdr, out_img};
-        const void *const src[2] = {d_hdr, d_img};
-        if (int rc = copy_out(c, st, dst, src, 3 * tile_pixels * sizeof(T))) return rc;
         if (out_spp) HIP_TRY(hipMemcpyAsync(out_spp, c.ad_n.p, tile_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (out_q) HIP_TRY(hipMemcpyAsync(out_q, c.ad_q.p, tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
     }
-    if (int rc = mark_done(c, st)) return rc;
-    if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return s.close();
 }
 
 // render_adaptive_impl<T> of whichever translation unit holds the kernels of T
@@ -1383,17 +1393,14 @@ template <class T>
 int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
                   T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
     uint32_t rows = 0;
-    tl_lds_optin = hipSuccess;
     const T *some_out = out_albedo ? out_albedo : out_normal ? out_normal : out_depth;
     if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, some_out, (const T *)nullptr, false, 0, nullptr, &rows)) return rc;
     const char *msg = nullptr;
     if (int rc = spira::features_check(p->flags, some_out != nullptr, &msg)) return fail(rc, msg);
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    hipStream_t st = out_on_device ? (hipStream_t)user_stream : c.stream;
-    if (int rc = order_after_previous(c, st)) return rc;
+    Session s;
+    if (int rc = Session::open(s, out_on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
 
     spira::FeatureArgs<T> fa{};
     if (int rc = acquire_scene<T>(c, st, h, spheres5, materials8, triangles10, p, fa.scene)) return rc;
@@ -1412,19 +1419,15 @@ int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, 
     }
     const size_t lds = spira::scene_lds_bytes<T>(fa.scene.n_spheres, fa.scene.n_materials, fa.scene.n_triangles);
     const dim3 grid(spira::features_grid(tile_pixels, spira::kBlock, (uint32_t)c.num_cus)), block(spira::kBlock);
-    if (fa.scene.n_bvh_tris) launch_lds(spira::k_features<T, true, false>, grid, block, lds, st, fa);
-    else if (fa.scene.n_triangles) launch_lds(spira::k_features<T, false, true>, grid, block, lds, st, fa);
-    else launch_lds(spira::k_features<T, false, false>, grid, block, lds, st, fa);
-    if (int rc = lds_optin_failed()) return rc;
-    HIP_TRY(hipGetLastError());
+    if (int rc = fa.scene.n_bvh_tris    ? launch_lds(spira::k_features<T, true, false>, grid, block, lds, st, fa)
+                 : fa.scene.n_triangles ? launch_lds(spira::k_features<T, false, true>, grid, block, lds, st, fa)
+                                        : launch_lds(spira::k_features<T, false, false>, grid, block, lds, st, fa)) return rc;
     if (!out_on_device) {
         if (out_albedo) HIP_TRY(hipMemcpyAsync(out_albedo, fa.albedo, 3 * tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
         if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal, fa.normal, 3 * tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
         if (out_depth) HIP_TRY(hipMemcpyAsync(out_depth, fa.depth, tile_pixels * sizeof(T), hipMemcpyDeviceToHost, st));
     }
-    if (int rc = mark_done(c, st)) return rc;
-    if (!out_on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return s.close();
 }
 
 template <class T>
@@ -1454,12 +1457,10 @@ int denoise_impl(const T *color, const T *variance, const T *albedo, const T *no
     spira::DenoisePlan dp;
     const char *msg = nullptr;
     if (int rc = spira::make_denoise_plan(in, dp, &msg)) return fail(rc, msg);
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    hipStream_t st = on_device ? (hipStream_t)user_stream : c.stream;
-    if (int rc = order_after_previous(c, st)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
     for (int i = 0; i < 2; ++i) if (int rc = c.dn_rec[i].ensure(dp.rec_bytes)) return rc;
     if (int rc = c.dn_guide.ensure(dp.guide_bytes)) return rc;
     if (int rc = c.dn_io.ensure(dp.io_bytes)) return rc;
@@ -1496,14 +1497,11 @@ int denoise_impl(const T *color, const T *variance, const T *albedo, const T *no
         if (it + 1 < dn->iterations) hipLaunchKernelGGL((spira::k_denoise_iter<T, false>), dim3(dp.grid), block, 0, st, a, dp.step(it), src);
         else hipLaunchKernelGGL((spira::k_denoise_iter<T, true>), dim3(dp.grid), block, 0, st, a, dp.step(it), src);
     }
-    HIP_TRY(hipGetLastError());
     if (!on_device) {
         if (out_hdr) HIP_TRY(hipMemcpyAsync(out_hdr, a.out_hdr, 3 * npix * sizeof(T), hipMemcpyDeviceToHost, st));
         if (out_img) HIP_TRY(hipMemcpyAsync(out_img, a.out_img, 3 * npix * sizeof(T), hipMemcpyDeviceToHost, st));
     }
-    if (int rc = mark_done(c, st)) return rc;
-    if (!on_device) HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return s.close();
 }
 
 template <class T>
@@ -1522,7 +1520,6 @@ int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, con
                uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance) {
     uint32_t rows = 0;
     if (!p) return fail(SPIRA_E_INVALID, "params is NULL");
-    tl_lds_optin = hipSuccess;
     if (int rc = validate_scene<T>(spheres5, materials8, triangles10, p->n_spheres, p->n_materials, triangles10 ? p->n_triangles : 0)) return rc;
     if (int rc = validate_params(camera12, p, triangles10 ? p->n_triangles : 0, &rows)) return rc;
     if (!n_paths || !ijs || !prims || !ts || !dirs || !radiance) return fail(SPIRA_E_INVALID, "NULL argument");
@@ -1531,12 +1528,10 @@ int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, con
     for (uint32_t k = 0; k < n_paths; ++k)
         if (ijs[3 * k] < 1 || ijs[3 * k] > p->width || ijs[3 * k + 1] < 1 || ijs[3 * k + 1] > p->height || ijs[3 * k + 2] >= p->spp)
             return fail(SPIRA_E_INVALID, "path (i, j, sample) out of range");
-    Ctx *cp = nullptr;
-    if (int rc = get_ctx(&cp)) return rc;
-    Ctx &c = *cp;
-    std::lock_guard<std::recursive_mutex> lock(c.mu);
-    hipStream_t st = c.stream;
-    if (int rc = order_after_previous(c, st)) return rc;
+    Session s;
+    if (int rc = Session::open(s, false, nullptr)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
     spira::BounceArgs<T> a{};
     if (int rc = acquire_scene<T>(c, st, (const spira_scene *)nullptr, spheres5, materials8, triangles10, p, a.scene)) return rc;
     if (int rc = attach_spd<T>(c, st, p, a.scene)) return rc;
@@ -1558,23 +1553,19 @@ int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, con
     HIP_TRY(hipMemsetAsync(d_ts, 0, b_ts + b_di, st));
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
     const uint32_t sem = p->flags & SPIRA_SEM_MASK;
-    if (sem == SPIRA_SEM_CPU) launch_lds(spira::k_trace_variant<T, 1>, dim3((n_paths + 63) / 64), dim3(64), lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
-    else if (sem == SPIRA_SEM_METAL) launch_lds(spira::k_trace_variant<T, 2>, dim3((n_paths + 63) / 64), dim3(64), lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
-    else {
-        const bool ext = (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
-        const dim3 tg((n_paths + 63) / 64), tb(64);
-        if (a.scene.n_bvh_tris) { if (ext) launch_lds(spira::k_trace<T, true, true>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra); else launch_lds(spira::k_trace<T, true, false>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra); }
-        else { if (ext) launch_lds(spira::k_trace<T, false, true>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra); else launch_lds(spira::k_trace<T, false, false>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra); }
-    }
-    if (int rc = lds_optin_failed()) return rc;
-    HIP_TRY(hipGetLastError());
+    const bool ext = (p->flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    const dim3 tg((n_paths + 63) / 64), tb(64);
+    int rc;
+    if (sem == SPIRA_SEM_CPU) rc = launch_lds(spira::k_trace_variant<T, 1>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
+    else if (sem == SPIRA_SEM_METAL) rc = launch_lds(spira::k_trace_variant<T, 2>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
+    else if (a.scene.n_bvh_tris) rc = ext ? launch_lds(spira::k_trace<T, true, true>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra) : launch_lds(spira::k_trace<T, true, false>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
+    else rc = ext ? launch_lds(spira::k_trace<T, false, true>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra) : launch_lds(spira::k_trace<T, false, false>, tg, tb, lds, st, a, d_ij, n_paths, d_pr, d_ts, d_di, d_ra);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(prims, d_pr, nseg * sizeof(int), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(ts, d_ts, nseg * sizeof(T), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(dirs, d_di, nseg * 3 * sizeof(T), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(radiance, d_ra, (size_t)n_paths * 3 * sizeof(T), hipMemcpyDeviceToHost, st));
-    if (int rc = mark_done(c, st)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
+    return s.close();
 }
 
 // Camera constructor arithmetic, host side.  Statement order of
@@ -1896,8 +1887,8 @@ int spira_tu::launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st,
     if (a.mesh_mode == 1) return launch_path_mode<double, true, 1>(R, grid, lds, st, a, spec);
     return launch_path_mode<double, true, 0>(R, grid, lds, st, a, spec);
 }
-void spira_tu::launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a) {
-    launch_path_resume<double>(R, grid, lds, st, a);
+int spira_tu::launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a) {
+    return launch_path_resume<double>(R, grid, lds, st, a);
 }
 #elif defined(SPIRA_TU_F32)
 int spira_tu::render_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
