@@ -253,6 +253,26 @@ int spira_render_multi_scene_f32(const spira_scene *scene, const float camera12[
                                  float *out_hdr, float *out_img);
 int spira_render_multi_scene_f64(const spira_scene *scene, const double camera12[12], const spira_params *params, int n_devices,
                                  double *out_hdr, double *out_img);
+/* New contents for a LIVE handle (an animated or deforming mesh): the arrays are replaced and the mesh's tree is REFITTED on the device — topology, slot
+ * order and frame kept, every box recomputed bottom-up from the new vertices — instead of rebuilt on the host.  The tree only prunes, so a render after an
+ * update is bit for bit the render of a fresh handle on the same arrays; what a refit costs is traversal time as the mesh leaves its build pose.
+ * The counts (n_spheres, n_materials, n_triangles) and the precision are those of creation.
+ * Host form: a NULL array means "unchanged" (all three NULL, or an array the scene was created without: SPIRA_E_INVALID); every array given is validated
+ * exactly as spira_scene_create_* validates it, and triangles10 against the frame rule below, BEFORE anything on the device is touched.  Ordered like every
+ * entry (renders still traversing the old tree finish first); returns when the scene is ready.
+ * Device form: d_triangles10 is a DEVICE array in the triangles10 layout (e.g. a tensor a simulation wrote), read on `stream`.  A check kernel runs first
+ * (finite vertices, material index in 1..n_materials, the frame rule); the entry SYNCHRONISES `stream` ONCE to read its status word — as the adaptive entries
+ * do once per round — then enqueues the refit and returns without a second synchronisation; d_triangles10 must stay valid until that work has run.
+ * A refused update (either form) leaves the handle rendering what it rendered before.
+ * Frame rule: the normalised frame of a tree (centre, power-of-two scale) is fixed when the handle is created, with the mesh within about +-0.5 of it; an
+ * update whose vertices leave |(x - centre) * scale| <= 1 on any axis is SPIRA_E_LIMIT — create a new handle for such a mesh.  That leaves room to move or
+ * grow by about the mesh's own size.  A mesh of at most SPIRA_LDS_TRIANGLES triangles has no tree and no frame: its update is the new array.
+ * Errors: the handle's other precision: SPIRA_E_INVALID; a handle made by spira_scene_create_multi_* (whatever its n_devices): SPIRA_E_UNSUPPORTED.
+ * The host-array render entry points and their hash-keyed tree cache are not involved. */
+int spira_scene_update_f32(spira_scene *scene, const float *spheres5, const float *materials8, const float *triangles10);
+int spira_scene_update_f64(spira_scene *scene, const double *spheres5, const double *materials8, const double *triangles10);
+int spira_scene_update_device_f32(spira_scene *scene, const float *d_triangles10, void *stream);
+int spira_scene_update_device_f64(spira_scene *scene, const double *d_triangles10, void *stream);
 int spira_render_scene_f32(const spira_scene *scene, const float camera12[12], const spira_params *params,
                            float *out_hdr, float *out_img);
 int spira_render_scene_f64(const spira_scene *scene, const double camera12[12], const spira_params *params,

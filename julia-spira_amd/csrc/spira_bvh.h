@@ -198,6 +198,8 @@ template <class T> struct BvhFrame {
     T scale;
     uint32_t n_slots;             // node slots (80 bytes each), breadth first: slot 0 = root
     int depth;                    // levels of 8-wide nodes
+    uint32_t level_first[kBvhStack];   // level d (0 = the root) holds slots [level_first[d], level_first[d + 1]), level_first[depth] = n_slots: what a refit
+                                       // walks, deepest level first (spira_refit.h)
 };
 
 template <class T> struct Bvh8Build {
@@ -589,6 +591,8 @@ bool bvh_build(const T *triangles10, uint32_t n, RawVec<uint32_t> &nodes, RawVec
         // number the level: child blocks and triangle positions in the level's order (a prefix sum, the only serial part), then write in parallel
         child_base_of.resize(level.size()); tri_base_of.resize(level.size());
         uint32_t slots = (uint32_t)(nodes.size() / kBvhNodeDwords), n_order = (uint32_t)order.size(), n_next = 0;
+        if (depth == 1) frame.level_first[0] = 0;
+        frame.level_first[depth] = slots;          // the next level starts with the first block handed out below (the last level hands out none: n_slots)
         for (size_t i = 0; i < level.size(); ++i) {
             const Made &m = made[i];
             if (!m.ok) return false;

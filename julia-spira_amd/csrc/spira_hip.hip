@@ -40,6 +40,7 @@
 #include "spira_plan.h"
 #include "spira_adaptive.h"
 #include "spira_denoise.h"
+#include "spira_refit.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -70,6 +71,7 @@ int features_impl_f32(const spira_scene *h, const float *spheres5, const float *
                       float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream);
 int denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                      float *out_hdr, float *out_img, bool on_device, void *user_stream);
+int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -111,7 +113,16 @@ struct SceneStore {
     uint32_t ns = 0, nm = 0, nt = 0;
     uint64_t bvh_hash = 0; uint32_t bvh_n = 0, bvh_slots = 0; int bvh_prec = 0, bvh_depth = 0;
     bool moderate = false;                    // every coordinate / radius of ordinary magnitude (spira::scene_scale_moderate): speculative division pays
-    void release() { arrays.release(); bvh_nodes.release(); bvh_tris.release(); bvh_tris32.release(); bvh_hash = 0; bvh_n = 0; }
+    bool moderate_s = true, moderate_t = true;      // ... its two halves, spheres and triangles: spira_scene_update_* replaces them one at a time
+    // what a refit of the tree needs (spira_refit.h): the frame the tree was built in, the first slot of every level (+ n_slots at the end), and — allocated by
+    // the first update — one Float32 box per triangle and per node slot, and the staged triangle array of a host-form update
+    double bvh_centre[3] = {0, 0, 0}, bvh_scale = 1;
+    std::vector<uint32_t> bvh_level_first;
+    DevBuf refit_tbox, refit_nbox, refit_stage;
+    void release() {
+        arrays.release(); bvh_nodes.release(); bvh_tris.release(); bvh_tris32.release(); refit_tbox.release(); refit_nbox.release(); refit_stage.release();
+        bvh_hash = 0; bvh_n = 0;
+    }
 };
 
 struct Ctx {
@@ -128,6 +139,8 @@ struct Ctx {
     DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
+    DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
+    uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
     SceneStore scene;                         // the scene of the current call (host-array entry points)
     spira::Stats *h_stats = nullptr;          // pinned
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging of a host-output frame (copy_out below)
@@ -158,6 +171,7 @@ struct spira_scene {
     int device;
     int prec;              // sizeof(T) the scene was created in
     SceneStore store;
+    bool multi = false;    // made by spira_scene_create_multi_* (whatever its device count): spira_scene_update_* does not take it
     // spira_scene_create_multi_*: the same scene resident on devices 1 .. n_replicas-1 as well (this handle is device 0's)
     int n_replicas = 1;
     spira_scene *replica[16] = {};
@@ -323,6 +337,7 @@ template <class T> struct HostBvh {
     spira::RawVec<spira::HostPack4<float>> tris32;          // Float64 only
     spira::HostPack4<T> frame[3];
     uint32_t slots = 0; int depth = 0; bool built = false;
+    std::vector<uint32_t> level_first;                      // BvhFrame::level_first[0 .. depth]
 };
 template <class T>
 int host_bvh_build(const T *triangles10, uint32_t nt, HostBvh<T> &hb) {
@@ -337,6 +352,7 @@ int host_bvh_build(const T *triangles10, uint32_t nt, HostBvh<T> &hb) {
     hb.frame[0] = {fr.root_mn[0], fr.root_mn[1], fr.root_mn[2], (T)0}; hb.frame[1] = {fr.root_mx[0], fr.root_mx[1], fr.root_mx[2], (T)0};
     hb.frame[2] = {fr.centre[0], fr.centre[1], fr.centre[2], fr.scale};
     hb.slots = fr.n_slots; hb.depth = fr.depth; hb.built = true;
+    hb.level_first.assign(fr.level_first, fr.level_first + fr.depth + 1);
     return 0;
 }
 
@@ -353,7 +369,9 @@ int scene_upload(SceneStore &s, hipStream_t st, hipEvent_t prev_done, const T *s
     Lap lap("scene_upload");
     if (int rc = s.arrays.ensure(up(ns_b) + up(nm_b) + up(nt_b) + 256)) return rc;
     s.ns = n_spheres; s.nm = n_materials; s.nt = nt;
-    s.moderate = spira::scene_scale_moderate<T>(spheres5, triangles10, n_spheres, nt);
+    s.moderate_s = spira::scene_scale_moderate<T>(spheres5, nullptr, n_spheres, 0);
+    s.moderate_t = spira::scene_scale_moderate<T>(nullptr, triangles10, 0, nt);
+    s.moderate = s.moderate_s && s.moderate_t;
     lap("alloc+scale");
     spira::SceneGlobal<T> g;
     scene_pointers<T>(s, g);
@@ -397,6 +415,8 @@ int scene_upload(SceneStore &s, hipStream_t st, hipEvent_t prev_done, const T *s
             const int depth = hb.depth;
             s.bvh_slots = hb.slots;
             s.bvh_hash = h; s.bvh_n = nt; s.bvh_prec = (int)sizeof(T); s.bvh_depth = depth;
+            s.bvh_centre[0] = (double)hb.frame[2].x; s.bvh_centre[1] = (double)hb.frame[2].y; s.bvh_centre[2] = (double)hb.frame[2].z; s.bvh_scale = (double)hb.frame[2].w;
+            s.bvh_level_first = hb.level_first;
         }
     }
     return 0;
@@ -1441,6 +1461,170 @@ int features_entry(const spira_scene *h, const T *spheres5, const T *materials8,
         return features_impl<T>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
 }
 
+// ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
+// The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
+// walk or the node format is involved: a refit rewrites boxes, and the walk only prunes with them.
+struct RefitFrame { double centre[3], scale, pad; };
+constexpr uint32_t kRefitBlock = 256, kRefitLevelBlock = 64;      // (a level is a few thousand lanes at most: small workgroups spread it over the CUs)
+
+// device form only: every triangle of the caller's array against the rules, the bits of all of them OR-ed into one word (vector atomics, and only from the
+// lanes that have something to say: none, for a mesh that is accepted and of ordinary magnitude)
+template <class T>
+__global__ __launch_bounds__(kRefitBlock) void k_refit_check(const T *tri10, uint32_t n, uint32_t n_materials, RefitFrame f, int frame, uint32_t *status) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    T t[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) t[k] = tri10[10 * (size_t)i + k];
+    const uint32_t st = spira::refit_check_triangle<T>(t, n_materials, f.centre, f.scale, frame != 0);
+    if (st) atomicOr(status, st);
+}
+
+// one lane per REORDERED triangle i < n: the original index sits in tris[3 i].w, the ten values are gathered from there, the three packets of the record
+// (and of the screening record, where the store has one) go out as 16-byte stores, the padded box to the scratch.  `tris` points past the frame packets.
+template <class T>
+__global__ __launch_bounds__(kRefitBlock) void k_refit_tris(const T *tri10, uint32_t n, RefitFrame f, spira::RefitPack4<T> *tris, spira::RefitPack4<float> *tris32,
+                                                            spira::RefitBox *tbox) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t oi = spira::refit_index_of<T>(tris[3 * (size_t)i].w);
+    if (oi >= n) return;                                   // (cannot happen in a record the builder or this kernel wrote; never read outside the array)
+    T t[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) t[k] = tri10[10 * (size_t)oi + k];
+    spira::RefitPack4<T> out[3];
+    spira::RefitPack4<float> out32[3];
+    spira::RefitBox box;
+    spira::refit_triangle<T>(t, oi, f.centre, f.scale, f.pad, out, tris32 ? out32 : nullptr, box);
+    tris[3 * (size_t)i + 0] = out[0]; tris[3 * (size_t)i + 1] = out[1]; tris[3 * (size_t)i + 2] = out[2];
+    if (tris32) { tris32[3 * (size_t)i + 0] = out32[0]; tris32[3 * (size_t)i + 1] = out32[1]; tris32[3 * (size_t)i + 2] = out32[2]; }
+    tbox[i] = box;
+}
+
+// one launch per level, deepest first (the stream orders them: a node reads the boxes its child nodes wrote in the launch before); one lane per slot in
+// [first, end).  The node comes in through the walk's five 16-byte loads; a hole is left alone; words 0-3 and 8-19 go back as four 16-byte stores (words
+// 4-7 are never written), the node's own box to the scratch, and slot 0 also rewrites the root box of the frame packets.
+template <class T>
+__global__ __launch_bounds__(kRefitLevelBlock) void k_refit_level(uint4 *nodes, uint32_t first, uint32_t end, uint32_t n_slots, const spira::RefitBox *tbox, uint32_t n,
+                                                                  spira::RefitBox *nbox, RefitFrame f, spira::RefitPack4<T> *frame_packets) {
+    const uint32_t s = first + blockIdx.x * kRefitLevelBlock + threadIdx.x;
+    if (s >= end || s >= n_slots) return;
+    uint4 *pn = nodes + 5 * (size_t)s;
+    const uint4 n0 = pn[0], n1 = pn[1], n2 = pn[2], n3 = pn[3], n4 = pn[4];
+    uint32_t w[20] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w, n2.x, n2.y, n2.z, n2.w, n3.x, n3.y, n3.z, n3.w, n4.x, n4.y, n4.z, n4.w};
+    spira::RefitBox self;
+    if (!spira::refit_node(w, tbox, n, nbox, n_slots, self)) return;
+    pn[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    pn[2] = make_uint4(w[8], w[9], w[10], w[11]); pn[3] = make_uint4(w[12], w[13], w[14], w[15]); pn[4] = make_uint4(w[16], w[17], w[18], w[19]);
+    nbox[s] = self;
+    if (s == 0) {
+        spira::RefitPack4<T> mn, mx;
+        spira::refit_root<T>(self, f.centre, f.scale, mn, mx);
+        frame_packets[0] = mn; frame_packets[1] = mx;
+    }
+}
+
+// Host form (device_form false): any of the three host arrays, NULL = unchanged; validated in full before the device is touched; returns when the scene
+// is ready.  Device form: d_triangles10 in the caller's layout, checked by k_refit_check (ONE synchronisation of the stream, to read the status word), then
+// the refit is enqueued and the call returns.  Either way a refused update leaves the handle as it was.
+template <class T>
+int scene_update_impl(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+    if (int rc = check_handle<T>(h)) return rc;
+    if (h->multi) return fail(SPIRA_E_UNSUPPORTED, "spira_scene_update_* does not take a handle made by spira_scene_create_multi_*");
+    SceneStore &s = h->store;
+    const bool use_bvh = s.nt > SPIRA_LDS_TRIANGLES;
+    const char *msg = nullptr;
+    bool mod_s = s.moderate_s, mod_t = s.moderate_t;
+    RefitFrame f{};
+    for (int k = 0; k < 3; ++k) f.centre[k] = s.bvh_centre[k];
+    f.scale = s.bvh_scale;
+    f.pad = spira::refit_pad<T>(f.centre, f.scale);
+    const bool new_tris = device_form || triangles10 != nullptr;
+    if (device_form) {
+        if (!d_triangles10) return fail(SPIRA_E_INVALID, "d_triangles10 is NULL");
+        if (!s.nt) return fail(SPIRA_E_INVALID, "the scene was created without triangles: the counts of a handle are fixed");
+    } else {
+        if (!spheres5 && !materials8 && !triangles10) return fail(SPIRA_E_INVALID, "spheres5, materials8 and triangles10 are all NULL: nothing to update");
+        if ((spheres5 && !s.ns) || (triangles10 && !s.nt)) return fail(SPIRA_E_INVALID, "the scene was created without that array: the counts of a handle are fixed");
+        if (spheres5) { if (int rc = spira::spheres_check<T>(spheres5, s.ns, s.nm, &msg)) return fail(rc, msg); }
+        if (materials8) { if (int rc = spira::materials_check<T>(materials8, s.nm, &msg)) return fail(rc, msg); }
+        if (triangles10) {
+            if (int rc = spira::triangles_check<T>(triangles10, s.nt, s.nm, &msg)) return fail(rc, msg);
+            uint32_t st = 0;
+            for (uint32_t i = 0; i < s.nt; ++i) st |= spira::refit_check_triangle<T>(triangles10 + 10 * (size_t)i, s.nm, f.centre, f.scale, use_bvh);
+            if (st & (spira::kRefitNonFinite | spira::kRefitMaterial)) return fail(SPIRA_E_INVALID, "triangle with a non-finite vertex or a material index out of range");
+            if (st & spira::kRefitFrame) return fail(SPIRA_E_LIMIT, "a vertex leaves the frame the tree was built in (|(x - centre) * scale| <= 1): create a new handle for this mesh");
+            mod_t = !(st & spira::kRefitImmoderate);
+        }
+        if (spheres5) mod_s = spira::scene_scale_moderate<T>(spheres5, nullptr, s.ns, 0);
+    }
+    if (use_bvh && new_tris) {
+        const size_t d = (size_t)s.bvh_depth;
+        bool ok = s.bvh_prec == (int)sizeof(T) && s.bvh_n == s.nt && d >= 1 && s.bvh_level_first.size() == d + 1 && s.bvh_level_first[0] == 0 && s.bvh_level_first[d] == s.bvh_slots;
+        for (size_t l = 0; ok && l < d; ++l) ok = s.bvh_level_first[l] < s.bvh_level_first[l + 1];
+        if (!ok) return fail(SPIRA_E_LIMIT, "internal: the handle's tree has no consistent level table");
+        if (!(f.pad < 1e12)) return fail(SPIRA_E_LIMIT, "the mesh is too far from the origin for its size: its boxes cannot be padded in Float32");
+    }
+    Session sess;
+    if (int rc = Session::open(sess, device_form, user_stream)) return rc;
+    Ctx &c = *sess.cp;
+    const hipStream_t st = sess.st;
+    if (use_bvh && new_tris) {
+        if (int rc = s.refit_tbox.ensure((size_t)s.nt * sizeof(spira::RefitBox))) return rc;
+        if (int rc = s.refit_nbox.ensure((size_t)s.bvh_slots * sizeof(spira::RefitBox))) return rc;
+        if (!device_form) { if (int rc = s.refit_stage.ensure((size_t)s.nt * 10 * sizeof(T))) return rc; }
+    }
+    const dim3 tri_grid((s.nt + kRefitBlock - 1) / kRefitBlock), tri_block(kRefitBlock);
+    if (device_form) {
+        if (int rc = c.refit_status.ensure(sizeof(uint32_t))) return rc;
+        if (!c.h_refit_status) HIP_TRY(hipHostMalloc((void **)&c.h_refit_status, sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(hipMemsetAsync(c.refit_status.p, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL((k_refit_check<T>), tri_grid, tri_block, 0, st, d_triangles10, s.nt, s.nm, f, use_bvh ? 1 : 0, (uint32_t *)c.refit_status.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c.h_refit_status, c.refit_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t status = *c.h_refit_status;
+        if (status & spira::kRefitNonFinite) return fail(SPIRA_E_INVALID, "triangle with a non-finite vertex");
+        if (status & spira::kRefitMaterial) return fail(SPIRA_E_INVALID, "triangle material index out of range");
+        if (status & spira::kRefitFrame) return fail(SPIRA_E_LIMIT, "a vertex leaves the frame the tree was built in (|(x - centre) * scale| <= 1): create a new handle for this mesh");
+        mod_t = !(status & spira::kRefitImmoderate);
+    }
+    spira::SceneGlobal<T> g;
+    scene_pointers<T>(s, g);
+    if (spheres5) HIP_TRY(hipMemcpyAsync((void *)g.spheres5, spheres5, (size_t)s.ns * 5 * sizeof(T), hipMemcpyHostToDevice, st));
+    if (materials8) HIP_TRY(hipMemcpyAsync((void *)g.materials8, materials8, (size_t)s.nm * 8 * sizeof(T), hipMemcpyHostToDevice, st));
+    if (new_tris && !use_bvh) {          // an LDS-resident mesh has no tree: its update is the array
+        HIP_TRY(hipMemcpyAsync((void *)g.triangles10, device_form ? d_triangles10 : triangles10, (size_t)s.nt * 10 * sizeof(T),
+                               device_form ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    } else if (new_tris) {
+        const T *src = d_triangles10;
+        if (!device_form) {
+            HIP_TRY(hipMemcpyAsync(s.refit_stage.p, triangles10, (size_t)s.nt * 10 * sizeof(T), hipMemcpyHostToDevice, st));
+            src = (const T *)s.refit_stage.p;
+        }
+        spira::RefitPack4<T> *frame_packets = (spira::RefitPack4<T> *)s.bvh_tris.p;
+        spira::RefitBox *tbox = (spira::RefitBox *)s.refit_tbox.p, *nbox = (spira::RefitBox *)s.refit_nbox.p;
+        hipLaunchKernelGGL((k_refit_tris<T>), tri_grid, tri_block, 0, st, src, s.nt, f, frame_packets + 3, (spira::RefitPack4<float> *)s.bvh_tris32.p, tbox);
+        for (int l = s.bvh_depth - 1; l >= 0; --l) {
+            const uint32_t first = s.bvh_level_first[(size_t)l], end = s.bvh_level_first[(size_t)l + 1];
+            hipLaunchKernelGGL((k_refit_level<T>), dim3((end - first + kRefitLevelBlock - 1) / kRefitLevelBlock), dim3(kRefitLevelBlock), 0, st, (uint4 *)s.bvh_nodes.p, first, end,
+                               s.bvh_slots, (const spira::RefitBox *)tbox, s.nt, nbox, f, frame_packets);
+        }
+    }
+    s.moderate_s = mod_s; s.moderate_t = mod_t; s.moderate = mod_s && mod_t;
+    return sess.close();
+}
+
+// scene_update_impl<T> of whichever translation unit holds the kernels of T
+template <class T>
+int scene_update_entry(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4) return spira_tu::scene_update_impl_f32(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
+    else
+#endif
+        return scene_update_impl<T>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
+}
+
 // ---- the a-trous denoiser (spira_denoise_*; spira_denoise.h): prepare, then one launch per iteration between the context's two record buffers, the last
 // one writing the outputs.  The device form enqueues and returns; it allocates only when a workspace has to grow (a first call at a size).
 template <class T>
@@ -1617,7 +1801,7 @@ int scene_create(const T *spheres5, const T *materials8, const T *triangles10, u
         if ((rc = get_ctx(&cp))) break;                // also selects the device
         spira_scene *h = new (std::nothrow) spira_scene();
         if (!h) { rc = fail(SPIRA_E_HIP, "out of host memory"); break; }
-        h->magic = kSceneMagic; h->device = tl_device; h->prec = (int)sizeof(T);
+        h->magic = kSceneMagic; h->device = tl_device; h->prec = (int)sizeof(T); h->multi = multi;
         if (!first) first = h; else { first->replica[d] = h; }
         rc = scene_upload<T>(h->store, nullptr, nullptr, spheres5, materials8, triangles10, n_spheres, n_materials, nt, &hb);
         if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SPIRA_E_HIP, "hipStreamSynchronize failed after the scene upload");
@@ -1907,6 +2091,9 @@ int spira_tu::features_impl_f32(const spira_scene *h, const float *spheres5, con
                                 float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream) {
     return features_impl<float>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
 }
+int spira_tu::scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
+    return scene_update_impl<float>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
+}
 int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                                float *out_hdr, float *out_img, bool on_device, void *user_stream) {
     return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
@@ -2001,6 +2188,8 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
+        c.refit_status.release();
+        if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
         c.ev_pool.clear();
         for (hipEvent_t e : c.ev_mid) (void)hipEventDestroy(e);
@@ -2107,6 +2296,19 @@ int spira_scene_destroy(spira_scene *scene) {
     }
     (void)hipSetDevice(tl_device);
     return 0;
+}
+// ---- new contents for a live handle (host arrays, NULL = unchanged; a device triangle array on the caller's stream): the tree is refitted, not rebuilt
+int spira_scene_update_f32(spira_scene *scene, const float *spheres5, const float *materials8, const float *triangles10) {
+    return scene_update_entry<float>(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
+}
+int spira_scene_update_f64(spira_scene *scene, const double *spheres5, const double *materials8, const double *triangles10) {
+    return scene_update_entry<double>(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
+}
+int spira_scene_update_device_f32(spira_scene *scene, const float *d_triangles10, void *stream) {
+    return scene_update_entry<float>(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
+}
+int spira_scene_update_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) {
+    return scene_update_entry<double>(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
 }
 int spira_render_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, float *out_hdr, float *out_img) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");

@@ -19,7 +19,7 @@ using Colors
 
 export Scene, Camera, Ray, Sphere, Material, Point3, Vec3, Color,
        render_hybrid_gpu, render_with_cpu, render, render_multi, create_scene, prepare_scene_data,
-       SceneHandle, destroy!, save_png, save_exr
+       SceneHandle, destroy!, update!, save_png, save_exr
 
 const libspira = get(ENV, "SPIRA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libspira_hip.so"))
 
@@ -171,6 +171,34 @@ function destroy!(h::SceneHandle)
         h.ptr = C_NULL
     end
     return nothing
+end
+
+# New contents for a live handle (spira_scene_update_f32): spheres and materials of `scene` (as many of each as the handle was made with), and / or a flat
+# triangles10 array for a handle whose mesh has a tree — that tree is refitted on the device, not rebuilt, and the vertices must stay inside the frame it
+# was built in (error -4 otherwise; the handle then renders what it rendered before).  Returns when the scene is ready.
+function update!(h::SceneHandle; scene::Union{Scene,Nothing}=nothing, triangles::Union{Vector{Float32},Nothing}=nothing)
+    scene === nothing && triangles === nothing && error("update!: nothing to update")
+    if scene !== nothing
+        (length(scene.spheres) == length(h.scene.spheres) && length(scene.materials) == length(h.scene.materials)) ||
+            error("update!: the counts of a handle are fixed at creation")
+    end
+    sphere_data, material_data = scene === nothing ? (C_NULL, C_NULL) : prepare_scene_data(scene)
+    rc = ccall((:spira_scene_update_f32, libspira), Cint,
+               (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}),
+               h.ptr, sphere_data, material_data, triangles === nothing ? C_NULL : triangles)
+    rc == 0 || spira_error(rc)
+    scene === nothing || (h.scene = scene)
+    return h
+end
+
+# The device form (spira_scene_update_device_f32): triangles10 in DEVICE memory (e.g. the pointer of a ROCArray a simulation wrote), read on `stream`;
+# synchronises the stream once (the check kernel's status word), then enqueues the refit and returns.
+function update!(h::SceneHandle, d_triangles::Ptr{Float32}; stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_scene_update_device_f32, libspira), Cint,
+               (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}),
+               h.ptr, d_triangles, stream)
+    rc == 0 || spira_error(rc)
+    return h
 end
 
 function render_hybrid_gpu(width::Int, height::Int, h::SceneHandle, camera::Camera;

@@ -38,6 +38,7 @@ EXPORTS = [
     "spira_render_features_f32", "spira_render_features_f64", "spira_render_features_scene_f32", "spira_render_features_scene_f64",
     "spira_render_features_scene_device_f32", "spira_render_features_scene_device_f64",
     "spira_denoise_f32", "spira_denoise_f64", "spira_denoise_device_f32", "spira_denoise_device_f64",
+    "spira_scene_update_f32", "spira_scene_update_f64", "spira_scene_update_device_f32", "spira_scene_update_device_f64",
 ]
 
 
@@ -243,6 +244,35 @@ class Scene:
         _check(fn(self._h, cp, C.byref(params), C.c_int(n_devices or self.n_devices), hdr.ctypes.data_as(C.c_void_p) if want_hdr else None,
                   img.ctypes.data_as(C.c_void_p) if want_img else None))
         return hdr, img
+
+    def update(self, spheres5=None, materials8=None, triangles10=None):
+        """spira_scene_update_*: new contents for this handle from host arrays (None = unchanged; the counts are those of creation).  A mesh with a
+        tree is refitted on the device, not rebuilt: its vertices must stay inside the frame the tree was built in (|(x - centre) * scale| <= 1, about the
+        mesh's own size of room), else SpiraError (-4) and the handle renders what it rendered before.  Returns when the scene is ready."""
+        npdt, _ = _dt(self.prec)
+        arrs = [_arr(spheres5, npdt), _arr(materials8, npdt), _arr(triangles10, npdt)]
+        for (a, _), n, w in zip(arrs, self.counts, (5, 8, 10)):
+            if a is not None and a.size != n * w:
+                raise ValueError("update: an array of %d values where the handle holds %d x %d" % (a.size, n, w))
+        fn = lib().spira_scene_update_f32 if self.prec == "f32" else lib().spira_scene_update_f64
+        _check(fn(self._h, arrs[0][1], arrs[1][1], arrs[2][1]))
+
+    def update_device(self, triangles, stream=None):
+        """spira_scene_update_device_*: the mesh's new triangles10 from DEVICE memory — a contiguous torch tensor of the handle's precision and n_triangles x 10
+        values, or an integer device address — read on `stream` (a torch stream, an integer hipStream_t, None = the null stream).  Synchronises the stream once
+        (the check kernel's status), then enqueues the refit and returns; the array must stay alive until that work has run."""
+        npdt, _ = _dt(self.prec)
+        if hasattr(triangles, "data_ptr"):
+            import torch
+            want = torch.float32 if self.prec == "f32" else torch.float64
+            if triangles.dtype != want or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() != self.counts[2] * 10:
+                raise ValueError("update_device: a contiguous device tensor of %d x 10 %s values is needed" % (self.counts[2], self.prec))
+            ptr = triangles.data_ptr()
+        else:
+            ptr = int(triangles or 0)
+        sp = getattr(stream, "cuda_stream", stream)
+        fn = lib().spira_scene_update_device_f32 if self.prec == "f32" else lib().spira_scene_update_device_f64
+        _check(fn(self._h, C.c_void_p(ptr or None), C.c_void_p(sp or None)))
 
     def destroy(self):
         if self._h:
