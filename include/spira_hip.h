@@ -273,6 +273,31 @@ int spira_scene_update_f32(spira_scene *scene, const float *spheres5, const floa
 int spira_scene_update_f64(spira_scene *scene, const double *spheres5, const double *materials8, const double *triangles10);
 int spira_scene_update_device_f32(spira_scene *scene, const float *d_triangles10, void *stream);
 int spira_scene_update_device_f64(spira_scene *scene, const double *d_triangles10, void *stream);
+/* A new triangle array for a LIVE handle, the mesh's tree built ANEW on the device (spira_lbvh.h): a new frame and a new topology, so there is NO frame rule
+ * — the mesh may have walked across the scene or grown to any size — and no refit decay to carry along.  n_triangles and the precision are those of creation;
+ * spheres and materials are untouched (spira_scene_update_* still changes them).  The build: exact vertex bounds -> the frame a fresh host build of the same
+ * array would get, bit for bit -> 63-bit Morton keys of the centroids, sorted stably -> a binary radix tree (Karras 2012) -> its boxes, bottom-up ->
+ * collapsed to the 8-wide slots by the host builder's rules -> the refit passes of spira_scene_update_* write every record and every box.  The tree only
+ * prunes: a render after a rebuild is bit for bit the render of a fresh handle on the same arrays.  What differs is the topology (Morton order, not SAH) and
+ * with it traversal time (README, docs/experiments.md section 24).  There is no automatic choice between refit and rebuild: the caller decides.
+ * Validation is that of the update entries minus the frame rule: every vertex finite, every material index an integer in 1..n_materials, else SPIRA_E_INVALID.
+ * Host form: validates on the host BEFORE the device is touched, stages the array, runs the same pipeline; returns when the scene is ready.
+ * Device form: d_triangles10 is a DEVICE array in the triangles10 layout, read on `stream`.  A check kernel validates it and reduces the vertex bounds in the
+ * same pass.  The entry SYNCHRONISES `stream` ONCE for that status and the bounds, and ONCE PER LEVEL of the new tree for the level's counts (4 levels of
+ * 8-wide nodes for a sphere of 1 280 triangles; never more than 61); after the last of these it enqueues the remaining work and returns; d_triangles10 must
+ * stay valid until that work has run.  Ordered like every entry: renders still walking the old tree finish first, a render enqueued after the call on any stream sees the new tree.
+ * A REFUSED rebuild (either form) leaves the handle rendering what it rendered before: validation, a tree of 62 levels or more, more than 2^24 node slots, a
+ * mesh so far from the origin for its size that its boxes cannot be padded in Float32 (SPIRA_E_LIMIT, as for an update) and a failed allocation all refuse
+ * while only scratch memory of the device context has been written (kept until spira_shutdown, like the other workspaces).
+ * A mesh of at most SPIRA_LDS_TRIANGLES triangles has no tree: its rebuild is the array copy, exactly as for the update.
+ * Errors: a NULL or destroyed handle, the handle's other precision, a NULL array, a handle created without triangles: SPIRA_E_INVALID; a handle made by
+ * spira_scene_create_multi_* (whatever its n_devices): SPIRA_E_UNSUPPORTED.
+ * Afterwards the handle is an ordinary handle: spira_scene_update_* refits the NEW tree and applies the frame rule against the NEW frame, and every render,
+ * feature and adaptive entry works on it. */
+int spira_scene_rebuild_f32(spira_scene *scene, const float *triangles10);
+int spira_scene_rebuild_f64(spira_scene *scene, const double *triangles10);
+int spira_scene_rebuild_device_f32(spira_scene *scene, const float *d_triangles10, void *stream);
+int spira_scene_rebuild_device_f64(spira_scene *scene, const double *d_triangles10, void *stream);
 int spira_render_scene_f32(const spira_scene *scene, const float camera12[12], const spira_params *params,
                            float *out_hdr, float *out_img);
 int spira_render_scene_f64(const spira_scene *scene, const double camera12[12], const spira_params *params,

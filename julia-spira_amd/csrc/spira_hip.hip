@@ -41,6 +41,7 @@
 #include "spira_adaptive.h"
 #include "spira_denoise.h"
 #include "spira_refit.h"
+#include "spira_lbvh.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -72,6 +73,7 @@ int features_impl_f32(const spira_scene *h, const float *spheres5, const float *
 int denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                      float *out_hdr, float *out_img, bool on_device, void *user_stream);
 int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
+int scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -125,6 +127,18 @@ struct SceneStore {
     }
 };
 
+// spira_scene_rebuild_* (spira_lbvh.h): what the host reads back, and the context's scratch carved for n triangles.  Named types: the kernels that do not
+// depend on the precision live in one translation unit and are reached from the others through spira_tu::lbvh_topology.
+struct LbvhSmall { unsigned long long nlo[3], hi[3]; uint32_t status, pad; uint32_t totals[4]; };      // bounds as lbvh_enc codes (nlo: of the complement, so 0 is neutral for both)
+struct LbvhWs {
+    uint64_t *keys; uint32_t *idx;                 // lbvh_sort_size(n) of each: sorted in place
+    spira::RefitBox *leafbox, *bbox;              // per triangle (original order); per binary node id
+    int32_t *left, *right, *parent; uint32_t *counter;
+    spira::LbvhPending *pending[2]; spira::LbvhMade *made;
+    uint32_t *child_base, *tri_base, *next_at, *order;
+};
+struct LbvhTopo { uint32_t n_slots = 0; int depth = 0; std::vector<uint32_t> level_first; };
+
 struct Ctx {
     bool init = false;
     int device = -1;
@@ -141,6 +155,9 @@ struct Ctx {
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
     uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
+    DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
+    struct LbvhSmall *h_lbvh = nullptr;           // ... and where the host reads the last (pinned)
+    std::vector<void *> lbvh_retired;             // node scratch outgrown in the middle of a rebuild: freed by the next one (a free waits for the device)
     SceneStore scene;                         // the scene of the current call (host-array entry points)
     spira::Stats *h_stats = nullptr;          // pinned
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging of a host-output frame (copy_out below)
@@ -164,6 +181,9 @@ inline Ctx g_ctx[kMaxDevices];
 
 }  // namespace spira_host
 using namespace spira_host;
+namespace spira_tu {      // defined in the SPIRA_TU_MAIN unit (or the single one): sort, radix tree, boxes and collapse of a rebuild — nothing of it reads T
+int lbvh_topology(Ctx &c, hipStream_t st, uint32_t n, const LbvhWs &w, LbvhTopo &out);
+}
 
 // The opaque scene handle of the C ABI (spira_scene_create_* / spira_scene_destroy).
 struct spira_scene {
@@ -1625,6 +1645,341 @@ int scene_update_entry(spira_scene *h, const T *spheres5, const T *materials8, c
         return scene_update_impl<T>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
 }
 
+// ======================================================================= spira_scene_rebuild_*: a new triangle array for a live handle, the tree built anew on the device
+// The arithmetic is spira_lbvh.h's (frame, Morton keys, radix tree, collapse) and spira_refit.h's (records and boxes).  A rebuild produces a frame and a
+// topology in the context's scratch — nothing of the handle is written while anything can still refuse — then moves them in and lets the refit passes
+// (k_refit_tris, k_refit_level) finish the tree.  The kernels that read T are here; the rest is spira_tu::lbvh_topology, compiled once.
+inline int lbvh_carve(Ctx &c, uint32_t n, LbvhWs &w) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+    const size_t nn = n, n_pad = spira::lbvh_sort_size(n), o_k0 = take(n_pad * 8), o_i0 = take(n_pad * 4), o_lb = take(nn * sizeof(spira::RefitBox)),
+                 o_bb = take(2 * nn * sizeof(spira::RefitBox)), o_l = take(nn * 4), o_r = take(nn * 4), o_p = take(2 * nn * 4), o_c = take(nn * 4),
+                 o_p0 = take(nn * sizeof(spira::LbvhPending)), o_p1 = take(nn * sizeof(spira::LbvhPending)), o_m = take(nn * sizeof(spira::LbvhMade)),
+                 o_cb = take(nn * 4), o_tb = take(nn * 4), o_na = take(nn * 4), o_o = take(nn * 4);
+    if (int rc = c.lbvh_ws.ensure(off)) return rc;
+    char *b = (char *)c.lbvh_ws.p;
+    w.keys = (uint64_t *)(b + o_k0); w.idx = (uint32_t *)(b + o_i0);
+    w.leafbox = (spira::RefitBox *)(b + o_lb); w.bbox = (spira::RefitBox *)(b + o_bb);
+    w.left = (int32_t *)(b + o_l); w.right = (int32_t *)(b + o_r); w.parent = (int32_t *)(b + o_p); w.counter = (uint32_t *)(b + o_c);
+    w.pending[0] = (spira::LbvhPending *)(b + o_p0); w.pending[1] = (spira::LbvhPending *)(b + o_p1); w.made = (spira::LbvhMade *)(b + o_m);
+    w.child_base = (uint32_t *)(b + o_cb); w.tri_base = (uint32_t *)(b + o_tb); w.next_at = (uint32_t *)(b + o_na); w.order = (uint32_t *)(b + o_o);
+    return 0;
+}
+
+// one lane per triangle of the caller's array: the status bits of all of them OR-ed into one word and the exact bounds of all vertices, reduced in the wave
+// (shuffles), in the workgroup (LDS), then by vector atomics on order-preserving integer codes — minimum and maximum are exact, so the order does not matter
+template <class T>
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_check(const T *tri10, uint32_t n, uint32_t n_materials, LbvhSmall *out) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    double lo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()}, hi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
+    uint32_t st = 0;
+    if (i < n) {
+        T t[10];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) t[k] = tri10[10 * (size_t)i + k];
+        const double zero[3] = {0, 0, 0};
+        st = spira::refit_check_triangle<T>(t, n_materials, zero, 1.0, false);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { const double x = (double)t[k]; lo[k % 3] = x < lo[k % 3] ? x : lo[k % 3]; hi[k % 3] = x > hi[k % 3] ? x : hi[k % 3]; }
+    }
+    for (int off = 32; off; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double a = __shfl_xor(lo[k], off), b = __shfl_xor(hi[k], off);
+            lo[k] = a < lo[k] ? a : lo[k]; hi[k] = b > hi[k] ? b : hi[k];
+        }
+        st |= __shfl_xor(st, off);
+    }
+    __shared__ double s_lo[kRefitBlock / 64][3], s_hi[kRefitBlock / 64][3];
+    __shared__ uint32_t s_st[kRefitBlock / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0) { for (int k = 0; k < 3; ++k) { s_lo[wave][k] = lo[k]; s_hi[wave][k] = hi[k]; } s_st[wave] = st; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int k = (int)threadIdx.x;
+        double a = s_lo[0][k], b = s_hi[0][k];
+        for (uint32_t v = 1; v < kRefitBlock / 64; ++v) { a = s_lo[v][k] < a ? s_lo[v][k] : a; b = s_hi[v][k] > b ? s_hi[v][k] : b; }
+        atomicMax(&out->nlo[k], (unsigned long long)~spira::lbvh_enc(a));
+        atomicMax(&out->hi[k], (unsigned long long)spira::lbvh_enc(b));
+    } else if (threadIdx.x == 3) {
+        uint32_t all = 0;
+        for (uint32_t v = 0; v < kRefitBlock / 64; ++v) all |= s_st[v];
+        if (all) atomicOr(&out->status, all);
+    }
+}
+
+// one lane per element i of the sort's padded array: triangle i's Morton key in the new frame, itself as the pair's second half, and its padded box
+// (original order); beyond the mesh the pairs that sort last
+template <class T>
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_keys(const T *tri10, uint32_t n, uint32_t n_pad, RefitFrame f, uint64_t *keys, uint32_t *idx, spira::RefitBox *leafbox) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) { if (i < n_pad) { keys[i] = ~0ull; idx[i] = ~0u; } return; }
+    T t[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) t[k] = tri10[10 * (size_t)i + k];
+    spira::RefitPack4<T> rec[3];
+    spira::RefitBox box;
+    spira::refit_triangle<T>(t, i, f.centre, f.scale, f.pad, rec, nullptr, box);
+    keys[i] = spira::lbvh_key<T>(t, f.centre, f.scale);
+    idx[i] = i;
+    leafbox[i] = box;
+}
+
+// commit: the new triangle order into the records (tris[3 i].w = bits(original index): k_refit_tris gathers by it) and the new frame into packet 2
+template <class T>
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_commit(const uint32_t *order, uint32_t n, RefitFrame f, spira::RefitPack4<T> *frame_packets) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i >= n) return;
+    frame_packets[3 + 3 * (size_t)i].w = spira::refit_index_bits<T>(order[i]);
+    if (i == 0) { spira::RefitPack4<T> p; p.x = (T)f.centre[0]; p.y = (T)f.centre[1]; p.z = (T)f.centre[2]; p.w = (T)f.scale; frame_packets[2] = p; }
+}
+
+#if !defined(SPIRA_TU_F32) && !defined(SPIRA_TU_F64MESH)
+// ---- the kernels of a rebuild that do not read T (this unit only)
+constexpr uint32_t kLbvhScanBlock = 1024;
+// the sort (spira_lbvh.h, lbvh_sort_schedule): a tile of kLbvhSortTile pairs in LDS, one lane per pair, every pass of stages k_first .. k_last that stays
+// inside the tile; and one pass over the whole array for the strides that do not
+__global__ __launch_bounds__(spira::kLbvhSortTile) void k_lbvh_sort_tile(uint64_t *keys, uint32_t *idx, uint32_t k_first, uint32_t k_last) {
+    __shared__ uint64_t s_key[spira::kLbvhSortTile];
+    __shared__ uint32_t s_idx[spira::kLbvhSortTile];
+    const uint32_t t = threadIdx.x, g = blockIdx.x * spira::kLbvhSortTile + t;
+    s_key[t] = keys[g]; s_idx[t] = idx[g];
+    __syncthreads();
+    for (uint32_t k = k_first; k <= k_last && k != 0; k <<= 1)
+        for (uint32_t j = spira::lbvh_tile_first_j(k); j > 0; j >>= 1) {
+            spira::lbvh_bitonic_cx(s_key, s_idx, t, g, j, k);
+            __syncthreads();
+        }
+    keys[g] = s_key[t]; idx[g] = s_idx[t];
+}
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_sort_wide(uint64_t *keys, uint32_t *idx, uint32_t n_pad, uint32_t j, uint32_t k) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i < n_pad && (i ^ j) < n_pad) spira::lbvh_bitonic_cx(keys, idx, i, i, j, k);
+}
+// one lane per inner node of the binary radix tree; lane 0 also seeds the first level of the collapse.  The arrival counters are zeroed here.
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_radix(const uint64_t *keys, uint32_t n, int32_t *left, int32_t *right, int32_t *parent, uint32_t *counter,
+                                                            spira::LbvhPending *pending0) {
+    const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (i + 1 >= n) return;
+    int32_t l, r;
+    spira::lbvh_radix_node(keys, n, i, l, r);
+    left[i] = l; right[i] = r; counter[i] = 0u;
+    if ((uint32_t)l < 2 * n - 1) parent[l] = (int32_t)i;
+    if ((uint32_t)r < 2 * n - 1) parent[r] = (int32_t)i;
+    if (i == 0) { parent[0] = -1; pending0[0] = {0, 0u}; }
+}
+
+// One lane per leaf, walking up: it writes its node's box, bumps the parent's arrival counter, and goes on only if it came second — then the sibling's box
+// is complete.  Nobody waits for anybody.  Another CU (another XCD, with an L2 of its own) reads what this lane wrote, so: the box goes out as agent-scope
+// stores, a device fence (and the wait for it) stands between the box and the counter, the counter is an agent-scope atomic, and the lane that goes on fences
+// again before it reads the sibling's box with agent-scope loads.  Unions of Float32 bounds are exact: the result does not depend on who came first.
+__device__ inline void lbvh_box_publish(spira::RefitBox *dst, const spira::RefitBox &b) {
+    uint32_t *d = (uint32_t *)dst;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        __hip_atomic_store(d + k, spira::refit_bits(b.lo[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(d + 3 + k, spira::refit_bits(b.hi[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+__device__ inline void lbvh_box_fetch(const spira::RefitBox *src, spira::RefitBox &b) {
+    uint32_t *s = (uint32_t *)src;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        b.lo[k] = spira::refit_f32(__hip_atomic_load(s + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        b.hi[k] = spira::refit_f32(__hip_atomic_load(s + 3 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+}
+__global__ __launch_bounds__(kRefitBlock) void k_lbvh_boxes(uint32_t n, const uint32_t *sorted_idx, const spira::RefitBox *leafbox, const int32_t *left, const int32_t *right,
+                                                            const int32_t *parent, uint32_t *counter, spira::RefitBox *bbox) {
+    const uint32_t j = blockIdx.x * kRefitBlock + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t oi = sorted_idx[j];
+    if (oi >= n) return;                                   // (cannot happen: the sort permutes 0 .. n-1)
+    spira::RefitBox b = leafbox[oi];
+    uint32_t cur = (n - 1) + j;
+    for (int step = 0; step < 160; ++step) {               // (a path is at most 63 + 32 + 1 nodes long)
+        lbvh_box_publish(bbox + cur, b);
+        const int32_t p = parent[cur];
+        if (p < 0 || (uint32_t)p + 1 >= n) return;         // the root is done
+        __threadfence();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t arrived = __hip_atomic_fetch_add(counter + p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (arrived == 0u) return;                         // the first of the two: the second one goes on
+        __threadfence();
+        const int32_t l = left[p], r = right[p];
+        const int32_t sib = (uint32_t)l == cur ? r : l;
+        if ((uint32_t)sib >= 2 * n - 1) return;
+        spira::RefitBox o;
+        lbvh_box_fetch(bbox + sib, o);
+        spira::lbvh_box_union(b, o, b);
+        cur = (uint32_t)p;
+    }
+}
+
+// collapse, per level: (1) one lane per node of the level works out its entries and slots; (2) ONE workgroup takes the three prefix sums over the level, in
+// level order — wave scans by shuffles, the waves' totals through LDS — and leaves the new totals for the host; (3) one lane per node writes its slot, the
+// holes of its child block, its leaves' places in the triangle order and its node children's entries in the next level's list
+__global__ __launch_bounds__(kRefitLevelBlock) void k_lbvh_make(const spira::LbvhPending *level, uint32_t count, const int32_t *left, const int32_t *right, const spira::RefitBox *bbox,
+                                                                uint32_t n_inner, spira::LbvhMade *made) {
+    const uint32_t i = blockIdx.x * kRefitLevelBlock + threadIdx.x;
+    if (i >= count) return;
+    spira::LbvhMade m;
+    spira::lbvh_make_node(level[i].bnode, left, right, bbox, n_inner, m);
+    made[i] = m;
+}
+__global__ __launch_bounds__(kLbvhScanBlock) void k_lbvh_scan(const spira::LbvhMade *made, uint32_t count, uint32_t slots0, uint32_t tris0, uint32_t *child_base, uint32_t *tri_base,
+                                                              uint32_t *next_at, uint32_t *totals) {
+    __shared__ uint32_t s_wave[kLbvhScanBlock / 64][3], s_run[3];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (tid < 3) s_run[tid] = tid == 0 ? slots0 : tid == 1 ? tris0 : 0u;
+    __syncthreads();
+    for (uint32_t base = 0; base < count; base += kLbvhScanBlock) {
+        const uint32_t i = base + tid;
+        uint32_t v[3] = {0u, 0u, 0u}, inc[3];
+        if (i < count) spira::lbvh_node_counts(made[i], v[0], v[1], v[2]);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            inc[k] = v[k];
+            for (uint32_t off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(inc[k], off); if (lane >= off) inc[k] += t; }
+            if (lane == 63) s_wave[wave][k] = inc[k];
+        }
+        __syncthreads();
+        uint32_t pre[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { pre[k] = s_run[k]; for (uint32_t w = 0; w < wave; ++w) pre[k] += s_wave[w][k]; }
+        if (i < count) { child_base[i] = v[0] ? pre[0] + inc[0] - v[0] : 0u; tri_base[i] = pre[1] + inc[1] - v[1]; next_at[i] = pre[2] + inc[2] - v[2]; }
+        __syncthreads();
+        if (tid == kLbvhScanBlock - 1) { for (int k = 0; k < 3; ++k) s_run[k] = pre[k] + inc[k]; }
+        __syncthreads();
+    }
+    if (tid == 0) { totals[0] = s_run[0]; totals[1] = s_run[1]; totals[2] = s_run[2]; totals[3] = 0u; }
+}
+__global__ __launch_bounds__(kRefitLevelBlock) void k_lbvh_write(const spira::LbvhPending *level, uint32_t count, const spira::LbvhMade *made, const uint32_t *child_base,
+                                                                 const uint32_t *tri_base, const uint32_t *next_at, uint32_t n_inner, const uint32_t *sorted_idx, uint32_t *nodes,
+                                                                 uint32_t cap_slots, uint32_t *order, uint32_t n, spira::LbvhPending *next_level) {
+    const uint32_t i = blockIdx.x * kRefitLevelBlock + threadIdx.x;
+    if (i >= count) return;
+    const spira::LbvhMade m = made[i];
+    spira::lbvh_write_node(m, level[i].slot, child_base[i], tri_base[i], next_at[i], n_inner, sorted_idx, nodes, cap_slots, order, n, next_level);
+}
+#endif
+
+// Host form: triangles10 validated in full on the host before the device is touched, staged, then the same pipeline; returns when the scene is ready.
+// Device form: d_triangles10 on the caller's stream.  The stream is synchronised once for the check kernel's status and bounds and once per level of the new
+// tree (the level's counts); after the last of these the remaining work is enqueued and the call returns.  Whatever refuses, refuses before the handle's
+// node array, records, frame packets or level fields are touched.
+template <class T>
+int scene_rebuild_impl(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+    if (int rc = check_handle<T>(h)) return rc;
+    if (h->multi) return fail(SPIRA_E_UNSUPPORTED, "spira_scene_rebuild_* does not take a handle made by spira_scene_create_multi_*");
+    SceneStore &s = h->store;
+    const T *given = device_form ? d_triangles10 : triangles10;
+    if (!given) return fail(SPIRA_E_INVALID, device_form ? "d_triangles10 is NULL" : "triangles10 is NULL");
+    if (!s.nt) return fail(SPIRA_E_INVALID, "the scene was created without triangles: the counts of a handle are fixed");
+    const uint32_t n = s.nt;
+    const bool use_bvh = n > SPIRA_LDS_TRIANGLES;
+    bool mod_t = s.moderate_t;
+    if (!device_form) {
+        const char *msg = nullptr;
+        if (int rc = spira::triangles_check<T>(triangles10, n, s.nm, &msg)) return fail(rc, msg);
+        const double zero[3] = {0, 0, 0};
+        uint32_t st = 0;
+        for (uint32_t i = 0; i < n; ++i) st |= spira::refit_check_triangle<T>(triangles10 + 10 * (size_t)i, s.nm, zero, 1.0, false);
+        if (st & (spira::kRefitNonFinite | spira::kRefitMaterial)) return fail(SPIRA_E_INVALID, "triangle with a non-finite vertex or a material index out of range");
+        mod_t = !(st & spira::kRefitImmoderate);
+    }
+    if (use_bvh && (s.bvh_prec != (int)sizeof(T) || s.bvh_n != n || !s.bvh_nodes.p || !s.bvh_tris.p)) return fail(SPIRA_E_LIMIT, "internal: the handle has no tree to replace");
+    Session sess;
+    if (int rc = Session::open(sess, device_form, user_stream)) return rc;
+    Ctx &c = *sess.cp;
+    const hipStream_t st = sess.st;
+    auto bail = [&](int rc) { (void)mark_done(c, st); return rc; };      // (scratch kernels may still be running: the next call is ordered after them)
+    for (void *q : c.lbvh_retired) (void)hipFree(q);
+    c.lbvh_retired.clear();
+    if (int rc = c.lbvh_small.ensure(sizeof(LbvhSmall))) return rc;
+    if (!c.h_lbvh) HIP_TRY(hipHostMalloc((void **)&c.h_lbvh, sizeof(LbvhSmall), hipHostMallocDefault));
+    LbvhSmall *small = (LbvhSmall *)c.lbvh_small.p;
+    LbvhWs w{};
+    const T *src = given;
+    if (use_bvh) {
+        if (int rc = lbvh_carve(c, n, w)) return rc;
+        if (!device_form) {
+            if (int rc = s.refit_stage.ensure((size_t)n * 10 * sizeof(T))) return rc;
+            HIP_TRY(hipMemcpyAsync(s.refit_stage.p, triangles10, (size_t)n * 10 * sizeof(T), hipMemcpyHostToDevice, st));
+            src = (const T *)s.refit_stage.p;
+        }
+    }
+    const dim3 tri_grid((n + kRefitBlock - 1) / kRefitBlock), tri_block(kRefitBlock);
+    if (device_form || use_bvh) {
+        HIP_TRY(hipMemsetAsync(small, 0, sizeof(LbvhSmall), st));
+        hipLaunchKernelGGL((k_lbvh_check<T>), tri_grid, tri_block, 0, st, src, n, s.nm, small);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c.h_lbvh, small, sizeof(LbvhSmall), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t status = c.h_lbvh->status;
+        if (status & spira::kRefitNonFinite) return bail(fail(SPIRA_E_INVALID, "triangle with a non-finite vertex"));
+        if (status & spira::kRefitMaterial) return bail(fail(SPIRA_E_INVALID, "triangle material index out of range"));
+        mod_t = !(status & spira::kRefitImmoderate);
+    }
+    if (!use_bvh) {          // an LDS-resident mesh has no tree: its rebuild is the array
+        spira::SceneGlobal<T> g;
+        scene_pointers<T>(s, g);
+        HIP_TRY(hipMemcpyAsync((void *)g.triangles10, given, (size_t)n * 10 * sizeof(T), device_form ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        s.moderate_t = mod_t; s.moderate = s.moderate_s && mod_t;
+        return sess.close();
+    }
+    // ---- the new frame: what bvh_build would give this array
+    double lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = spira::lbvh_dec(~(uint64_t)c.h_lbvh->nlo[k]); hi[k] = spira::lbvh_dec((uint64_t)c.h_lbvh->hi[k]); }
+    RefitFrame f{};
+    spira::lbvh_frame<T>(lo, hi, f.centre, f.scale);
+    f.pad = spira::refit_pad<T>(f.centre, f.scale);
+    if (!(f.pad < 1e12)) return bail(fail(SPIRA_E_LIMIT, "the mesh is too far from the origin for its size: its boxes cannot be padded in Float32"));
+    const uint32_t n_pad = spira::lbvh_sort_size(n);
+    hipLaunchKernelGGL((k_lbvh_keys<T>), dim3(n_pad / kRefitBlock), tri_block, 0, st, src, n, n_pad, f, w.keys, w.idx, w.leafbox);
+    HIP_TRY(hipGetLastError());
+    LbvhTopo topo;
+    if (int rc = spira_tu::lbvh_topology(c, st, n, w, topo)) return bail(rc);
+    // ---- the last things that can fail: the handle's own allocations (a node array that has to grow is allocated BEFORE the old one is let go)
+    if (int rc = s.refit_tbox.ensure((size_t)n * sizeof(spira::RefitBox))) return bail(rc);
+    if (int rc = s.refit_nbox.ensure((size_t)topo.n_slots * sizeof(spira::RefitBox))) return bail(rc);
+    const size_t nodes_b = (size_t)topo.n_slots * spira::kLbvhNodeDwords * sizeof(uint32_t);
+    if (nodes_b + 128 > s.bvh_nodes.cap) {          // (+ one record of padding, as scene_upload leaves)
+        void *np = nullptr;
+        const hipError_t e = hipMalloc(&np, nodes_b + 128);
+        if (e != hipSuccess) return bail(fail(SPIRA_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)));
+        (void)hipFree(s.bvh_nodes.p);               // (waits for whatever still walks the old tree)
+        s.bvh_nodes.p = np; s.bvh_nodes.cap = nodes_b + 128;
+    }
+    // ---- commit: topology, triangle order and frame move in, the refit passes write every record and every box
+    spira::RefitPack4<T> *frame_packets = (spira::RefitPack4<T> *)s.bvh_tris.p;
+    spira::RefitBox *tbox = (spira::RefitBox *)s.refit_tbox.p, *nbox = (spira::RefitBox *)s.refit_nbox.p;
+    HIP_TRY(hipMemcpyAsync(s.bvh_nodes.p, c.lbvh_nodes.p, nodes_b, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL((k_lbvh_commit<T>), tri_grid, tri_block, 0, st, (const uint32_t *)w.order, n, f, frame_packets);
+    hipLaunchKernelGGL((k_refit_tris<T>), tri_grid, tri_block, 0, st, src, n, f, frame_packets + 3, (spira::RefitPack4<float> *)s.bvh_tris32.p, tbox);
+    for (int l = topo.depth - 1; l >= 0; --l) {
+        const uint32_t first = topo.level_first[(size_t)l], end = topo.level_first[(size_t)l + 1];
+        hipLaunchKernelGGL((k_refit_level<T>), dim3((end - first + kRefitLevelBlock - 1) / kRefitLevelBlock), dim3(kRefitLevelBlock), 0, st, (uint4 *)s.bvh_nodes.p, first, end,
+                           topo.n_slots, (const spira::RefitBox *)tbox, n, nbox, f, frame_packets);
+    }
+    s.bvh_slots = topo.n_slots; s.bvh_depth = topo.depth;
+    for (int k = 0; k < 3; ++k) s.bvh_centre[k] = f.centre[k];
+    s.bvh_scale = f.scale;
+    s.bvh_level_first = topo.level_first;
+    s.moderate_t = mod_t; s.moderate = s.moderate_s && mod_t;
+    return sess.close();
+}
+
+// scene_rebuild_impl<T> of whichever translation unit holds the kernels of T
+template <class T>
+int scene_rebuild_entry(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4) return spira_tu::scene_rebuild_impl_f32(h, triangles10, d_triangles10, device_form, user_stream);
+    else
+#endif
+        return scene_rebuild_impl<T>(h, triangles10, d_triangles10, device_form, user_stream);
+}
+
 // ---- the a-trous denoiser (spira_denoise_*; spira_denoise.h): prepare, then one launch per iteration between the context's two record buffers, the last
 // one writing the outputs.  The device form enqueues and returns; it allocates only when a workspace has to grow (a first call at a size).
 template <class T>
@@ -2066,6 +2421,77 @@ int render_multi_impl(const spira_scene *mh, const T *spheres5, const T *materia
 
 }  // namespace
 
+#if !defined(SPIRA_TU_F32) && !defined(SPIRA_TU_F64MESH)
+// The part of a rebuild that does not read T: the sort of the (key, index) pairs (a bitonic network on the pairs: equal keys end up in index order, whatever
+// the scheduling), the radix tree, its boxes, and the collapse to 8-wide slots in the context's node scratch.  w.keys / w.idx / w.leafbox are filled; on return
+// c.lbvh_nodes holds out.n_slots slots without boxes and w.order the triangle order.  ONE synchronisation of `st` per level (the level's three counts);
+// refuses (SPIRA_E_LIMIT) a tree of kBvhStack - 2 levels or more and more than 2^24 slots, having written scratch only.
+int spira_tu::lbvh_topology(Ctx &c, hipStream_t st, uint32_t n, const LbvhWs &w, LbvhTopo &out) {
+    if (n < 2 || n > spira::kBvhMaxTris) return fail(SPIRA_E_LIMIT, "internal: a rebuild needs 2 .. 2^24 triangles");
+    const uint32_t n_pad = spira::lbvh_sort_size(n);
+    spira::lbvh_sort_schedule(
+        n_pad, [&](uint32_t k_first, uint32_t k_last) { hipLaunchKernelGGL(k_lbvh_sort_tile, dim3(n_pad / spira::kLbvhSortTile), dim3(spira::kLbvhSortTile), 0, st, w.keys, w.idx, k_first, k_last); },
+        [&](uint32_t j, uint32_t k) { hipLaunchKernelGGL(k_lbvh_sort_wide, dim3(n_pad / kRefitBlock), dim3(kRefitBlock), 0, st, w.keys, w.idx, n_pad, j, k); });
+    HIP_TRY(hipGetLastError());
+    const uint64_t *keys = w.keys;
+    const uint32_t *sorted_idx = w.idx;
+    const uint32_t n_inner = n - 1;
+    const dim3 blk(kRefitBlock);
+    hipLaunchKernelGGL(k_lbvh_radix, dim3((n_inner + kRefitBlock - 1) / kRefitBlock), blk, 0, st, keys, n, w.left, w.right, w.parent, w.counter, w.pending[0]);
+    hipLaunchKernelGGL(k_lbvh_boxes, dim3((n + kRefitBlock - 1) / kRefitBlock), blk, 0, st, n, sorted_idx, (const spira::RefitBox *)w.leafbox, (const int32_t *)w.left,
+                       (const int32_t *)w.right, (const int32_t *)w.parent, w.counter, w.bbox);
+    HIP_TRY(hipGetLastError());
+    // the node scratch: n slots to begin with (a host build of n triangles has about n / 2), grown with its contents when a level needs more
+    auto reserve = [&](uint32_t need_slots, uint32_t live_slots) -> int {
+        const size_t need = (size_t)need_slots * spira::kLbvhNodeDwords * 4 + 128;
+        if (need <= c.lbvh_nodes.cap) return 0;
+        const size_t cap = std::max(need, 2 * c.lbvh_nodes.cap);
+        void *np = nullptr;
+        const hipError_t e = hipMalloc(&np, cap);
+        if (e != hipSuccess) return fail(SPIRA_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        if (c.lbvh_nodes.p) {
+            if (live_slots) {
+                const hipError_t e2 = hipMemcpyAsync(np, c.lbvh_nodes.p, (size_t)live_slots * spira::kLbvhNodeDwords * 4, hipMemcpyDeviceToDevice, st);
+                if (e2 != hipSuccess) { (void)hipFree(np); return fail(SPIRA_E_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e2)); }
+            }
+            c.lbvh_retired.push_back(c.lbvh_nodes.p);      // (the copy may not have run yet: freed by the next rebuild)
+        }
+        c.lbvh_nodes.p = np; c.lbvh_nodes.cap = cap;
+        return 0;
+    };
+    if (int rc = reserve(n, 0)) return rc;
+    LbvhSmall *small = (LbvhSmall *)c.lbvh_small.p;
+    uint32_t level_n = 1, slots = 1, n_order = 0;
+    int depth = 0, cur = 0;
+    out.level_first.assign(1, 0u);
+    while (level_n) {
+        ++depth;
+        if (depth >= spira::kLbvhMaxDepth) return fail(SPIRA_E_LIMIT, "rebuild refused: the tree is too deep for the walk's stack");
+        out.level_first.push_back(slots);          // the next level starts with the first block this level hands out (the last level hands out none: n_slots)
+        const dim3 lgrid((level_n + kRefitLevelBlock - 1) / kRefitLevelBlock), lblk(kRefitLevelBlock);
+        hipLaunchKernelGGL(k_lbvh_make, lgrid, lblk, 0, st, (const spira::LbvhPending *)w.pending[cur], level_n, (const int32_t *)w.left, (const int32_t *)w.right,
+                           (const spira::RefitBox *)w.bbox, n_inner, w.made);
+        hipLaunchKernelGGL(k_lbvh_scan, dim3(1), dim3(kLbvhScanBlock), 0, st, (const spira::LbvhMade *)w.made, level_n, slots, n_order, w.child_base, w.tri_base, w.next_at,
+                           small->totals);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c.h_lbvh->totals, small->totals, sizeof small->totals, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t new_slots = c.h_lbvh->totals[0], new_order = c.h_lbvh->totals[1], n_next = c.h_lbvh->totals[2];
+        if (new_slots > spira::kLbvhMaxSlots) return fail(SPIRA_E_LIMIT, "rebuild refused: more than 2^24 node slots");
+        if (new_slots < slots || new_order < n_order || new_order > n || n_next > n_inner || (n_next == 0) != (new_slots == slots))
+            return fail(SPIRA_E_LIMIT, "internal: inconsistent level counts in a rebuild");
+        if (int rc = reserve(new_slots, slots)) return rc;
+        hipLaunchKernelGGL(k_lbvh_write, lgrid, lblk, 0, st, (const spira::LbvhPending *)w.pending[cur], level_n, (const spira::LbvhMade *)w.made, (const uint32_t *)w.child_base,
+                           (const uint32_t *)w.tri_base, (const uint32_t *)w.next_at, n_inner, sorted_idx, (uint32_t *)c.lbvh_nodes.p, new_slots, w.order, n, w.pending[cur ^ 1]);
+        HIP_TRY(hipGetLastError());
+        slots = new_slots; n_order = new_order; level_n = n_next; cur ^= 1;
+    }
+    if (n_order != n) return fail(SPIRA_E_LIMIT, "internal: a rebuild lost triangles");
+    out.n_slots = slots; out.depth = depth;
+    return 0;
+}
+#endif
+
 #ifdef SPIRA_TU_F64MESH
 int spira_tu::launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec) {
     if (a.mesh_mode == 1) return launch_path_mode<double, true, 1>(R, grid, lds, st, a, spec);
@@ -2093,6 +2519,9 @@ int spira_tu::features_impl_f32(const spira_scene *h, const float *spheres5, con
 }
 int spira_tu::scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
     return scene_update_impl<float>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
+}
+int spira_tu::scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
+    return scene_rebuild_impl<float>(h, triangles10, d_triangles10, device_form, user_stream);
 }
 int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                                float *out_hdr, float *out_img, bool on_device, void *user_stream) {
@@ -2190,6 +2619,10 @@ void spira_shutdown(void) {
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
         c.refit_status.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
+        c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
+        for (void *q : c.lbvh_retired) (void)hipFree(q);
+        c.lbvh_retired.clear();
+        if (c.h_lbvh) { (void)hipHostFree(c.h_lbvh); c.h_lbvh = nullptr; }
         for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
         c.ev_pool.clear();
         for (hipEvent_t e : c.ev_mid) (void)hipEventDestroy(e);
@@ -2310,6 +2743,11 @@ int spira_scene_update_device_f32(spira_scene *scene, const float *d_triangles10
 int spira_scene_update_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) {
     return scene_update_entry<double>(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
 }
+// ---- a new triangle array for a live handle, the tree built anew on the device: a new frame, a new topology, no frame rule
+int spira_scene_rebuild_f32(spira_scene *scene, const float *triangles10) { return scene_rebuild_entry<float>(scene, triangles10, nullptr, false, nullptr); }
+int spira_scene_rebuild_f64(spira_scene *scene, const double *triangles10) { return scene_rebuild_entry<double>(scene, triangles10, nullptr, false, nullptr); }
+int spira_scene_rebuild_device_f32(spira_scene *scene, const float *d_triangles10, void *stream) { return scene_rebuild_entry<float>(scene, nullptr, d_triangles10, true, stream); }
+int spira_scene_rebuild_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) { return scene_rebuild_entry<double>(scene, nullptr, d_triangles10, true, stream); }
 int spira_render_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, float *out_hdr, float *out_img) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
     return render_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, out_hdr, out_img, false, nullptr);

@@ -19,7 +19,7 @@ using Colors
 
 export Scene, Camera, Ray, Sphere, Material, Point3, Vec3, Color,
        render_hybrid_gpu, render_with_cpu, render, render_multi, create_scene, prepare_scene_data,
-       SceneHandle, destroy!, update!, save_png, save_exr
+       SceneHandle, destroy!, update!, rebuild!, save_png, save_exr
 
 const libspira = get(ENV, "SPIRA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libspira_hip.so"))
 
@@ -197,6 +197,30 @@ function update!(h::SceneHandle, d_triangles::Ptr{Float32}; stream::Ptr{Cvoid}=C
     rc = ccall((:spira_scene_update_device_f32, libspira), Cint,
                (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}),
                h.ptr, d_triangles, stream)
+    rc == 0 || spira_error(rc)
+    return h
+end
+
+# A new triangle array for a live handle, the mesh's tree built anew on the device (spira_scene_rebuild_*): a new frame and a new topology, so the mesh may
+# be anywhere and of any size — no frame rule.  Host arrays (returns when the scene is ready) or a device pointer read on `stream` (synchronises the stream
+# once for the check and once per level of the new tree, then enqueues the rest).  A refused rebuild leaves the handle rendering what it rendered before.
+function rebuild!(h::SceneHandle, triangles::Vector{Float32})
+    rc = ccall((:spira_scene_rebuild_f32, libspira), Cint, (Ptr{Cvoid}, Ptr{Float32}), h.ptr, triangles)
+    rc == 0 || spira_error(rc)
+    return h
+end
+function rebuild!(h::SceneHandle, triangles::Vector{Float64})          # a handle created in Float64 through the C ABI
+    rc = ccall((:spira_scene_rebuild_f64, libspira), Cint, (Ptr{Cvoid}, Ptr{Float64}), h.ptr, triangles)
+    rc == 0 || spira_error(rc)
+    return h
+end
+function rebuild!(h::SceneHandle, d_triangles::Ptr{Float32}; stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_scene_rebuild_device_f32, libspira), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Cvoid}), h.ptr, d_triangles, stream)
+    rc == 0 || spira_error(rc)
+    return h
+end
+function rebuild!(h::SceneHandle, d_triangles::Ptr{Float64}; stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_scene_rebuild_device_f64, libspira), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), h.ptr, d_triangles, stream)
     rc == 0 || spira_error(rc)
     return h
 end

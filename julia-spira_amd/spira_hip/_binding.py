@@ -39,6 +39,7 @@ EXPORTS = [
     "spira_render_features_scene_device_f32", "spira_render_features_scene_device_f64",
     "spira_denoise_f32", "spira_denoise_f64", "spira_denoise_device_f32", "spira_denoise_device_f64",
     "spira_scene_update_f32", "spira_scene_update_f64", "spira_scene_update_device_f32", "spira_scene_update_device_f64",
+    "spira_scene_rebuild_f32", "spira_scene_rebuild_f64", "spira_scene_rebuild_device_f32", "spira_scene_rebuild_device_f64",
 ]
 
 
@@ -272,6 +273,32 @@ class Scene:
             ptr = int(triangles or 0)
         sp = getattr(stream, "cuda_stream", stream)
         fn = lib().spira_scene_update_device_f32 if self.prec == "f32" else lib().spira_scene_update_device_f64
+        _check(fn(self._h, C.c_void_p(ptr or None), C.c_void_p(sp or None)))
+
+    def rebuild(self, triangles10):
+        """spira_scene_rebuild_*: a new triangle array (host, n_triangles x 10 as at creation) and the mesh's tree built anew on the device — a new frame and a
+        new topology, so the mesh may be anywhere and of any size (no frame rule).  A refused rebuild leaves the handle as it was.  Returns when the scene is ready."""
+        npdt, _ = _dt(self.prec)
+        a, ap = _arr(triangles10, npdt)
+        if a is not None and a.size != self.counts[2] * 10:
+            raise ValueError("rebuild: an array of %d values where the handle holds %d x 10" % (a.size, self.counts[2]))
+        fn = lib().spira_scene_rebuild_f32 if self.prec == "f32" else lib().spira_scene_rebuild_f64
+        _check(fn(self._h, ap))
+
+    def rebuild_device(self, triangles, stream=None):
+        """spira_scene_rebuild_device_*: the same from DEVICE memory — a contiguous torch tensor of the handle's precision and n_triangles x 10 values, or an
+        integer device address — read on `stream` (a torch stream, an integer hipStream_t, None = the null stream).  Synchronises the stream once for the check
+        kernel's status and bounds and once per level of the new tree, then enqueues the rest and returns; the array must stay alive until that work has run."""
+        if hasattr(triangles, "data_ptr"):
+            import torch
+            want = torch.float32 if self.prec == "f32" else torch.float64
+            if triangles.dtype != want or not triangles.is_contiguous() or not triangles.is_cuda or triangles.numel() != self.counts[2] * 10:
+                raise ValueError("rebuild_device: a contiguous device tensor of %d x 10 %s values is needed" % (self.counts[2], self.prec))
+            ptr = triangles.data_ptr()
+        else:
+            ptr = int(triangles or 0)
+        sp = getattr(stream, "cuda_stream", stream)
+        fn = lib().spira_scene_rebuild_device_f32 if self.prec == "f32" else lib().spira_scene_rebuild_device_f64
         _check(fn(self._h, C.c_void_p(ptr or None), C.c_void_p(sp or None)))
 
     def destroy(self):
