@@ -2562,6 +2562,55 @@ extern "C" int spira_debug_mesh_stats(unsigned long long *out32, int reset) {
 }
 #endif
 
+// Test support, always compiled but outside the ABI (not in include/spira_hip.h; tests/test_gpu_tree_bytes.py finds it by name): a single-device handle's
+// tree as it lies on the device, to be compared byte for byte with the host twin of tests/native/tree_twin.h.  `what`:
+//   0  summary: uint32 precision (4 / 8), n, bvh_slots, bvh_depth; double bvh_centre[3], bvh_scale; uint32 level_first[0 .. depth]
+//   1  the node array: bvh_slots * 20 dwords
+//   2  the three frame packets and the triangle records: (3 + 3 n) packets of four T
+//   3  the Float32 screening records, 3 n packets of four floats (0 bytes where the store has none)
+// Takes the context's lock and waits for the device to be idle — so it comes after a device-form update or rebuild on whatever stream — then copies.
+// *need_bytes is written whenever the handle is accepted; nothing is copied unless cap_bytes suffices (SPIRA_E_INVALID).  Reads only.
+int spira_debug_scene_tree(const spira_scene *scene, uint32_t what, void *out, uint64_t cap_bytes, uint64_t *need_bytes) {
+    if (need_bytes) *need_bytes = 0;
+    if (!scene || scene->magic != kSceneMagic) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
+    if (!need_bytes) return fail(SPIRA_E_INVALID, "need_bytes is NULL");
+    if (what > 3u) return fail(SPIRA_E_INVALID, "what: 0 summary, 1 nodes, 2 frame packets and triangle records, 3 screening records");
+    if (scene->multi) return fail(SPIRA_E_UNSUPPORTED, "spira_debug_scene_tree does not take a handle made by spira_scene_create_multi_*");
+    if (scene->device != tl_device) return fail(SPIRA_E_INVALID, "scene handle belongs to another device (spira_set_device)");
+    const SceneStore &s = scene->store;
+    if (s.nt <= SPIRA_LDS_TRIANGLES) return fail(SPIRA_E_INVALID, "the handle's mesh has no tree (at most SPIRA_LDS_TRIANGLES triangles)");
+    const size_t depth = (size_t)s.bvh_depth;
+    if (s.bvh_prec != scene->prec || s.bvh_n != s.nt || s.bvh_depth < 1 || s.bvh_level_first.size() != depth + 1 || !s.bvh_nodes.p || !s.bvh_tris.p)
+        return fail(SPIRA_E_LIMIT, "internal: the handle's tree has no consistent level table");
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(cp->mu);
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t packet = 4 * (size_t)scene->prec;
+    if (what == 0u) {
+        const uint32_t head[4] = {(uint32_t)scene->prec, s.nt, s.bvh_slots, (uint32_t)s.bvh_depth};
+        const double fr[4] = {s.bvh_centre[0], s.bvh_centre[1], s.bvh_centre[2], s.bvh_scale};
+        const size_t need = sizeof head + sizeof fr + (depth + 1) * sizeof(uint32_t);
+        *need_bytes = need;
+        if (!out || cap_bytes < need) return fail(SPIRA_E_INVALID, "out is NULL or cap_bytes is too small (see *need_bytes)");
+        char *o = (char *)out;
+        std::memcpy(o, head, sizeof head); std::memcpy(o + sizeof head, fr, sizeof fr);
+        std::memcpy(o + sizeof head + sizeof fr, s.bvh_level_first.data(), (depth + 1) * sizeof(uint32_t));
+        return 0;
+    }
+    const void *src = what == 1u ? s.bvh_nodes.p : what == 2u ? s.bvh_tris.p : s.bvh_tris32.p;
+    const size_t need = what == 1u ? (size_t)s.bvh_slots * spira::kLbvhNodeDwords * sizeof(uint32_t)
+                      : what == 2u ? (3 + 3 * (size_t)s.nt) * packet
+                                   : (s.bvh_tris32.p ? 3 * (size_t)s.nt * 4 * sizeof(float) : 0);
+    *need_bytes = need;
+    if (need == 0) return 0;
+    if (!out || cap_bytes < need) return fail(SPIRA_E_INVALID, "out is NULL or cap_bytes is too small (see *need_bytes)");
+    const DevBuf &b = what == 1u ? s.bvh_nodes : what == 2u ? s.bvh_tris : s.bvh_tris32;
+    if (need > b.cap) return fail(SPIRA_E_LIMIT, "internal: the handle's buffer is smaller than its tree");
+    HIP_TRY(hipMemcpy(out, src, need, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int spira_get_counters(spira_counters *out) {
     if (!out) return fail(SPIRA_E_INVALID, "out is NULL");
     Ctx *cp = nullptr;

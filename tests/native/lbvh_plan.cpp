@@ -1,5 +1,5 @@
 // lbvh_plan.cpp — host-only harness built with -fsanitize=address,undefined (tests/test_rebuild_cpu.py), in the manner of refit_plan.cpp: the whole pipeline
-// of spira_scene_rebuild_* run serially through the very functions the kernels call (spira_lbvh.h: frame, Morton keys, radix tree, collapse; spira_refit.h:
+// of spira_scene_rebuild_* (host_rebuild of tree_twin.h) run serially through the very functions the kernels call (spira_lbvh.h: frame, Morton keys, radix tree, collapse; spira_refit.h:
 // records and boxes), with std::stable_sort in the place of the device's radix sort.  Float32 and Float64 on a 1 280-triangle icosphere, a 900-triangle
 // soup, 33 triangles (the smallest mesh that gets a tree), 200 copies of one triangle (all keys equal) and a flat 512-triangle grid (one axis without extent):
 //   coverage     every original index once in the triangle order; every triangle reached from the root exactly once
@@ -21,14 +21,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../julia-spira_amd/csrc/spira_bvh.h"
-#include "../../julia-spira_amd/csrc/spira_refit.h"
-#include "../../julia-spira_amd/csrc/spira_lbvh.h"
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { if (g_fail < 50) std::fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
-
-using spira::kBvhNodeDwords;
+#include "tree_twin.h"      // Handle, host_build, host_rebuild (the twins, shared with tree_twin_dump.cpp), CHECK
 
 // ---- meshes (double; converted to T per run).  icosphere and soup are refit_plan.cpp's.
 static std::vector<double> icosphere(int level) {
@@ -89,176 +82,6 @@ static std::vector<double> flat_grid(int q) {          // q x q quads, two trian
             out.insert(out.end(), a, a + 10); out.insert(out.end(), b, b + 10);
         }
     return out;
-}
-
-// What spira_scene_rebuild_* replaces in a handle.
-template <class T> struct Handle {
-    std::vector<uint32_t> nodes;
-    std::vector<spira::RefitPack4<T>> tris;
-    std::vector<spira::RefitPack4<float>> tris32;
-    spira::RefitPack4<T> frame[3];
-    std::vector<uint32_t> level_first;
-    uint32_t n_slots = 0, n = 0;
-    int depth = 0;
-    double centre[3] = {0, 0, 0}, scale = 1;
-};
-template <class T> static bool same(const Handle<T> &a, const Handle<T> &b) {
-    return a.nodes == b.nodes && a.tris.size() == b.tris.size() && std::memcmp(a.tris.data(), b.tris.data(), a.tris.size() * sizeof(a.tris[0])) == 0 &&
-           std::memcmp(a.frame, b.frame, sizeof a.frame) == 0 && a.level_first == b.level_first && a.n_slots == b.n_slots && a.depth == b.depth &&
-           std::memcmp(a.centre, b.centre, sizeof a.centre) == 0 && a.scale == b.scale;
-}
-
-template <class T>
-static bool host_build(Handle<T> &h, const std::vector<T> &tri10, bool screen) {
-    spira::RawVec<uint32_t> nodes; spira::RawVec<spira::HostPack4<T>> tris; spira::RawVec<spira::HostPack4<float>> t32; spira::BvhFrame<T> fr{};
-    h.n = (uint32_t)(tri10.size() / 10);
-    if (!spira::bvh_build<T>(tri10.data(), h.n, nodes, tris, fr, 1, screen ? &t32 : nullptr)) return false;
-    h.nodes.assign(nodes.begin(), nodes.end());
-    h.tris.resize(tris.size()); std::memcpy(h.tris.data(), tris.data(), tris.size() * sizeof(tris[0]));
-    h.tris32.resize(t32.size()); if (!t32.empty()) std::memcpy(h.tris32.data(), t32.data(), t32.size() * sizeof(t32[0]));
-    h.frame[0] = {fr.root_mn[0], fr.root_mn[1], fr.root_mn[2], (T)0}; h.frame[1] = {fr.root_mx[0], fr.root_mx[1], fr.root_mx[2], (T)0};
-    h.frame[2] = {fr.centre[0], fr.centre[1], fr.centre[2], fr.scale};
-    h.level_first.assign(fr.level_first, fr.level_first + fr.depth + 1);
-    h.n_slots = fr.n_slots; h.depth = fr.depth;
-    for (int k = 0; k < 3; ++k) h.centre[k] = (double)fr.centre[k];
-    h.scale = (double)fr.scale;
-    return true;
-}
-
-// The host twin of spira_scene_rebuild_*: 0, or the status bits / -4 of a refusal.  Everything up to "commit" writes locals (the device's scratch) only.
-template <class T>
-static int host_rebuild(Handle<T> &h, const std::vector<T> &tri10, uint32_t n_materials, int depth_cap) {
-    const uint32_t n = h.n;
-    const double zero[3] = {0, 0, 0};
-    // 1. check and bounds (through the integer codes the device reduces with)
-    uint32_t status = 0;
-    uint64_t nlo[3] = {0, 0, 0}, ehi[3] = {0, 0, 0};
-    for (uint32_t i = 0; i < n; ++i) {
-        status |= spira::refit_check_triangle<T>(&tri10[10 * (size_t)i], n_materials, zero, 1.0, false);
-        for (int k = 0; k < 9; ++k) {
-            const double x = (double)tri10[10 * (size_t)i + k];
-            if (!(x == x)) continue;
-            nlo[k % 3] = std::max(nlo[k % 3], ~spira::lbvh_enc(x)); ehi[k % 3] = std::max(ehi[k % 3], spira::lbvh_enc(x));
-        }
-    }
-    if (status & (spira::kRefitNonFinite | spira::kRefitMaterial)) return (int)status;
-    double lo[3], hi[3], centre[3], scale;
-    for (int k = 0; k < 3; ++k) { lo[k] = spira::lbvh_dec(~nlo[k]); hi[k] = spira::lbvh_dec(ehi[k]); }
-    spira::lbvh_frame<T>(lo, hi, centre, scale);
-    const double pad = spira::refit_pad<T>(centre, scale);
-    if (!(pad < 1e12)) return -4;
-    // 2. keys, stable sort
-    std::vector<uint64_t> key0(n), keys(n);
-    std::vector<uint32_t> sorted_idx(n);
-    std::vector<spira::RefitBox> leafbox(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        spira::RefitPack4<T> rec[3];
-        spira::refit_triangle<T>(&tri10[10 * (size_t)i], i, centre, scale, pad, rec, nullptr, leafbox[i]);
-        key0[i] = spira::lbvh_key<T>(&tri10[10 * (size_t)i], centre, scale);
-        CHECK(key0[i] < (1ull << 63));
-    }
-    std::iota(sorted_idx.begin(), sorted_idx.end(), 0u);
-    std::stable_sort(sorted_idx.begin(), sorted_idx.end(), [&](uint32_t a, uint32_t b) { return key0[a] < key0[b]; });
-    for (uint32_t j = 0; j < n; ++j) keys[j] = key0[sorted_idx[j]];
-    {   // the device's sort — the bitonic network on the padded (key, index) pairs, in the kernels' schedule of tiles and wide passes — gives that very order
-        const uint32_t n_pad = spira::lbvh_sort_size(n);
-        std::vector<uint64_t> dk(n_pad, ~0ull);
-        std::vector<uint32_t> di(n_pad, ~0u);
-        for (uint32_t i = 0; i < n; ++i) { dk[i] = key0[i]; di[i] = i; }
-        uint32_t launches = 0;
-        spira::lbvh_sort_schedule(
-            n_pad,
-            [&](uint32_t k_first, uint32_t k_last) {
-                ++launches;
-                for (uint32_t base = 0; base < n_pad; base += spira::kLbvhSortTile)
-                    for (uint32_t k = k_first; k <= k_last; k <<= 1)
-                        for (uint32_t j = spira::lbvh_tile_first_j(k); j > 0; j >>= 1)
-                            for (uint32_t t = 0; t < spira::kLbvhSortTile; ++t) spira::lbvh_bitonic_cx(&dk[base], &di[base], t, base + t, j, k);
-            },
-            [&](uint32_t j, uint32_t k) { ++launches; for (uint32_t i = 0; i < n_pad; ++i) spira::lbvh_bitonic_cx(dk.data(), di.data(), i, i, j, k); });
-        CHECK(launches >= 1);
-        for (uint32_t j = 0; j < n; ++j) CHECK(di[j] == sorted_idx[j] && dk[j] == keys[j]);
-        for (uint32_t j = n; j < n_pad; ++j) CHECK(di[j] == ~0u && dk[j] == ~0ull);
-    }
-    // 3. radix tree
-    const uint32_t n_inner = n - 1;
-    std::vector<int32_t> left(n_inner), right(n_inner), parent(2 * (size_t)n - 1, -2);
-    for (uint32_t i = 0; i < n_inner; ++i) {
-        spira::lbvh_radix_node(keys.data(), n, i, left[i], right[i]);
-        CHECK(left[i] >= 0 && (uint32_t)left[i] < 2 * n - 1 && right[i] >= 0 && (uint32_t)right[i] < 2 * n - 1 && left[i] != right[i]);
-        CHECK(parent[left[i]] == -2 && parent[right[i]] == -2);          // every node is somebody's child once
-        parent[left[i]] = (int32_t)i; parent[right[i]] = (int32_t)i;
-    }
-    CHECK(parent[0] == -2);
-    parent[0] = -1;
-    for (size_t k = 1; k < parent.size(); ++k) CHECK(parent[k] >= 0);
-    // 4. boxes, bottom-up with arrival counters (serially: the second arrival at a node is simply the later leaf)
-    std::vector<spira::RefitBox> bbox(2 * (size_t)n - 1);
-    std::vector<uint32_t> counter(n_inner, 0);
-    for (uint32_t j = 0; j < n; ++j) {
-        spira::RefitBox b = leafbox[sorted_idx[j]];
-        uint32_t cur = n_inner + j;
-        for (;;) {
-            bbox[cur] = b;
-            const int32_t p = parent[cur];
-            if (p < 0) break;
-            if (counter[p]++ == 0) break;
-            const int32_t sib = (uint32_t)left[p] == cur ? right[p] : left[p];
-            spira::lbvh_box_union(b, bbox[sib], b);
-            cur = (uint32_t)p;
-        }
-    }
-    for (uint32_t i = 0; i < n_inner; ++i) CHECK(counter[i] == 2);
-    // 5. collapse, level by level
-    std::vector<uint32_t> nodes(kBvhNodeDwords, 0xDEADBEEFu), order(n, 0xFFFFFFFFu), level_first(1, 0u);
-    std::vector<spira::LbvhPending> level(1, spira::LbvhPending{0, 0u}), next_level;
-    uint32_t slots = 1, n_order = 0;
-    int depth = 0;
-    while (!level.empty()) {
-        ++depth;
-        if (depth >= depth_cap) return -4;
-        level_first.push_back(slots);
-        std::vector<spira::LbvhMade> made(level.size());
-        std::vector<uint32_t> cb(level.size()), tb(level.size()), na(level.size());
-        uint32_t n_next = 0;
-        for (size_t i = 0; i < level.size(); ++i) {
-            spira::lbvh_make_node(level[i].bnode, left.data(), right.data(), bbox.data(), n_inner, made[i]);
-            uint32_t a, b, c;
-            spira::lbvh_node_counts(made[i], a, b, c);
-            cb[i] = a ? slots : 0u; tb[i] = n_order; na[i] = n_next;
-            slots += a; n_order += b; n_next += c;
-        }
-        if (slots > spira::kLbvhMaxSlots) return -4;
-        nodes.resize((size_t)slots * kBvhNodeDwords, 0xDEADBEEFu);
-        next_level.assign(n_next, spira::LbvhPending{-1, 0u});
-        for (size_t i = 0; i < level.size(); ++i)
-            spira::lbvh_write_node(made[i], level[i].slot, cb[i], tb[i], na[i], n_inner, sorted_idx.data(), nodes.data(), slots, order.data(), n, next_level.data());
-        level.swap(next_level);
-    }
-    CHECK(n_order == n);
-    for (uint32_t w : nodes) CHECK(w != 0xDEADBEEFu);          // every word of every slot was written: a node's or a hole's
-    // 6. commit and finish: the refit passes over the new level table
-    h.nodes = nodes; h.n_slots = slots; h.depth = depth; h.level_first = level_first;
-    for (int k = 0; k < 3; ++k) h.centre[k] = centre[k];
-    h.scale = scale;
-    h.frame[2] = {(T)centre[0], (T)centre[1], (T)centre[2], (T)scale};
-    for (uint32_t i = 0; i < n; ++i) h.tris[3 * (size_t)i].w = spira::refit_index_bits<T>(order[i]);
-    std::vector<spira::RefitBox> tbox(n), nbox(slots);
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t oi = spira::refit_index_of<T>(h.tris[3 * (size_t)i].w);
-        CHECK(oi < n);
-        if (oi >= n) return -99;
-        spira::RefitPack4<T> out[3]; spira::RefitPack4<float> o32[3];
-        spira::refit_triangle<T>(&tri10[10 * (size_t)oi], oi, centre, scale, pad, out, h.tris32.empty() ? nullptr : o32, tbox[i]);
-        std::memcpy(&h.tris[3 * (size_t)i], out, sizeof out);
-        if (!h.tris32.empty()) std::memcpy(&h.tris32[3 * (size_t)i], o32, sizeof o32);
-    }
-    for (int d = depth - 1; d >= 0; --d)
-        for (uint32_t s = level_first[d]; s < level_first[d + 1]; ++s) {
-            if (!spira::refit_node(&h.nodes[(size_t)s * kBvhNodeDwords], tbox.data(), n, nbox.data(), slots, nbox[s])) continue;
-            if (s == 0) spira::refit_root<T>(nbox[0], centre, scale, h.frame[0], h.frame[1]);
-        }
-    return 0;
 }
 
 static bool child_empty(const uint32_t *w, int s) { return spira::refit_child_byte(w, 0, s) == 255u && spira::refit_child_byte(w, 3, s) == 0u; }

@@ -19,13 +19,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../julia-spira_amd/csrc/spira_bvh.h"
-#include "../../julia-spira_amd/csrc/spira_refit.h"
-
-static int g_fail = 0;
-#define CHECK(c) do { if (!(c)) { if (g_fail < 50) std::fprintf(stderr, "CHECK failed %s:%d: %s\n", __FILE__, __LINE__, #c); ++g_fail; } } while (0)
-
-using spira::kBvhNodeDwords;
+#include "tree_twin.h"      // Tree, build, host_refit, check_identity_bounds (the twins, shared with tree_twin_dump.cpp), CHECK
 
 // ---- meshes (double; converted to T per run)
 static std::vector<double> icosphere(int level) {
@@ -89,66 +83,6 @@ static std::vector<double> deform(const std::vector<double> &tri) {
             p[2] = c[2] + sn * x + cs * z;
         }
     return out;
-}
-
-template <class T> struct Tree {
-    spira::RawVec<uint32_t> nodes;
-    spira::RawVec<spira::HostPack4<T>> tris;
-    spira::RawVec<spira::HostPack4<float>> tris32;
-    spira::BvhFrame<T> fr{};
-    T root_mn[3], root_mx[3];
-    double centre[3], scale;
-    uint32_t n = 0;
-};
-
-static bool slot_child_empty(const uint32_t *w, int s) { return spira::refit_child_byte(w, 0, s) == 255u && spira::refit_child_byte(w, 3, s) == 0u; }
-static bool slot_is_hole(const uint32_t *w) { for (int s = 0; s < 8; ++s) if (!slot_child_empty(w, s)) return false; return true; }
-static void decode_child(const uint32_t *w, int s, double lo[3], double hi[3], double step[3]) {
-    for (int k = 0; k < 3; ++k) {
-        step[k] = std::ldexp(1.0, (int)((w[3] >> (8 * k)) & 0xFFu) - 127);
-        const double p = (double)spira::bits_float(w[k]);
-        lo[k] = p + (double)spira::refit_child_byte(w, k, s) * step[k];
-        hi[k] = p + (double)spira::refit_child_byte(w, 3 + k, s) * step[k];
-    }
-}
-
-// The host twin of spira_scene_update_*: check every triangle first (nothing is written on a refusal), then the triangle pass and one node pass per level,
-// deepest first.  Returns the status bits.
-template <class T>
-static uint32_t host_refit(Tree<T> &tr, const std::vector<T> &tri10, uint32_t n_materials) {
-    uint32_t status = 0;
-    for (uint32_t i = 0; i < tr.n; ++i) status |= spira::refit_check_triangle<T>(&tri10[10 * (size_t)i], n_materials, tr.centre, tr.scale, true);
-    if (status & (spira::kRefitNonFinite | spira::kRefitMaterial | spira::kRefitFrame)) return status;
-    const double pad = spira::refit_pad<T>(tr.centre, tr.scale);
-    std::vector<spira::RefitBox> tbox(tr.n), nbox(tr.fr.n_slots);
-    for (uint32_t i = 0; i < tr.n; ++i) {
-        const uint32_t oi = spira::refit_index_of<T>(tr.tris[3 * (size_t)i].w);
-        CHECK(oi < tr.n);
-        spira::RefitPack4<T> out[3]; spira::RefitPack4<float> o32[3];
-        spira::refit_triangle<T>(&tri10[10 * (size_t)oi], oi, tr.centre, tr.scale, pad, out, tr.tris32.empty() ? nullptr : o32, tbox[i]);
-        std::memcpy(&tr.tris[3 * (size_t)i], out, sizeof out);
-        if (!tr.tris32.empty()) std::memcpy(&tr.tris32[3 * (size_t)i], o32, sizeof o32);
-    }
-    for (int d = tr.fr.depth - 1; d >= 0; --d)
-        for (uint32_t s = tr.fr.level_first[d]; s < tr.fr.level_first[d + 1]; ++s) {
-            uint32_t *w = &tr.nodes[(size_t)s * kBvhNodeDwords];
-            if (!spira::refit_node(w, tbox.data(), tr.n, nbox.data(), tr.fr.n_slots, nbox[s])) continue;
-            if (s == 0) {
-                spira::RefitPack4<T> mn, mx;
-                spira::refit_root<T>(nbox[0], tr.centre, tr.scale, mn, mx);
-                tr.root_mn[0] = mn.x; tr.root_mn[1] = mn.y; tr.root_mn[2] = mn.z; tr.root_mx[0] = mx.x; tr.root_mx[1] = mx.y; tr.root_mx[2] = mx.z;
-            }
-        }
-    return status;
-}
-
-template <class T>
-static bool build(Tree<T> &tr, const std::vector<T> &tri10, bool screen) {
-    tr.n = (uint32_t)(tri10.size() / 10);
-    if (!spira::bvh_build<T>(tri10.data(), tr.n, tr.nodes, tr.tris, tr.fr, 1, screen ? &tr.tris32 : nullptr)) return false;
-    for (int k = 0; k < 3; ++k) { tr.root_mn[k] = tr.fr.root_mn[k]; tr.root_mx[k] = tr.fr.root_mx[k]; tr.centre[k] = (double)tr.fr.centre[k]; }
-    tr.scale = (double)tr.fr.scale;
-    return true;
 }
 
 // the levels of BvhFrame: every slot belongs to one level, children of a level-d node lie in level d + 1, the root is level 0
@@ -240,9 +174,7 @@ static void run_mesh(const char *name, const std::vector<double> &mesh_d, bool s
     const uint32_t n = built.n, n_slots = built.fr.n_slots;
     const double pad = spira::refit_pad<T>(built.centre, built.scale);
     // the builder's own pad, for the identity bound (spira_bvh.h "Padding")
-    double amax = 0;
-    for (size_t i = 0; i < A.size() / 10; ++i) for (int k = 0; k < 9; ++k) amax = std::max(amax, std::fabs((double)A[10 * i + k]));
-    const double pad_built = sizeof(T) == 4 ? 1e-4 * std::max(1.0, amax * built.scale) : 1e-4 + 1e-9 * amax * built.scale;
+    const double pad_built = builder_pad<T>(A, built.scale);
     CHECK(pad >= pad_built);
     check_tree(built, A, pad_built);                       // the harness itself: the built tree passes its own checks
 
@@ -308,27 +240,7 @@ static void run_mesh(const char *name, const std::vector<double> &mesh_d, bool s
     // ---- identity: containment, the records bit for bit, and every child bound within one grid step of the built one (+ the pad difference + one Float32 ulp)
     check_tree(ident, A, pad);
     CHECK(std::memcmp(ident.tris.data(), built.tris.data(), ident.tris.size() * sizeof(ident.tris[0])) == 0);
-    const double slack = (pad - pad_built) + std::ldexp(1.0, -23) * std::max(1.0, 1.0 + pad);
-    double worst = 0;
-    for (uint32_t s = 0; s < n_slots; ++s) {
-        const uint32_t *a = &built.nodes[(size_t)s * kBvhNodeDwords], *b = &ident.nodes[(size_t)s * kBvhNodeDwords];
-        if (slot_is_hole(a)) continue;
-        for (int c = 0; c < 8; ++c) {
-            if (slot_child_empty(a, c)) continue;
-            double lo0[3], hi0[3], st0[3], lo1[3], hi1[3], st1[3];
-            decode_child(a, c, lo0, hi0, st0); decode_child(b, c, lo1, hi1, st1);
-            for (int k = 0; k < 3; ++k) {
-                const double step = std::max(st0[k], st1[k]);
-                CHECK(std::fabs(lo1[k] - lo0[k]) <= step + slack && std::fabs(hi1[k] - hi0[k]) <= step + slack);
-                worst = std::max(worst, std::max(std::fabs(lo1[k] - lo0[k]), std::fabs(hi1[k] - hi0[k])) / step);
-            }
-        }
-    }
-    for (int k = 0; k < 3; ++k) {          // the root box of the frame packets: not inside the built one, and no further out than pad difference + roundings
-        const double tol = slack / built.scale + 8 * std::fabs((double)built.root_mn[k]) * std::numeric_limits<T>::epsilon();
-        CHECK(ident.root_mn[k] <= built.root_mn[k] + (T)0 && (double)built.root_mn[k] - (double)ident.root_mn[k] <= tol);
-        CHECK(ident.root_mx[k] >= built.root_mx[k] && (double)ident.root_mx[k] - (double)built.root_mx[k] <= tol);
-    }
+    const double worst = check_identity_bounds<T>(built.nodes.data(), ident.nodes.data(), n_slots, built.root_mn, built.root_mx, ident.root_mn, ident.root_mx, built.scale, pad, pad_built);
     std::printf("%s %s: identity refit moves a child bound by at most %.3f grid steps\n", name, sizeof(T) == 4 ? "f32" : "f64", worst);
 
     // ---- refusals: the shared check says no and nothing is written
