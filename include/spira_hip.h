@@ -307,6 +307,56 @@ int spira_render_scene_device_f32(const spira_scene *scene, const float camera12
 int spira_render_scene_device_f64(const spira_scene *scene, const double camera12[12], const spira_params *params,
                                   double *d_out_hdr, double *d_out_img, void *stream);
 
+/* ---- ray queries on a scene handle: closest hit and occlusion for the CALLER'S rays (line of sight, range finding, visibility, picking) ----
+ * Replaces hit(world, ray, t_min, t_max) of examples/julia-raytracer.jl:242-258 called once per ray: the same scan — spheres [0..) then triangles [0..)
+ * in the caller's order, accepted when !(t < t_min || t > closest) with closest starting at t_max — answered for a whole ray list in one launch, a mesh of
+ * more than SPIRA_LDS_TRIANGLES triangles through the handle's tree, which only prunes: prim and t are bit for bit the scan's.
+ * rays8: n_rays x [ox oy oz t_min dx dy dz t_max].  Preparation per ray, in the call's precision T, nothing fused: s = (dx dx + dy dy) + dz dz,
+ * d = (dx, dy, dz) / sqrt(s) — the library normalises (the walk assumes unit directions) and does not trust the caller; t, t_min and t_max are distances
+ * along the UNIT direction.
+ * Closest hit: the minimal t wins, ties go to the later object, a hit at exactly t_max counts.  out_prim: the object index, spheres first; out_t: that t;
+ * out_normal (n_rays x 3, interleaved): the geometric normal of spira_render_features_* (outward normalize(pos - centre) for a sphere, the unflipped unit
+ * normalize(cross(e1, e2)) for a triangle) at pos = o + d t.  A miss gives prim SPIRA_RAY_MISS, t = the ray's t_max copied, normal 0.
+ * Invalid rays are ordinary input that the entry classifies — prim SPIRA_RAY_INVALID, t 0, normal 0; occlusion output 255 — they never fault and never
+ * disturb their neighbours.  A ray is invalid when any of its eight values is NaN; an origin or direction component is infinite; s is not finite or is
+ * below the smallest normal number of T; t_min < 0; t_max < t_min; or the origin rule is broken.
+ * Origin rule (scenes WITH a tree only): |(o_k - centre_k) * scale| <= 64 on every axis, in T, with the tree's normalised frame (centre, power-of-two
+ * scale; the mesh lies within about +-0.5 of it) — i.e. an origin within about 64 mesh sizes of the mesh.  Why: the walk starts from the point where the
+ * ray enters the mesh's box, o + d te, computed in T, whose error is a few ulps of max(|o_k|, te); in normalised units that is in Float32 about
+ * 3 (amax_n + 64) 2^-24 = 1.2e-5 + 1.8e-7 amax_n (amax_n: the largest coordinate of the mesh) against the builder's box padding of 1e-4 max(1, amax_n),
+ * a margin of 8 or more.  A refitted tree (spira_scene_update_*) pads with max_k |centre_k| + 1 / scale in place of amax, which is never smaller for a mesh
+ * inside its frame: the fresh build's margin is the smaller one and 64 covers both.  In Float64 (3 (amax_n + 64) 2^-53 against 1e-4 + 1e-9 amax_n) the bound
+ * is far from binding and is kept for one contract.  A ray from further away: move its origin along the ray.  Scenes without a tree have no such rule.
+ * Occlusion: out_hit[i] is 1 exactly where the closest-hit answer for the same ray would be prim >= 0, 0 otherwise, 255 for an invalid ray; the kernel
+ * stops at the first accepted hit.
+ * flags: 0, the library's organisation for scenes with a tree: persistent waves that each own a contiguous range of the ray list and refill their free
+ * lanes from it while the others keep walking (a traversal session, as the renderer's); or SPIRA_CAST_INPLACE, one lane per ray walking to the end — the
+ * comparison point, as SPIRA_KERNEL_BOUNCE is for the renderer.  Both give identical bytes.  Scenes without a tree run one lane per ray either way.
+ * Errors, all decided before any device is touched: a NULL ray array, n_rays == 0, unknown flag bits, every output NULL (out_prim, out_t and out_normal may
+ * each be NULL, not all three), a NULL or destroyed handle, one of the other precision or of another device: SPIRA_E_INVALID; n_rays > SPIRA_MAX_RAYS:
+ * SPIRA_E_LIMIT.  A handle made by spira_scene_create_multi_* is served by device 0's copy, as the single-device render entries serve it.
+ * The host form copies in and out and returns when the outputs are written.  The *_device_* form takes DEVICE pointers, is asynchronous on `stream`,
+ * synchronises nothing, allocates nothing, and is ordered like every entry: a cast enqueued after a device-form update or rebuild on another stream sees
+ * the new tree.  spira_get_counters is not affected by these entries. */
+#define SPIRA_MAX_RAYS      (1u << 26)
+#define SPIRA_RAY_MISS      -1
+#define SPIRA_RAY_INVALID   -3          /* -2 is taken by spira_trace_paths */
+#define SPIRA_CAST_INPLACE  0x1u
+int spira_scene_cast_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags,
+                         int *out_prim, float *out_t, float *out_normal);
+int spira_scene_cast_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags,
+                         int *out_prim, double *out_t, double *out_normal);
+int spira_scene_cast_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags,
+                                int *d_out_prim, float *d_out_t, float *d_out_normal, void *stream);
+int spira_scene_cast_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags,
+                                int *d_out_prim, double *d_out_t, double *d_out_normal, void *stream);
+int spira_scene_occluded_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit);
+int spira_scene_occluded_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit);
+int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags,
+                                    uint8_t *d_out_hit, void *stream);
+int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags,
+                                    uint8_t *d_out_hit, void *stream);
+
 /* ---- progressive accumulation (checkpoint / resume / adaptive sampling) ----
  * The contract the reference's kernel was designed for and no host code uses: `current_sample_index`,
  * persisted `rng_states`, `output_hdr_image[p] += L` (src/spira_path_trace_kernel.metal:143-145, :252-268).

@@ -42,6 +42,7 @@
 #include "spira_denoise.h"
 #include "spira_refit.h"
 #include "spira_lbvh.h"
+#include "spira_query.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -74,6 +75,8 @@ int denoise_impl_f32(const float *color, const float *variance, const float *alb
                      float *out_hdr, float *out_img, bool on_device, void *user_stream);
 int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
 int scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
+int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
+                  bool any, bool on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -153,6 +156,7 @@ struct Ctx {
     DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
+    DevBuf cast_io;                               // spira_scene_cast_* / spira_scene_occluded_*: the host form's staged rays and outputs
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
     uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
     DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
@@ -1481,6 +1485,76 @@ int features_entry(const spira_scene *h, const T *spheres5, const T *materials8,
         return features_impl<T>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
 }
 
+// ======================================================================= spira_scene_cast_* / spira_scene_occluded_*: the caller's rays against a handle
+// Kernels and the ray preparation: spira_query.h; launch arithmetic: spira_plan.h (make_cast_plan).  One launch.  The device form touches no workspace of
+// the context (it allocates nothing); the host form stages rays and outputs in cast_io.  The counters of the last render are left as they are.
+spira::CastKnobs read_cast_knobs() {
+    spira::CastKnobs k;
+    k.refill = env_u32("SPIRA_CAST_REFILL", SPIRA_CAST_REFILL);
+    k.waves_per_cu = env_u32("SPIRA_CAST_WAVES_PER_CU", SPIRA_CAST_WAVES_PER_CU);
+    return k;
+}
+template <class T, bool ANY>
+int launch_cast(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::CastArgs<T> &a) {
+    const dim3 block(spira::kBlock), flat(cp.grid_flat);
+    if (a.scene.n_bvh_tris && !inplace)
+        return launch_lds(spira::k_cast_session<T, ANY>, dim3(cp.grid), block, lds + (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb, st, a);
+    if (a.scene.n_bvh_tris) return launch_lds(spira::k_cast<T, true, false, ANY>, flat, block, lds, st, a);
+    if (a.scene.n_triangles) return launch_lds(spira::k_cast<T, false, true, ANY>, flat, block, lds, st, a);
+    return launch_lds(spira::k_cast<T, false, false, ANY>, flat, block, lds, st, a);
+}
+template <class T>
+int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
+              bool any, bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::cast_check(rays8 != nullptr, n_rays, flags, any ? out_hit != nullptr : (out_prim || out_t || out_normal), &msg)) return fail(rc, msg);
+    if (int rc = check_handle<T>(h)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
+
+    spira::CastArgs<T> a{};
+    scene_pointers<T>(h->store, a.scene);
+    a.scene.spd = nullptr;
+    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)c.num_cus, spira::kBlock, read_cast_knobs());
+    a.rays = rays8; a.n_rays = n_rays; a.prim = out_prim; a.t = out_t; a.normal = out_normal; a.hit = out_hit;
+    a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_rays, ray_b = 8 * n * sizeof(T), t_b = n * sizeof(T), prim_b = n * sizeof(int);
+    if (!on_device) {
+        // [rays | t | normal | prim | hit]: every block starts at a multiple of sizeof(T) or more
+        if (int rc = c.cast_io.ensure(ray_b + 4 * t_b + prim_b + n)) return rc;
+        char *base = (char *)c.cast_io.p;
+        HIP_TRY(hipMemcpyAsync(base, rays8, ray_b, hipMemcpyHostToDevice, st));
+        a.rays = (const T *)base;
+        a.t = out_t ? (T *)(base + ray_b) : nullptr;
+        a.normal = out_normal ? (T *)(base + ray_b + t_b) : nullptr;
+        a.prim = out_prim ? (int *)(base + ray_b + 4 * t_b) : nullptr;
+        a.hit = out_hit ? (uint8_t *)(base + ray_b + 4 * t_b + prim_b) : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    const bool inplace = (flags & SPIRA_CAST_INPLACE) != 0;
+    if (int rc = any ? launch_cast<T, true>(cp, inplace, lds, st, a) : launch_cast<T, false>(cp, inplace, lds, st, a)) return rc;
+    if (!on_device) {
+        if (out_t) HIP_TRY(hipMemcpyAsync(out_t, a.t, t_b, hipMemcpyDeviceToHost, st));
+        if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal, a.normal, 3 * t_b, hipMemcpyDeviceToHost, st));
+        if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, a.prim, prim_b, hipMemcpyDeviceToHost, st));
+        if (out_hit) HIP_TRY(hipMemcpyAsync(out_hit, a.hit, n, hipMemcpyDeviceToHost, st));
+    }
+    return s.close();
+}
+
+template <class T>
+int cast_entry(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
+               bool any, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::cast_impl_f32(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
+    else
+#endif
+        return cast_impl<T>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
+}
+
 // ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
 // The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
 // walk or the node format is involved: a refit rewrites boxes, and the walk only prunes with them.
@@ -2523,6 +2597,10 @@ int spira_tu::scene_update_impl_f32(spira_scene *h, const float *spheres5, const
 int spira_tu::scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
     return scene_rebuild_impl<float>(h, triangles10, d_triangles10, device_form, user_stream);
 }
+int spira_tu::cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
+                            bool any, bool on_device, void *user_stream) {
+    return cast_impl<float>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
+}
 int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                                float *out_hdr, float *out_img, bool on_device, void *user_stream) {
     return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
@@ -2561,6 +2639,41 @@ extern "C" int spira_debug_mesh_stats(unsigned long long *out32, int reset) {
     return 0;
 }
 #endif
+
+// ---- ray queries on a scene handle (spira_query.h)
+int spira_scene_cast_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal) {
+    return cast_entry<float>(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
+}
+int spira_scene_cast_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, double *out_t, double *out_normal) {
+    return cast_entry<double>(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
+}
+int spira_scene_cast_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags, int *d_out_prim, float *d_out_t, float *d_out_normal, void *stream) {
+    return cast_entry<float>(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
+}
+int spira_scene_cast_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags, int *d_out_prim, double *d_out_t, double *d_out_normal, void *stream) {
+    return cast_entry<double>(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
+}
+int spira_scene_occluded_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit) {
+    return cast_entry<float>(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
+}
+int spira_scene_occluded_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit) {
+    return cast_entry<double>(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
+}
+int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return cast_entry<float>(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
+}
+int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return cast_entry<double>(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
+}
+// Test support, outside the ABI like spira_debug_scene_tree: the launch plan a cast of n_rays would get on a device of num_cus CUs, with the knobs of the
+// environment as the entries read them.  out8: grid, wpb, waves, base, rem, refill_free, grid_flat, kCastMinRaysPerWave.  No device needed.
+int spira_debug_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t *out8) {
+    if (!out8 || n_rays == 0 || n_rays > SPIRA_MAX_RAYS) return fail(SPIRA_E_INVALID, "spira_debug_cast_plan: out8 is NULL or n_rays outside 1 .. SPIRA_MAX_RAYS");
+    const spira::CastPlan cp = spira::make_cast_plan(n_rays, num_cus, spira::kBlock, read_cast_knobs());
+    const uint32_t v[8] = {cp.grid, cp.wpb, cp.waves, cp.base, cp.rem, cp.refill_free, cp.grid_flat, spira::kCastMinRaysPerWave};
+    std::memcpy(out8, v, sizeof v);
+    return 0;
+}
 
 // Test support, always compiled but outside the ABI (not in include/spira_hip.h; tests/test_gpu_tree_bytes.py finds it by name): a single-device handle's
 // tree as it lies on the device, to be compared byte for byte with the host twin of tests/native/tree_twin.h.  `what`:
@@ -2666,7 +2779,7 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release();
+        c.refit_status.release(); c.cast_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);

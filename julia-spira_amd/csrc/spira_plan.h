@@ -359,4 +359,42 @@ inline int make_denoise_plan(const DenoiseIn &in, DenoisePlan &dp, const char **
     return 0;
 }
 
+// ---- ray queries on a scene handle (spira_scene_cast_* / spira_scene_occluded_*); kernels in spira_query.h.
+// The session kernel runs `waves` persistent waves in workgroups of wpb; wave w owns the contiguous range of base + (w < rem) rays that starts at
+// w base + min(w, rem): the ranges are disjoint, cover [0, n_rays) and differ by at most one ray, so no wave is empty unless n_rays < waves.  The number
+// of waves is what the device holds (waves_per_cu per CU) but never so many that a wave gets fewer than kCastMinRaysPerWave rays: a session lives on
+// refills, and a wave with one fill of rays would be the in-place walk with extra bookkeeping.  The one-lane-per-ray kernels stride a flat grid.
+constexpr uint32_t kCastMinRaysPerWave = 128;
+struct CastKnobs { uint32_t refill = 16, waves_per_cu = 20; };      // SPIRA_CAST_REFILL (free lanes that trigger a refill, 1 .. 64), SPIRA_CAST_WAVES_PER_CU
+struct CastPlan {
+    uint32_t n_rays = 0;
+    uint32_t grid = 0, wpb = 0, waves = 0;     // session: workgroups, waves per workgroup, grid * wpb
+    uint32_t base = 0, rem = 0;                // rays per wave and how many waves take one more
+    uint32_t refill_free = 0;
+    uint32_t grid_flat = 0;                    // one lane per ray: workgroups (the kernel strides)
+    uint32_t begin(uint32_t w) const { return w * base + std::min(w, rem); }
+    uint32_t count(uint32_t w) const { return base + (w < rem ? 1u : 0u); }
+};
+inline int cast_check(bool rays, uint32_t n_rays, uint32_t flags, bool any_output, const char **msg) {
+    if (!rays) { *msg = "the ray array is NULL"; return SPIRA_E_INVALID; }
+    if (n_rays == 0) { *msg = "n_rays is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = "every output is NULL"; return SPIRA_E_INVALID; }
+    if (n_rays > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) rays"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
+    CastPlan p;
+    p.n_rays = n_rays;
+    p.wpb = std::max<uint32_t>(1, block / 64);
+    const uint64_t max_blocks = std::max<uint64_t>(1, (uint64_t)std::max<uint32_t>(1, num_cus) * std::max<uint32_t>(1, k.waves_per_cu) / p.wpb);
+    const uint64_t want_blocks = std::max<uint64_t>(1, (uint64_t)n_rays / ((uint64_t)kCastMinRaysPerWave * p.wpb));
+    p.grid = (uint32_t)std::min<uint64_t>(std::min(max_blocks, want_blocks), 1u << 20);
+    p.waves = p.grid * p.wpb;
+    p.base = n_rays / p.waves; p.rem = n_rays % p.waves;
+    p.refill_free = std::min<uint32_t>(64, std::max<uint32_t>(1, k.refill));
+    p.grid_flat = features_grid(n_rays, block, num_cus);
+    return p;
+}
+
 }  // namespace spira

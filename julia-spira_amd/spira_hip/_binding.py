@@ -23,6 +23,10 @@ POST_ACES, POST_ACES_GAMMA, POST_CLAMP_GAMMA, POST_NONE = 0x000, 0x100, 0x200, 0
 ROWS_BOTTOM_UP = 0x1000
 FLAG_PROFILE = 0x10000
 EXT_DIELECTRIC, EXT_SPECTRAL = 0x20000, 0x40000
+# ---- ray queries (spira_scene_cast_* / spira_scene_occluded_*) ----
+MAX_RAYS = 1 << 26
+RAY_MISS, RAY_INVALID = -1, -3
+CAST_INPLACE = 0x1
 
 EXPORTS = [
     "spira_abi_version", "spira_build_id", "spira_last_error", "spira_device_count", "spira_set_device", "spira_get_counters",
@@ -40,6 +44,8 @@ EXPORTS = [
     "spira_denoise_f32", "spira_denoise_f64", "spira_denoise_device_f32", "spira_denoise_device_f64",
     "spira_scene_update_f32", "spira_scene_update_f64", "spira_scene_update_device_f32", "spira_scene_update_device_f64",
     "spira_scene_rebuild_f32", "spira_scene_rebuild_f64", "spira_scene_rebuild_device_f32", "spira_scene_rebuild_device_f64",
+    "spira_scene_cast_f32", "spira_scene_cast_f64", "spira_scene_cast_device_f32", "spira_scene_cast_device_f64",
+    "spira_scene_occluded_f32", "spira_scene_occluded_f64", "spira_scene_occluded_device_f32", "spira_scene_occluded_device_f64",
 ]
 
 
@@ -366,6 +372,56 @@ class Scene:
         fn = lib().spira_render_features_scene_device_f32 if self.prec == "f32" else lib().spira_render_features_scene_device_f64
         _check(fn(self._h, cp, C.byref(params), C.c_void_p(d_albedo_ptr or None), C.c_void_p(d_normal_ptr or None), C.c_void_p(d_depth_ptr or None),
                   C.c_void_p(stream_ptr or None)))
+
+    def _rays(self, rays8):
+        npdt, _ = _dt(self.prec)
+        r = np.ascontiguousarray(rays8, dtype=npdt)
+        if r.ndim != 2 or r.shape[1] != 8:
+            raise ValueError("rays8: n_rays x [ox oy oz t_min dx dy dz t_max]")
+        return r
+
+    def cast(self, rays8, want_normal=False, inplace=False, want_prim=True, want_t=True):
+        """spira_scene_cast_*: the closest hit of every ray of rays8 (n x [ox oy oz t_min dx dy dz t_max], host array; directions are normalised by the
+        library, t / t_min / t_max are distances along the unit direction).  Returns (prim int32 [n], t [n], normal [n, 3]), None where not wanted:
+        prim is the object index (spheres first), RAY_MISS (t = the ray's t_max) or RAY_INVALID (t = 0).  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        r = self._rays(rays8)
+        n = len(r)
+        prim = np.empty(n, dtype=np.int32) if want_prim else None
+        t = np.empty(n, dtype=npdt) if want_t else None
+        nrm = np.empty((n, 3), dtype=npdt) if want_normal else None
+        fn = lib().spira_scene_cast_f32 if self.prec == "f32" else lib().spira_scene_cast_f64
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, nrm)]))
+        return prim, t, nrm
+
+    def occluded(self, rays8, inplace=False):
+        """spira_scene_occluded_*: uint8 [n] — 1 where the ray hits anything within [t_min, t_max], 0 where not, 255 for an invalid ray."""
+        r = self._rays(rays8)
+        hit = np.empty(len(r), dtype=np.uint8)
+        fn = lib().spira_scene_occluded_f32 if self.prec == "f32" else lib().spira_scene_occluded_f64
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)), C.c_uint32(CAST_INPLACE if inplace else 0), hit.ctypes.data_as(C.c_void_p)))
+        return hit
+
+    def cast_device(self, d_rays_ptr, n_rays, d_prim_ptr, d_t_ptr, d_normal_ptr, stream_ptr, inplace=False):
+        """spira_scene_cast_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or allocated."""
+        fn = lib().spira_scene_cast_device_f32 if self.prec == "f32" else lib().spira_scene_cast_device_f64
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
+                  C.c_void_p(d_t_ptr or None), C.c_void_p(d_normal_ptr or None), C.c_void_p(stream_ptr or None)))
+
+    def occluded_device(self, d_rays_ptr, n_rays, d_hit_ptr, stream_ptr, inplace=False):
+        """spira_scene_occluded_device_*: DEVICE addresses, asynchronous on the stream."""
+        fn = lib().spira_scene_occluded_device_f32 if self.prec == "f32" else lib().spira_scene_occluded_device_f64
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
+
+def cast_plan(n_rays, num_cus):
+    """The launch plan a cast of n_rays gets on a device of num_cus compute units (test support; no device needed): a dict of grid, wpb, waves, base,
+    rem, refill_free, grid_flat, min_rays_per_wave — wave w of the session kernel owns base + (w < rem) rays from w * base + min(w, rem)."""
+    out = (C.c_uint32 * 8)()
+    _check(lib().spira_debug_cast_plan(C.c_uint32(n_rays), C.c_uint32(num_cus), out))
+    return dict(zip(("grid", "wpb", "waves", "base", "rem", "refill_free", "grid_flat", "min_rays_per_wave"), [int(v) for v in out]))
 
 
 def _feature_outputs(params, npdt, want_albedo, want_normal, want_depth):
