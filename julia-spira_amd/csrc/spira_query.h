@@ -19,6 +19,7 @@
 // the frame, so that pad is never the smaller one and the margin of the fresh build is the one that binds; 64 serves both.  In Float64 the error is
 // 3 (amax_n + 64) 2^-53 against 1e-4 + 1e-9 amax_n: eleven orders of magnitude under.  A caller further away than 64 mesh sizes moves its origin along
 // the ray (o' = o + d t0, t_min and t_max less t0) — or the scene has no tree (at most SPIRA_LDS_TRIANGLES triangles), where there is no rule.
+// Valid origins at 60 .. 64 units, their twins just beyond the bound and the refitted and rebuilt trees are held to the scan by tests/test_gpu_cast_edges.py.
 //
 // Kernels (each stages the scene with stage_scene: one barrier; ExactDiv everywhere — the compiler's division and square root):
 //   k_cast<T, BVH, TRI, ANY>      one lane per ray, grid-stride.  BVH = false: scenes without a tree, the LDS scan alone.  BVH = true: the plain

@@ -223,15 +223,8 @@ def test_bvh_normalised_frame_any_scale_and_position(gpu, oracle, prec):
 def test_bvh_far_camera_and_axis_parallel_rays(gpu, oracle):
     """Rays that start hundreds of mesh sizes away (the Float32 side of a ray starts where it enters the mesh's box) and rays parallel to an
     axis (1/d clamped) against a mesh of axis-aligned quads: bit-exact against the linear scan."""
-    rng = np.random.default_rng(4)
-    quads = []
-    for k in range(300):                           # axis-aligned little squares at random places: many boxes of zero extent along one axis
-        c = rng.uniform(-1, 1, 3)
-        ax = k % 3
-        u, v = np.roll(np.eye(3), ax, axis=1)[0] * 0.2, np.roll(np.eye(3), ax, axis=1)[1] * 0.2
-        quads.append(list(c) + list(c + u) + list(c + v) + [1.0])
-        quads.append(list(c + u) + list(c + u + v) + list(c + v) + [1.0])
-    s = dict(spheres5=np.zeros((0, 5)), materials8=np.array([[0.8, 0.8, 0.8, 0, 0, 0, 0.5, 0.0]]), triangles10=np.array(quads))
+    from cast_support import quad_scene
+    s = quad_scene()                               # axis-aligned little squares at random places: many boxes of zero extent along one axis
     from spira_hip import _binding as B
     for pos, look in (([0.0, 0.0, 500.0], [0.0, 0.0, 0.0]), ([0.0, 0.0, 3.0], [0.0, 0.0, 0.0]), ([250.0, 0.0, 0.0], [0.0, 0.0, 0.0])):
         s["camera12"] = B.camera_lookat(pos, look, [0.0, 1.0, 0.0], 0.4 if max(map(abs, pos)) > 100 else 40.0, 16.0 / 9.0, 1.0, prec="f64")
