@@ -176,6 +176,7 @@ const char *spira_last_error(void);
 int         spira_device_count(void);
 int         spira_set_device(int device);      /* device used by subsequent calls on this thread */
 int         spira_get_counters(spira_counters *out);
+int         spira_get_sky_pixels(uint64_t *out);   /* of the same render: pixels of all-sky runs that k_path summed ahead of its loop (SPIRA_SKY_RUNS; 0 wherever no pixel-owning pass ran).  Beside spira_counters, whose layout stays */
 void        spira_shutdown(void);              /* frees cached device workspaces */
 
 /* ---- camera (host arithmetic only; no device needed) ---- */
@@ -424,6 +425,12 @@ int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const doubl
  * SPIRA_E_* code (sum3 NULL, n outside 1 .. 2^24, tolerance or floor negative or NaN). */
 int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor);
 int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, double tolerance, double floor);
+
+/* ---- all-sky pixels (Float64 pixel-owning passes, SPIRA_SKY_RUNS) ----
+ * Can any camera ray of pixel (i, j) (reference indices: 1 .. width, 1 .. height from the bottom row) meet any sphere?  The host arithmetic of the
+ * function k_path asks (csrc/spira_sky.h; no device needed): 1 no ray of the pixel can — it sees the sky alone —, 0 one may, or a negative SPIRA_E_*
+ * code (a NULL pointer).  It errs towards 0 only. */
+int spira_sky_pixel_f64(const double camera12[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres);
 
 /* ---- first-hit feature buffers: per-pixel albedo, normal and depth, the guides of the denoiser below ----
  * For samples 0 .. params->spp - 1 of each pixel: the camera ray every render entry takes (RNG key: global pixel, sample, bounce 0) and its closest

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "spira_fastdiv.h"
+#include "spira_sky.h"
 
 namespace spira {
 
@@ -1210,6 +1211,7 @@ template <class T> struct RayQueue { Pack4<T> *A; Pack4<T> *B; Pack2<T> *C; };
 struct Stats {                       // device-side counters (one per context)
     unsigned long long segments, rays_enqueued, radiance_rmw, radiance_store, redone_waves, rays_parked;
     unsigned long long mesh_wave_trips, mesh_lane_trips;      // traversal sessions: trips of the walk loop, and the lanes that took part in them (bvh8_step calls)
+    unsigned long long sky_pixels;                            // pixels of all-sky runs, summed ahead of k_path's loop (PathArgs::sky_runs)
 };
 
 template <class T> struct BounceArgs {
@@ -1590,6 +1592,12 @@ template <class T> struct PathArgs {
     // then w * 64 k_eff + e instead of the path index: the carried RNG key stands in for that (kCarry, max_depth <= 128 — the host sets the flag only
     // there; 0: slot-major).  L then holds 64 NW k_eff <= 2^31 entries (>= n_first: the last wave's pixels past the tile's end have entries nobody touches).
     uint32_t l_private;
+    // All-sky runs (pixel-owning passes; 0: off): a run of RUN adjacent pixels none of whose camera rays can reach a sphere (spira_sky.h, decided per
+    // owned pixel at the wave's start) never enters the loop.  Its paths are camera rays that leave the scene: the wave sums their sky terms ahead
+    // of the loop, through its idle work-list LDS and in sample order, and parks each pixel's finished sum in the pixel's slot-0 entry of L — the
+    // only entry of the run it touches — until the end-of-wave block moves it to accum under the conditions it already has.  No scan, and no
+    // 24 bytes per sample written and read back.
+    uint32_t sky_runs;
 };
 
 // Pixel-owning passes: lane l of wave w owns pixel ((l / RUN) * nw + w) * RUN + l % RUN — 64 / RUN runs of RUN adjacent pixels, nw * RUN pixels
@@ -1751,6 +1759,64 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     // the wave's radiance in a block of its own (PathArgs::l_private): the queue word of path e of the wave is l_base + e instead of the path index
     const bool priv = kCarry && own && a.l_private != 0;
     const uint32_t l_base = priv ? wid * n_own : 0u;
+    // All-sky runs (PathArgs::sky_runs): bit g of sky_mask = none of the camera rays of run g's RUN pixels can reach a sphere.  Geometry alone decides
+    // (sky_pixel; lane = owned pixel), so the exact launch behind a speculative one finds the same runs.
+    constexpr bool kOwnT = !BVH && !EXT && !TRI && sizeof(T) == 8;      // the compile-time part of `own`
+    // The loop and the end-of-wave block read the mask from a word of LDS (the camera's 128 bytes hold 96: a word per wave behind them) — kept in a
+    // scalar register across the loop it cost the speculative kernel 13 more spilled SGPRs, from LDS 3 (docs/experiments.md §28).
+    uint32_t sky_mask = 0;
+    uint32_t *sky_word = reinterpret_cast<uint32_t *>(cam_lds + 12) + wave;
+    static_assert(12 * sizeof(T) + WPB * sizeof(uint32_t) <= 128 || !kOwnT, "a word per wave behind the camera");
+    if constexpr (kOwnT) {
+        if (own && a.sky_runs) {
+            constexpr uint32_t kRun = SPIRA_RESOLVE_RUN, kRuns = 64 / kRun, kRowSlots = 64 / kRun;
+            static_assert(kRun == 4 && 2 * 64 * sizeof(Pack3<T>) <= SUB * sizeof(Pack4<T>), "the run mask below is written for runs of 4; a row of terms fits the work list");
+            {
+                const uint32_t px = owned_pixel(wid, NW, lane);
+                bool sky = false;
+                if (px < rc.tile_pixels) {
+                    uint32_t pi, pj, pixel, sample;
+                    path_of<T>(rc, px, a.pass, pi, pj, pixel, sample);
+                    sky = sky_pixel(cam_lds, rc.width, rc.height, pi, pj, a.scene.spheres5, a.scene.n_spheres);
+                }
+                unsigned long long b = __ballot(sky);
+                b &= b >> 1; b &= b >> 2;                            // bit 4 g: all four pixels of run g (inside the tile, and sky)
+                for (uint32_t g = 0; g < kRuns; ++g) sky_mask |= (uint32_t)((b >> (kRun * g)) & 1ull) << g;
+            }
+            // The sky pass.  Run g's paths in the loop's order — rows of RUN pixels x 64 / RUN slots, the loop's own camera ray and sky term — but the
+            // terms go to the wave's work list (idle until the loop's first phase 1) and lanes 0 .. RUN-1 add them up in sample order: resolve_pixel's statements.
+            Pack3<T> *s_sky = reinterpret_cast<Pack3<T> *>(s_rnd);
+            for (uint32_t m = sky_mask; m; m &= m - 1u) {
+                const uint32_t g = (uint32_t)__builtin_ctz(m);
+                const uint32_t px = owned_pixel(wid, NW, g * kRun + lane % kRun);
+                uint32_t pi, pj, pixel, sample0;
+                path_of<T>(rc, px, a.pass, pi, pj, pixel, sample0);           // slot 0 of the pixel
+                Pack3<T> acc;
+                acc.x = 0; acc.y = 0; acc.z = 0;
+                if (!a.accum_first && lane < kRun) { const Pack4<T> a0 = a.accum[px]; acc.x = a0.x; acc.y = a0.y; acc.z = a0.z; }
+                for (uint32_t s0 = 0; s0 < a.k_eff; s0 += kRowSlots) {
+                    const uint32_t slot = s0 + lane / kRun;
+                    if (slot < a.k_eff) {
+                        Vec<T> o_, d_;
+                        camera_ray_lds<T>(rc, cam_lds, pix_div, pi, pj, pixel, sample0 + slot, o_, d_, pol);
+                        const Vec<T> c = sky_term_x<T, EXT>(d_, mk<T>(1, 1, 1), nullptr);      // :365-366, beta as the loop has it for a camera ray
+                        Pack3<T> l; l.x = c.x; l.y = c.y; l.z = c.z;
+                        s_sky[lane] = l;
+                        ++n_seg; ++n_store;                               // counted as the loop counts a camera ray that leaves the scene
+                    }
+                    wave_lds_sync();
+                    if (lane < kRun) {
+                        const uint32_t n = a.k_eff - s0 < kRowSlots ? a.k_eff - s0 : kRowSlots;
+                        for (uint32_t k = 0; k < n; ++k) { const Pack3<T> l = s_sky[k * kRun + lane]; acc.x = acc.x + l.x; acc.y = acc.y + l.y; acc.z = acc.z + l.z; }
+                    }
+                    wave_lds_sync();
+                }
+                // the finished sum waits in the pixel's slot-0 entry of L (nothing else of the run is touched) for the end-of-wave block
+                if (lane < kRun) a.L[priv ? l_base + g * a.k_eff * kRun + lane : px] = acc;
+            }
+        }
+        if (own) { if (lane == 0) *sky_word = sky_mask; wave_lds_sync(); }
+    }
 
     // park a ray on the wave's mesh list (entry = 3 packets: {o, d.x} {d.y, d.z, beta.xy} {beta.z, closest so far, q, object so far + stage of the hit})
     auto park = [&](uint32_t slot_i, const Vec<T> o_, const Vec<T> d_, const Vec<T> beta_, T closest_, uint32_t q_, int prim_, uint32_t stage_hit) {
@@ -1793,6 +1859,11 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
         const uint32_t n_sub = first ? n_sub_first : (n_in + SUB - 1) / SUB;
         uint32_t fill = 0;
         for (uint32_t sub = first ? first_sub : 0u; sub < n_sub; sub += first ? sub_step : 1u) {
+            if constexpr (kOwnT) if (own && first) {      // a sub-chunk that lies inside one all-sky run holds nothing to deal (wave-uniform)
+                const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)*sky_word);
+                const uint32_t r0 = fastdiv(sub * SUB / SPIRA_RESOLVE_RUN, a.fd_keff), r1 = fastdiv((sub * SUB + SUB - 1) / SPIRA_RESOLVE_RUN, a.fd_keff);
+                if (r0 == r1 && ((m >> r0) & 1u)) continue;
+            }
             Vec<T> o[R], beta[R];
             Pending<T> pend[R];                           // between trips pend[r].v holds the direction the hit was reached along
             ExtState<T> ex[R];                            // EXT instantiations only (dead otherwise)
@@ -1814,6 +1885,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                     const uint32_t px = owned_pixel(wid, NW, run * SPIRA_RESOLVE_RUN + idx % SPIRA_RESOLVE_RUN);
                     qf = (t - run * a.k_eff) * rc.tile_pixels + px;
                     in = in && px < rc.tile_pixels;
+                    if constexpr (kOwnT) in = in && !((*sky_word >> run) & 1u);       // an all-sky run was summed ahead of the loop
                 }
                 const uint32_t ql = priv ? l_base + idx : qf;              // where the path's radiance lives: what the queue word carries
                 if (in) {
@@ -2237,7 +2309,16 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         const uint32_t px = owned_pixel(wid, NW, lane);
-        if (px < rc.tile_pixels) {
+        bool summed = false;                                     // the pixel of an all-sky run: its sum is ready, in its slot-0 entry
+        if constexpr (kOwnT) sky_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)*sky_word);
+        if constexpr (kOwnT) summed = ((sky_mask >> (lane / SPIRA_RESOLVE_RUN)) & 1u) != 0;
+        if (summed) {
+            const Pack3<T> l = a.L[priv ? l_base + (lane / SPIRA_RESOLVE_RUN) * a.k_eff * SPIRA_RESOLVE_RUN + lane % SPIRA_RESOLVE_RUN : px];
+            Pack4<T> acc;
+            if (a.accum_first) acc.w = 0; else acc = a.accum[px];
+            acc.x = l.x; acc.y = l.y; acc.z = l.z;
+            a.accum[px] = acc;
+        } else if (px < rc.tile_pixels) {
             if (priv) resolve_pixel_run<T>(a.accum, a.L + l_base + (lane / SPIRA_RESOLVE_RUN) * a.k_eff * SPIRA_RESOLVE_RUN + lane % SPIRA_RESOLVE_RUN, a.k_eff, a.accum_first != 0, px);
             else resolve_pixel<T>(a.accum, a.L, rc.tile_pixels, a.k_eff, a.accum_first != 0, px);
         }
@@ -2247,6 +2328,7 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
             unsigned long long *f = lane == 0 ? &a.stats->segments : (lane == 1 ? &a.stats->rays_enqueued : (lane == 2 ? &a.stats->radiance_rmw : &a.stats->radiance_store));
             atomicAdd(f, (unsigned long long)(lane == 0 ? seg : (lane == 1 ? n_enq : (lane == 2 ? rmw : sto))));
         }
+        if constexpr (kOwnT) if (lane == 4 && sky_mask) atomicAdd(&a.stats->sky_pixels, (unsigned long long)(SPIRA_RESOLVE_RUN * __popc(sky_mask)));
     }
     MESH_STAT(if (lane == 0) { unsigned long long *g = g_mesh_dbg + (mesh_mode == 2u ? 16 : 0);
                                atomicAdd(&g[0], __builtin_readcyclecounter() - dbg_t0); atomicAdd(&g[1], dbg_sess); atomicAdd(&g[2], (unsigned long long)dbg_ns);

@@ -175,6 +175,7 @@ struct Ctx {
     std::vector<size_t> ev_mid_end;           // ... and the ev_pool index of the event that closes that pass's bracket
     size_t ev_mid_used = 0;
     spira_counters last{};
+    uint64_t last_sky_pixels = 0;             // spira_get_sky_pixels: Stats::sky_pixels of the same render (spira_counters keeps its layout)
     bool last_valid = false, last_pending = false;
     hipStream_t last_stream = nullptr;
     std::recursive_mutex mu;                  // (recursive: a host-output frame rendered as row slabs holds it across its slabs' render calls)
@@ -730,6 +731,7 @@ spira::Knobs read_knobs() {
     k.mesh_refill = std::min<uint32_t>(64, std::max<uint32_t>(1, env_u32("SPIRA_MESH_REFILL", 16)));
     k.mesh_fat_waves_per_cu = env_u32("SPIRA_MESH_FAT_WAVES_PER_CU", 16);
     k.cam_consts = env_u32("SPIRA_CAM_CONSTS", 1);
+    k.sky_runs = env_u32("SPIRA_SKY_RUNS", 1);
     return k;
 }
 template <class T>
@@ -972,6 +974,7 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
         pa.accum = k.accum(); pa.k_eff = plan.k_eff(pa.pass); pa.fd_keff = spira::fastdiv_make(pa.k_eff);
         pa.accum_first = (pa.pass == 0 && !k.progressive) ? 1u : 0u;
         pa.l_private = plan.l_private ? 1u : 0u;
+        pa.sky_runs = plan.sky_runs ? 1u : 0u;
     }
     if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
@@ -2745,6 +2748,7 @@ int spira_get_counters(spira_counters *out) {
         c.last.rays_parked = c.h_stats->rays_parked;
         c.last.mesh_wave_trips = c.h_stats->mesh_wave_trips;
         c.last.mesh_lane_trips = c.h_stats->mesh_lane_trips;
+        c.last_sky_pixels = c.h_stats->sky_pixels;
         double wms = 0;
         for (size_t i = 0; i < c.ev_mid_used; ++i) {
             float m = 0;
@@ -2762,6 +2766,17 @@ int spira_get_counters(spira_counters *out) {
         c.last_pending = false;
     }
     *out = c.last;
+    return 0;
+}
+
+int spira_get_sky_pixels(uint64_t *out) {
+    if (!out) return fail(SPIRA_E_INVALID, "out is NULL");
+    spira_counters unused;
+    if (int rc = spira_get_counters(&unused)) return rc;      // (waits for the render and reads its device counters back)
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(cp->mu);
+    *out = cp->last_sky_pixels;
     return 0;
 }
 
@@ -2955,6 +2970,10 @@ int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const doubl
                                            double *d_hdr, double *d_img, uint32_t *d_spp, double *d_q, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
     return render_adaptive_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
+}
+int spira_sky_pixel_f64(const double cam[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres) {
+    if (!cam || (n_spheres && !spheres5)) return fail(SPIRA_E_INVALID, "cam or spheres5 is NULL");
+    return spira::sky_pixel(cam, width, height, i, j, spheres5, n_spheres) ? 1 : 0;
 }
 int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor) {
     return adaptive_converged_host<float>(sum3, q, n, tolerance, floor);

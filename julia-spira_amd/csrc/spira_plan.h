@@ -18,6 +18,7 @@ struct Knobs {
     uint32_t defer_mesh = 1, mesh_two_pass = 1, fused_resolve = 1, private_l = 1;
     uint32_t spec_div = 1;                     // SPIRA_SPEC_DIV: 0 off, 1 where the scene's scale allows, 2 report every wave, 3 on whatever the scale
     uint32_t dense_pct = 70, mesh_min_batch = 128, mesh_refill = 16, mesh_fat_waves_per_cu = 16, cam_consts = 1;
+    uint32_t sky_runs = 1;                     // SPIRA_SKY_RUNS: pixel-owning passes sum their all-sky runs ahead of the loop (0: every path goes through it; A/B, tests)
 };
 
 struct PlanIn {
@@ -52,6 +53,7 @@ struct Plan {
     uint32_t slots = 0, n_pass = 0;                        // samples of every pixel per pass; passes (equal: spp 256 at 80 slots -> 4 x 64, not 3 x 80 + 16)
     bool mesh_scene = false, defer_mesh = false, two_pass = false;      // a BVH scene; its traversal deferred (mesh lists); ... as a second, fat-wave launch
     bool fused = false, l_private = false;                 // pixel-owning passes (PathArgs::accum); wave-private radiance blocks (PathArgs::l_private)
+    bool sky_runs = false;                                 // ... whose all-sky runs never enter the loop (PathArgs::sky_runs)
     bool spec_allowed = false;                             // the organisation has a speculative-division launch for this call
     uint32_t G_max = 0, cap_max = 0;                       // geometry of the largest pass
     uint64_t q_rays = 0;
@@ -145,6 +147,7 @@ inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
     // RNG key is carried through the queue for max_depth <= 128 (deeper renders derive it from the path index and keep the slot-major L), and the
     // queue word has 31 bits for the entry of L.  SPIRA_PRIVATE_L=0: the slot-major layout (A/B).
     pl.l_private = pl.fused && in.carry_key && in.max_depth <= 128 && k.private_l != 0 && 64ull * waves * pl.slots <= 0x7FFFFFFFull;
+    pl.sky_runs = pl.fused && k.sky_runs != 0;
     pl.q_rays = (uint64_t)g.cap * waves;
     if (pl.q_rays > 0xFFFFFFFFull) return bad("pass too large");
     // the speculative launch: fresh renders only (a progressive SPIRA_SEM_METAL call updates sums and states in place), R = 2 instantiations only
