@@ -358,6 +358,76 @@ int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_ray
 int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags,
                                     uint8_t *d_out_hit, void *stream);
 
+/* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
+ * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
+ * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.
+ * rays6: n_rays x [ox oy oz dx dy dz].  Preparation per ray, in the call's precision T, nothing fused: s = (dx dx + dy dy) + dz dz,
+ * d = (dx, dy, dz) / sqrt(s) — exactly what the renderer's normalize() and the ray queries' preparation do.  A ray is INVALID when any of its six values is
+ * NaN or infinite, or s is not finite or is below the smallest normal number of T: out_valid[k] = 0 (valid rays: 1), nothing is added to its sums, and its
+ * neighbours are not disturbed.  There is no origin rule: every segment is the renderer's own.
+ * Paths: ray k, sample s in sample0 .. sample0 + spp - 1, is the path the renderer would trace for a camera ray of that origin and unit direction at PIXEL
+ * KEY key0 + k: SPIRA_SEM_A, every random number from rng_key(sA, sB, key0 + k, s, bounce) with sA, sB derived from `seed` as every entry derives them;
+ * every segment with t_min 0.001, the first included; scatter while bounce + 1 < max_depth; sky, emission, the extensions and the tree walk as in a render.
+ * So a ray list made from a pinhole camera (spira_camera_rays_* below) with key0 = row0 * width reproduces spira_accumulate_* and spira_render_scene_*
+ * bit for bit.
+ * Sums: sum_rgb is n_rays x 3, INTERLEAVED, caller-owned.  The entry ADDS, per channel in T, one addition per sample in ascending sample order,
+ * sum = sum + L_s — the contract of spira_accumulate_*: k calls of n samples leave bit for bit the sums of one call of k*n samples, and a ray list traced
+ * in chunks (key0 advanced by the rays before the chunk) leaves bit for bit the sums of the whole list.  out_valid may be NULL; sum_rgb may not.
+ * flags: 0, SPIRA_EXT_DIELECTRIC, SPIRA_EXT_SPECTRAL; any other bit is SPIRA_E_UNSUPPORTED.
+ * Errors, all decided before any device is touched: a NULL ray array, struct or sum_rgb, n_rays == 0, spp == 0, max_depth outside 1 .. SPIRA_MAX_DEPTH,
+ * reserved != 0, a NULL or destroyed handle, one of the other precision or of another device: SPIRA_E_INVALID; n_rays > SPIRA_MAX_RAYS, key0 + n_rays > 2^32,
+ * sample0 + spp > SPIRA_MAX_SPP: SPIRA_E_LIMIT.  A scene whose LDS the device refuses: SPIRA_E_LIMIT, as for a render.  A handle made by
+ * spira_scene_create_multi_* is served by device 0's copy.
+ * The host form copies rays in, sum_rgb in AND out, out_valid out, and returns when they are written.  The *_device_* form takes DEVICE pointers, is
+ * asynchronous on `stream`, synchronises nothing, allocates only on its first call at a size (the workspace stays in the device context until
+ * spira_shutdown; a call of one sample per ray needs none) and is ordered like every entry: a call enqueued after a device-form update or rebuild on
+ * another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+typedef struct spira_radiance {
+    uint32_t spp, max_depth, flags, sample0;
+    uint64_t seed;
+    uint32_t key0, reserved;         /* reserved must be 0 */
+} spira_radiance;                    /* 32 bytes */
+int spira_scene_radiance_f32(const spira_scene *scene, const float *rays6, uint32_t n_rays, const spira_radiance *rp,
+                             float *sum_rgb, uint8_t *out_valid);
+int spira_scene_radiance_f64(const spira_scene *scene, const double *rays6, uint32_t n_rays, const spira_radiance *rp,
+                             double *sum_rgb, uint8_t *out_valid);
+int spira_scene_radiance_device_f32(const spira_scene *scene, const float *d_rays6, uint32_t n_rays, const spira_radiance *rp,
+                                    float *d_sum_rgb, uint8_t *d_out_valid, void *stream);
+int spira_scene_radiance_device_f64(const spira_scene *scene, const double *d_rays6, uint32_t n_rays, const spira_radiance *rp,
+                                    double *d_sum_rgb, uint8_t *d_out_valid, void *stream);
+
+/* ---- camera ray generator: the ray list of one sample of every pixel of `rows` rows, for the radiance entries above ----
+ * Replaces get_ray(camera, u, v) of examples/julia-raytracer.jl:298-306 with the pixel jitter of :398-399 — and gives the reference's stored-but-unused
+ * lens_radius (:261-295, "No defocus blur" :298) its thin lens.  camera12 as everywhere (origin, lower_left_corner, horizontal, vertical; focus_dist is
+ * already in it).  rays6: rows * width x [ox oy oz dx dy dz], directions NOT normalised (the radiance entry normalises), ordered by reference pixel:
+ * ray k = (j - 1 - row0) * width + (i - 1) for i in 1 .. width, j - 1 in row0 .. row0 + rows - 1, j = 1 the BOTTOM row (v = 0).  The ray's key is its global
+ * pixel (j - 1) * width + (i - 1): pass key0 = row0 * width to the radiance entry.
+ * All models, in T, in the written order, nothing fused: (xu, xv) = the pixel jitter of every render entry, rng3(rng_key(pixel, sample, 0), 0);
+ * u = ((i - 1) + xu) / (W - 1), v = ((j - 1) + xv) / (H - 1); P = (llc + hor u) + ver v.
+ *   SPIRA_CAM_PINHOLE    o = origin, d = P - origin: bit for bit the renderer's camera ray before normalisation.
+ *   SPIRA_CAM_THIN_LENS  lens_radius == 0 is PINHOLE by definition.  Else eu = normalize(hor), ev = normalize(ver); a lens point p from the reference's
+ *                        rejection idiom under key (pixel, sample, bounce 255 — no path's, max_depth <= 255): tries t = 1 .. 64, p = (2 u0 - 1, 2 u1 - 1),
+ *                        accepted when p.p < 1, else p = 0; off = eu (R p.x) + ev (R p.y), o = origin + off, d = (P - origin) - off, R = lens_radius
+ *                        rounded to T once: every ray of a pixel sample meets the focus plane at P.
+ *   SPIRA_CAM_ORTHO      o = P, d = ((llc + hor / 2) + ver / 2) - origin: every ray runs along the camera axis.
+ * Limits: width, height >= 2, a known model, lens_radius finite and >= 0, row0 + rows <= height (rows == 0: the whole image, row0 ignored), NULL pointers:
+ * else SPIRA_E_INVALID; width * height >= 2^31, sample >= SPIRA_MAX_SPP, rows * width > SPIRA_MAX_RAYS: SPIRA_E_LIMIT.
+ * The host form is host arithmetic (the same inline function the kernel calls; no device needed).  The *_device_* form writes a DEVICE array, is
+ * asynchronous on `stream`, synchronises and allocates nothing, and is ordered like every device entry. */
+#define SPIRA_CAM_PINHOLE 0u
+#define SPIRA_CAM_THIN_LENS 1u
+#define SPIRA_CAM_ORTHO 2u
+typedef struct spira_lens {
+    uint32_t model, width, height, sample;
+    uint64_t seed;
+    uint32_t row0, rows;             /* reference rows j-1, from the bottom; rows == 0: all */
+    double   lens_radius;
+} spira_lens;                        /* 40 bytes */
+int spira_camera_rays_f32(const float camera12[12], const spira_lens *lens, float *rays6);
+int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, double *rays6);
+int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream);
+int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream);
+
 /* ---- progressive accumulation (checkpoint / resume / adaptive sampling) ----
  * The contract the reference's kernel was designed for and no host code uses: `current_sample_index`,
  * persisted `rng_states`, `output_hdr_image[p] += L` (src/spira_path_trace_kernel.metal:143-145, :252-268).

@@ -43,6 +43,7 @@
 #include "spira_refit.h"
 #include "spira_lbvh.h"
 #include "spira_query.h"
+#include "spira_radiance.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -77,6 +78,8 @@ int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *ma
 int scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
 int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
                   bool any, bool on_device, void *user_stream);
+int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
+int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -157,6 +160,7 @@ struct Ctx {
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
     DevBuf cast_io;                               // spira_scene_cast_* / spira_scene_occluded_*: the host form's staged rays and outputs
+    DevBuf radiance_io;                           // spira_scene_radiance_*: the host form's staged rays, sums and valid bytes (its workspace is L)
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
     uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
     DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
@@ -1558,6 +1562,124 @@ int cast_entry(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t f
         return cast_impl<T>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
 }
 
+// ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
+// Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
+// (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
+// the host form stages rays, sums and valid bytes in radiance_io.  The counters of the last render are left as they are.
+spira::RadianceKnobs read_radiance_knobs() {
+    spira::RadianceKnobs k;
+    k.waves_per_cu = env_u32("SPIRA_RADIANCE_WAVES_PER_CU", SPIRA_RADIANCE_WAVES_PER_CU);
+    k.max_items = env_u32("SPIRA_RADIANCE_MAX_ITEMS", SPIRA_RADIANCE_MAX_ITEMS);
+    return k;
+}
+template <class T>
+int launch_radiance(dim3 grid, size_t lds, hipStream_t st, const spira::RadianceArgs<T> &a) {
+    const dim3 block(spira::kBlock);
+    const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    if (a.scene.n_bvh_tris) return ext ? launch_lds(spira::k_radiance<T, true, true>, grid, block, lds, st, a) : launch_lds(spira::k_radiance<T, true, false>, grid, block, lds, st, a);
+    return ext ? launch_lds(spira::k_radiance<T, false, true>, grid, block, lds, st, a) : launch_lds(spira::k_radiance<T, false, false>, grid, block, lds, st, a);
+}
+template <class T>
+int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::radiance_check(rays6 != nullptr, rp != nullptr, sum_rgb != nullptr, n_rays, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
+                                       rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
+    if (int rc = check_handle<T>(h)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
+
+    const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, rp->spp, (uint32_t)c.num_cus, spira::kBlock, read_radiance_knobs());
+    if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
+    spira::RadianceArgs<T> a{};
+    scene_pointers<T>(h->store, a.scene);
+    spira_params fake{};
+    fake.flags = rp->flags;
+    if (int rc = attach_spd<T>(c, st, &fake, a.scene)) return rc;
+    spira::seed_halves(rp->seed, a.rc.sA, a.rc.sB);
+    a.rc.flags = rp->flags; a.rc.max_depth = rp->max_depth; a.rc.spp = rp->spp;
+    a.rays = rays6; a.n_rays = n_rays; a.sum = sum_rgb; a.valid = out_valid; a.key0 = rp->key0;
+    a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
+    const size_t n = n_rays, ray_b = 6 * n * sizeof(T), sum_b = 3 * n * sizeof(T);
+    if (!on_device) {
+        // [rays | sums | valid]: every block starts at a multiple of sizeof(T)
+        if (int rc = c.radiance_io.ensure(ray_b + sum_b + n)) return rc;
+        char *base = (char *)c.radiance_io.p;
+        HIP_TRY(hipMemcpyAsync(base, rays6, ray_b, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + ray_b, sum_rgb, sum_b, hipMemcpyHostToDevice, st));
+        a.rays = (const T *)base;
+        a.sum = (T *)(base + ray_b);
+        a.valid = out_valid ? (uint8_t *)(base + ray_b + sum_b) : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        a.sample_first = rp->sample0 + pl.first(pass);
+        a.spp_pass = pl.count(pass);
+        a.n_items = (uint32_t)pl.items(pass);
+        a.fd_spp = spira::fastdiv_make(a.spp_pass);
+        a.write_valid = pass == 0 ? 1u : 0u;
+        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+        if (a.ws && (uint64_t)a.n_items * sizeof(spira::Pack3<T>) > c.L.cap) return fail(SPIRA_E_LIMIT, "internal: the radiance workspace is smaller than the pass");
+        if (int rc = launch_radiance<T>(dim3(pl.grid), lds, st, a)) return rc;
+        if (a.ws) hipLaunchKernelGGL(spira::k_radiance_sum<T>, dim3(pl.grid_flat), dim3(spira::kBlock), 0, st, a);
+    }
+    if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(sum_rgb, a.sum, sum_b, hipMemcpyDeviceToHost, st));
+        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
+    }
+    return s.close();
+}
+template <class T>
+int radiance_entry(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::radiance_impl_f32(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
+    else
+#endif
+        return radiance_impl<T>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
+}
+
+// The generator: the host form runs camera_ray_generate<T> here, the device form launches k_camera_rays<T> over the same function.
+template <class T>
+int camera_rays_impl(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream) {
+    if (!camera12) return fail(SPIRA_E_INVALID, "camera12 is NULL");
+    if (!lens) return fail(SPIRA_E_INVALID, "the spira_lens struct is NULL");
+    if (!rays6) return fail(SPIRA_E_INVALID, "the ray array is NULL");
+    const char *msg = nullptr;
+    uint32_t rows = 0;
+    if (int rc = spira::camera_rays_check(lens->model, lens->width, lens->height, lens->sample, lens->row0, lens->rows, lens->lens_radius, &rows, &msg)) return fail(rc, msg);
+    const uint32_t row0 = lens->rows ? lens->row0 : 0, W = lens->width, n = rows * W;
+    uint32_t sA, sB;
+    spira::seed_halves(lens->seed, sA, sB);
+    const T R = (T)lens->lens_radius;
+    if (!on_device) {
+        for (uint32_t r = 0; r < rows; ++r)
+            for (uint32_t ix = 0; ix < W; ++ix)
+                spira::camera_ray_generate<T>(camera12, lens->model, W, lens->height, sA, sB, ix, row0 + r, lens->sample, R, rays6 + 6 * ((size_t)r * W + ix));
+        return 0;
+    }
+    Session s;
+    if (int rc = Session::open(s, true, user_stream)) return rc;
+    spira::CameraRaysArgs<T> a{};
+    for (int k = 0; k < 12; ++k) a.cam[k] = camera12[k];
+    a.lens_radius = R; a.rays = rays6;
+    a.model = lens->model; a.width = W; a.height = lens->height; a.sample = lens->sample; a.sA = sA; a.sB = sB; a.row0 = row0; a.n = n;
+    a.fd_width = spira::fastdiv_make(W);
+    if (!fastdiv_selfcheck(W, n)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+    hipLaunchKernelGGL(spira::k_camera_rays<T>, dim3((n + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
+    return s.close();
+}
+template <class T>
+int camera_rays_entry(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::camera_rays_impl_f32(camera12, lens, rays6, on_device, user_stream);
+    else
+#endif
+        return camera_rays_impl<T>(camera12, lens, rays6, on_device, user_stream);
+}
+
 // ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
 // The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
 // walk or the node format is involved: a refit rewrites boxes, and the walk only prunes with them.
@@ -2604,6 +2726,12 @@ int spira_tu::cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n
                             bool any, bool on_device, void *user_stream) {
     return cast_impl<float>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
 }
+int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
+}
+int spira_tu::camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream) {
+    return camera_rays_impl<float>(camera12, lens, rays6, on_device, user_stream);
+}
 int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                                float *out_hdr, float *out_img, bool on_device, void *user_stream) {
     return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
@@ -2674,6 +2802,34 @@ int spira_debug_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t *out8) {
     if (!out8 || n_rays == 0 || n_rays > SPIRA_MAX_RAYS) return fail(SPIRA_E_INVALID, "spira_debug_cast_plan: out8 is NULL or n_rays outside 1 .. SPIRA_MAX_RAYS");
     const spira::CastPlan cp = spira::make_cast_plan(n_rays, num_cus, spira::kBlock, read_cast_knobs());
     const uint32_t v[8] = {cp.grid, cp.wpb, cp.waves, cp.base, cp.rem, cp.refill_free, cp.grid_flat, spira::kCastMinRaysPerWave};
+    std::memcpy(out8, v, sizeof v);
+    return 0;
+}
+
+// ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)
+int spira_scene_radiance_f32(const spira_scene *scene, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid) {
+    return radiance_entry<float>(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
+}
+int spira_scene_radiance_f64(const spira_scene *scene, const double *rays6, uint32_t n_rays, const spira_radiance *rp, double *sum_rgb, uint8_t *out_valid) {
+    return radiance_entry<double>(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
+}
+int spira_scene_radiance_device_f32(const spira_scene *scene, const float *d_rays6, uint32_t n_rays, const spira_radiance *rp, float *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
+    return radiance_entry<float>(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
+}
+int spira_scene_radiance_device_f64(const spira_scene *scene, const double *d_rays6, uint32_t n_rays, const spira_radiance *rp, double *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
+    return radiance_entry<double>(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
+}
+int spira_camera_rays_f32(const float camera12[12], const spira_lens *lens, float *rays6) { return camera_rays_entry<float>(camera12, lens, rays6, false, nullptr); }
+int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, double *rays6) { return camera_rays_entry<double>(camera12, lens, rays6, false, nullptr); }
+int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream) { return camera_rays_entry<float>(camera12, lens, d_rays6, true, stream); }
+int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream) { return camera_rays_entry<double>(camera12, lens, d_rays6, true, stream); }
+// Test support, outside the ABI like spira_debug_cast_plan: the plan a radiance call of n_rays x spp gets on a device of num_cus CUs, with the knobs of the
+// environment as the entries read them.  out8: grid, wpb, spp_pass, n_pass, direct, workspace entries (low, high word), the item cap.  No device needed.
+int spira_debug_radiance_plan(uint32_t n_rays, uint32_t spp, uint32_t num_cus, uint32_t *out8) {
+    if (!out8 || n_rays == 0 || n_rays > SPIRA_MAX_RAYS || spp == 0 || spp > SPIRA_MAX_SPP)
+        return fail(SPIRA_E_INVALID, "spira_debug_radiance_plan: out8 is NULL, n_rays outside 1 .. SPIRA_MAX_RAYS or spp outside 1 .. SPIRA_MAX_SPP");
+    const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, spp, num_cus, spira::kBlock, read_radiance_knobs());
+    const uint32_t v[8] = {pl.grid, pl.wpb, pl.spp_pass, pl.n_pass, pl.direct ? 1u : 0u, (uint32_t)pl.ws_entries, (uint32_t)(pl.ws_entries >> 32), pl.max_items};
     std::memcpy(out8, v, sizeof v);
     return 0;
 }
@@ -2794,7 +2950,7 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release(); c.cast_io.release();
+        c.refit_status.release(); c.cast_io.release(); c.radiance_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);

@@ -400,4 +400,71 @@ inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block
     return p;
 }
 
+// ---- radiance along the caller's rays (spira_scene_radiance_*) and the camera ray generator (spira_camera_rays_*); kernels in spira_radiance.h.
+// A work item is (ray, sample), sample-minor.  A pass covers spp_pass consecutive samples of every ray — pass p the samples [p spp_pass, min((p + 1)
+// spp_pass, spp)) of the call, ascending and contiguous, so that the sums see their samples in order whatever the split — and holds at most max_items
+// items: what the workspace (one Pack3<T> per item) is capped by.  A pass of ONE sample per ray needs no workspace: the lane that owns the ray adds to its
+// sum itself (`direct`).  The pass count is the least the cap admits and the passes are as equal as that count allows (spp 10, at most 6 per pass: 5 + 5).
+constexpr uint32_t kRadianceMaxItems = 1u << 26;      // >= SPIRA_MAX_RAYS: one sample of every ray always fits a pass
+struct RadianceKnobs { uint32_t waves_per_cu = 64, max_items = kRadianceMaxItems; };      // SPIRA_RADIANCE_WAVES_PER_CU (0: one workgroup), SPIRA_RADIANCE_MAX_ITEMS
+struct RadiancePlan {
+    uint32_t n_rays = 0, spp = 0;
+    uint32_t spp_pass = 0, n_pass = 0;         // samples of every ray per pass (the last pass may hold fewer); passes
+    uint32_t grid = 0, wpb = 0;                // workgroups of k_radiance (it strides over the pass's items), waves per workgroup
+    uint32_t grid_flat = 0;                    // k_radiance_sum: one lane per ray (it strides)
+    bool direct = false;                       // spp_pass == 1: no workspace
+    uint64_t ws_entries = 0;                   // entries of the workspace: n_rays * spp_pass, or 0
+    uint32_t max_items = 0;                    // the cap as applied
+    uint32_t first(uint32_t p) const { return p * spp_pass; }                       // relative to the call's sample0
+    uint32_t count(uint32_t p) const { return std::min(spp_pass, spp - p * spp_pass); }
+    uint64_t items(uint32_t p) const { return (uint64_t)n_rays * count(p); }
+};
+inline int radiance_check(bool rays, bool params, bool sums, uint32_t n_rays, uint32_t spp, uint32_t max_depth, uint32_t flags, uint32_t sample0, uint32_t key0,
+                          uint32_t reserved, const char **msg) {
+    if (!rays) { *msg = "the ray array is NULL"; return SPIRA_E_INVALID; }
+    if (!params) { *msg = "the spira_radiance struct is NULL"; return SPIRA_E_INVALID; }
+    if (!sums) { *msg = "sum_rgb is NULL"; return SPIRA_E_INVALID; }
+    if (n_rays == 0) { *msg = "n_rays is 0"; return SPIRA_E_INVALID; }
+    if (spp == 0) { *msg = "spp is 0"; return SPIRA_E_INVALID; }
+    if (max_depth < 1 || max_depth > SPIRA_MAX_DEPTH) { *msg = "max_depth must be 1 .. SPIRA_MAX_DEPTH (255)"; return SPIRA_E_INVALID; }
+    if (reserved != 0) { *msg = "spira_radiance::reserved must be 0"; return SPIRA_E_INVALID; }
+    if (flags & ~(SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) { *msg = "flags: 0, SPIRA_EXT_DIELECTRIC and SPIRA_EXT_SPECTRAL are all the radiance entries take"; return SPIRA_E_UNSUPPORTED; }
+    if (n_rays > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) rays"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)key0 + n_rays > (1ull << 32)) { *msg = "key0 + n_rays exceeds 2^32"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)sample0 + spp > SPIRA_MAX_SPP) { *msg = "sample0 + spp exceeds 2^24"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+// n_rays in 1 .. SPIRA_MAX_RAYS, spp in 1 .. SPIRA_MAX_SPP (radiance_check)
+inline RadiancePlan make_radiance_plan(uint32_t n_rays, uint32_t spp, uint32_t num_cus, uint32_t block, const RadianceKnobs &k) {
+    RadiancePlan p;
+    p.n_rays = n_rays; p.spp = spp;
+    p.max_items = std::min<uint32_t>(std::max<uint32_t>(1, k.max_items), kRadianceMaxItems);
+    const uint32_t fit = std::max<uint32_t>(1, p.max_items / n_rays);              // samples of every ray the cap admits (1 even where it admits none: no workspace then)
+    const uint32_t n_pass = (uint32_t)(((uint64_t)spp + std::min(fit, spp) - 1) / std::min(fit, spp));
+    p.spp_pass = (spp + n_pass - 1) / n_pass;                                      // <= min(fit, spp)
+    p.n_pass = (spp + p.spp_pass - 1) / p.spp_pass;
+    p.direct = p.spp_pass == 1;
+    p.ws_entries = p.direct ? 0 : (uint64_t)n_rays * p.spp_pass;
+    p.wpb = std::max<uint32_t>(1, block / 64);
+    const uint64_t max_blocks = k.waves_per_cu == 0 ? 1 : std::max<uint64_t>(1, (uint64_t)std::max<uint32_t>(1, num_cus) * k.waves_per_cu / p.wpb);
+    const uint64_t items = (uint64_t)n_rays * p.spp_pass;
+    p.grid = (uint32_t)std::min<uint64_t>(std::min<uint64_t>((items + block - 1) / block, max_blocks), 1u << 20);
+    p.grid_flat = features_grid(n_rays, block, num_cus);
+    return p;
+}
+// spira_camera_rays_*: everything but the pointers.  *rows_out: the rows generated (rows == 0: all).
+inline int camera_rays_check(uint32_t model, uint32_t width, uint32_t height, uint32_t sample, uint32_t row0, uint32_t rows, double lens_radius,
+                             uint32_t *rows_out, const char **msg) {
+    if (model > 2u) { *msg = "spira_lens::model must be one of SPIRA_CAM_*"; return SPIRA_E_INVALID; }
+    if (width < 2 || height < 2) { *msg = "width and height must be >= 2 (u = (i-1+rand)/(W-1))"; return SPIRA_E_INVALID; }
+    if (!(lens_radius >= 0) || !(lens_radius - lens_radius == 0)) { *msg = "spira_lens::lens_radius must be finite and >= 0"; return SPIRA_E_INVALID; }
+    if (rows != 0 && (uint64_t)row0 + rows > height) { *msg = "row0 + rows > height"; return SPIRA_E_INVALID; }      // (rows == 0: the whole image, row0 ignored, as in spira_params)
+    if ((uint64_t)width * height > 0x7FFFFFFFull) { *msg = "image larger than 2^31 pixels"; return SPIRA_E_LIMIT; }
+    if (sample >= SPIRA_MAX_SPP) { *msg = "sample index must be below 2^24"; return SPIRA_E_LIMIT; }
+    const uint32_t r = rows ? rows : height;
+    if ((uint64_t)r * width > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) rays: generate the image in row chunks"; return SPIRA_E_LIMIT; }
+    *rows_out = r;
+    return 0;
+}
+
 }  // namespace spira

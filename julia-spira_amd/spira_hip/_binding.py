@@ -27,6 +27,9 @@ EXT_DIELECTRIC, EXT_SPECTRAL = 0x20000, 0x40000
 MAX_RAYS = 1 << 26
 RAY_MISS, RAY_INVALID = -1, -3
 CAST_INPLACE = 0x1
+# ---- camera models of the ray generator (spira_camera_rays_*) ----
+CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO = 0, 1, 2
+MAX_DEPTH, MAX_SPP = 255, 1 << 24
 
 EXPORTS = [
     "spira_abi_version", "spira_build_id", "spira_last_error", "spira_device_count", "spira_set_device", "spira_get_counters",
@@ -47,6 +50,8 @@ EXPORTS = [
     "spira_scene_rebuild_f32", "spira_scene_rebuild_f64", "spira_scene_rebuild_device_f32", "spira_scene_rebuild_device_f64",
     "spira_scene_cast_f32", "spira_scene_cast_f64", "spira_scene_cast_device_f32", "spira_scene_cast_device_f64",
     "spira_scene_occluded_f32", "spira_scene_occluded_f64", "spira_scene_occluded_device_f32", "spira_scene_occluded_device_f64",
+    "spira_scene_radiance_f32", "spira_scene_radiance_f64", "spira_scene_radiance_device_f32", "spira_scene_radiance_device_f64",
+    "spira_camera_rays_f32", "spira_camera_rays_f64", "spira_camera_rays_device_f32", "spira_camera_rays_device_f64",
 ]
 
 
@@ -81,6 +86,18 @@ class Denoise(C.Structure):
     """spira_denoise: the frame size and the settings of a denoise call."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("post", C.c_uint32),
                 ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
+
+
+class Radiance(C.Structure):
+    """spira_radiance: the samples, depth, seed and pixel keys of a radiance call on a ray list."""
+    _fields_ = [("spp", C.c_uint32), ("max_depth", C.c_uint32), ("flags", C.c_uint32), ("sample0", C.c_uint32),
+                ("seed", C.c_uint64), ("key0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Lens(C.Structure):
+    """spira_lens: camera model, image size, sample, seed and row range of a generated ray list."""
+    _fields_ = [("model", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("sample", C.c_uint32),
+                ("seed", C.c_uint64), ("row0", C.c_uint32), ("rows", C.c_uint32), ("lens_radius", C.c_double)]
 
 
 _lib = None
@@ -432,6 +449,71 @@ class Scene:
         fn = lib().spira_scene_occluded_device_f32 if self.prec == "f32" else lib().spira_scene_occluded_device_f64
         _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
                   C.c_void_p(stream_ptr or None)))
+
+
+    def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
+        """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).
+        Ray k, sample s is the renderer's path at pixel key key0 + k.  ADDS samples sample0 .. sample0 + spp - 1, in order, to sums ([n, 3], in place; None: a
+        fresh zero array).  Returns sums, or (sums, valid uint8 [n]) with want_valid."""
+        npdt, _ = _dt(self.prec)
+        r = np.ascontiguousarray(rays6, dtype=npdt)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("rays6: n_rays x [ox oy oz dx dy dz]")
+        n = len(r)
+        if sums is None:
+            sums = np.zeros((n, 3), dtype=npdt)
+        if sums.dtype != npdt or not sums.flags["C_CONTIGUOUS"] or sums.shape != (n, 3):
+            raise ValueError("sums: a contiguous [n_rays, 3] array of the handle's precision")
+        valid = np.empty(n, dtype=np.uint8) if want_valid else None
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        fn = lib().spira_scene_radiance_f32 if self.prec == "f32" else lib().spira_scene_radiance_f64
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(rp), sums.ctypes.data_as(C.c_void_p),
+                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        return (sums, valid) if want_valid else sums
+
+    def radiance_device(self, d_rays_ptr, n_rays, spp, max_depth, d_sums_ptr, seed=0, sample0=0, key0=0, flags=0, d_valid_ptr=0, stream_ptr=0):
+        """spira_scene_radiance_device_*: DEVICE addresses (d_valid_ptr 0 / None: not wanted), asynchronous on the stream; the sums are added to in place."""
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        fn = lib().spira_scene_radiance_device_f32 if self.prec == "f32" else lib().spira_scene_radiance_device_f64
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.byref(rp), C.c_void_p(d_sums_ptr or None), C.c_void_p(d_valid_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
+
+def make_lens(model, width, height, sample=0, seed=0, row0=0, rows=0, lens_radius=0.0):
+    return Lens(model, width, height, sample, seed, row0, rows, lens_radius)
+
+
+def camera_rays(camera12, model, width, height, sample=0, seed=0, row0=0, rows=0, lens_radius=0.0, prec="f32"):
+    """spira_camera_rays_*: the rays of one sample of every pixel of `rows` rows (0: all) as a host array [rows * width, 6] = [o, d], d not normalised,
+    ordered by reference pixel (row j - 1 = row0 first: the BOTTOM of the image, v = 0).  Host arithmetic; no device needed."""
+    npdt, _ = _dt(prec)
+    c, cp = _arr(camera12, npdt)
+    assert c.shape == (12,)
+    lens = make_lens(model, width, height, sample, seed, row0, rows, lens_radius)
+    n = (rows or height) * width
+    out = np.empty((n if 0 < n <= MAX_RAYS else 1, 6), dtype=npdt)      # (a refused size: the entry says so)
+    fn = lib().spira_camera_rays_f32 if prec == "f32" else lib().spira_camera_rays_f64
+    _check(fn(cp, C.byref(lens), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def camera_rays_device(camera12, model, width, height, d_rays_ptr, sample=0, seed=0, row0=0, rows=0, lens_radius=0.0, stream_ptr=0, prec="f32"):
+    """spira_camera_rays_device_*: the same into a DEVICE array of (rows or height) * width * 6 values, asynchronous on the stream."""
+    npdt, _ = _dt(prec)
+    c, cp = _arr(camera12, npdt)
+    assert c.shape == (12,)
+    lens = make_lens(model, width, height, sample, seed, row0, rows, lens_radius)
+    fn = lib().spira_camera_rays_device_f32 if prec == "f32" else lib().spira_camera_rays_device_f64
+    _check(fn(cp, C.byref(lens), C.c_void_p(d_rays_ptr or None), C.c_void_p(stream_ptr or None)))
+
+
+def radiance_plan(n_rays, spp, num_cus):
+    """The launch plan a radiance call of n_rays x spp gets on a device of num_cus compute units (test support; no device needed): a dict of grid, wpb,
+    spp_pass, n_pass, direct, ws_entries, max_items — pass p covers the samples [p * spp_pass, min((p + 1) * spp_pass, spp))."""
+    out = (C.c_uint32 * 8)()
+    _check(lib().spira_debug_radiance_plan(C.c_uint32(n_rays), C.c_uint32(spp), C.c_uint32(num_cus), out))
+    v = [int(x) for x in out]
+    return {"grid": v[0], "wpb": v[1], "spp_pass": v[2], "n_pass": v[3], "direct": bool(v[4]), "ws_entries": v[5] | (v[6] << 32), "max_items": v[7]}
 
 
 def cast_plan(n_rays, num_cus):

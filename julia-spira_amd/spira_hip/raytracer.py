@@ -69,7 +69,7 @@ class Camera:
         c = B.camera_lookat(position.tolist(), look_at.tolist(), up.tolist(), fov, aspect_ratio, focus_dist, prec="f64")
         self.position = position
         self.lower_left_corner, self.horizontal, self.vertical = Vec3(*c[3:6]), Vec3(*c[6:9]), Vec3(*c[9:12])
-        self.lens_radius = aperture / 2   # stored, unused (:293, :299-300)
+        self.lens_radius = aperture / 2   # :293; the reference's get_ray ignores it (:299-300) — render(..., defocus=True) gives it its thin lens
         self._flat = c
 
     def flat(self):
@@ -174,12 +174,20 @@ def to_acescg(color):
     return B.tonemap(a, B.POST_ACES).reshape(a.shape)
 
 
-def render(world, camera, width, height, samples_per_pixel=50, max_depth=20, seed=0, precision="f64", kernel=B.KERNEL_WAVEFRONT):
+def render(world, camera, width, height, samples_per_pixel=50, max_depth=20, seed=0, precision="f64", kernel=B.KERNEL_WAVEFRONT, defocus=False):
     """render(world, camera, width, height; samples_per_pixel=50, max_depth=20) (:387-421).
 
     Returns (img, hdr_data): img (H, W, 3) Float32 after to_acescg, hdr_data (H, W, 3) linear means.
+    defocus=True with a camera of aperture > 0: the frame is traced through a thin lens of radius aperture / 2 (cameras.ThinLens over
+    Scene.radiance) instead of the reference's pinhole; otherwise, and by default, the reference's path exactly as before.
     """
     spheres5, materials8, triangles10 = flatten_world(world)
+    if defocus and camera.lens_radius > 0:
+        from . import cameras
+        with B.Scene(spheres5, materials8, triangles10, prec=precision) as scene:
+            hdr = cameras.render(scene, cameras.ThinLens(camera.flat(), camera.lens_radius), width, height, samples_per_pixel, max_depth, seed=seed)
+        hdr = np.ascontiguousarray(np.moveaxis(hdr, 0, -1))
+        return to_acescg(hdr), hdr
     p = B.make_params(width, height, samples_per_pixel, max_depth, len(spheres5), len(materials8),
                       0 if triangles10 is None else len(triangles10), flags=B.SEM_A | kernel | B.POST_ACES, seed=seed)
     hdr, img = B.render(spheres5, materials8, triangles10, camera.flat(), p, prec=precision, want_hdr=True, want_img=True)
