@@ -428,6 +428,74 @@ int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, dou
 int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream);
 int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream);
 
+/* ---- hemisphere gather at surface points: irradiance sums and visibility counts for light probes, irradiance points and lightmap texels ----
+ * The reference has no baker; what these entries integrate is ray_color (examples/julia-raytracer.jl:328-367) and the hit scan (:242-258), over directions
+ * drawn by the reference's own rejection idiom (random_in_unit_sphere, :309-316).  The caller gives POINTS; the library draws the hemisphere directions with
+ * its own RNG inside the kernel, so a lightmap of n points at spp samples is one call on n x 6 values, not n * spp rays.
+ * points6: n_points x [px py pz nx ny nz] in the call's precision T.  The sampling rule, in T, in the written order, nothing fused:
+ *   validity   a point is INVALID when any of its six values is NaN or infinite, or (nx nx + ny ny) + nz nz is not finite or is below the smallest normal
+ *              number of T — the radiance entry's rule for a ray, applied to the six values.  Otherwise nh = n / sqrt(n.n).
+ *   q          for point k and sample s, the rejection idiom under the key rng_key(sA, sB, key0 + k, s, 255): tries t = 1 .. 64, scale 2^-20,
+ *              q = (2 u0 - 1, 2 u1 - 1, 2 u2 - 1), accepted when (q.x q.x + q.y q.y) + q.z q.z < 1, else q = 0.  Bounce 255 is the lens's slot of
+ *              spira_camera_rays_*: no path reaches it (bounces 0 .. 254) and a gather has no lens; the path's own keys are left alone.
+ *   direction  qh = q / sqrt(q.q), or 0 when q.q is below the smallest normal number of T; v = nh + qh — a unit normal plus a uniform point on the unit
+ *              sphere is exactly cosine-weighted.  Where [p, v] is no valid ray for the radiance entry (v cancelled to nothing), v = nh.
+ *   ray        [p, v], v NOT normalised: the radiance entry and the ray queries normalise it with the one formula the gather kernels use.
+ *   invalid    the generator writes six zeros, which the radiance entry and the ray queries classify as invalid themselves.
+ * So every number below is, by construction, what the existing entries give for the ray lists of spira_gather_rays_*.
+ *
+ * spira_gather_rays_*: rays6 = the ray list (n_points x 6) of ONE sample of every point.  The host form is host arithmetic (the same inline function the
+ * kernels call; no device needed).  The *_device_* form takes DEVICE pointers, is asynchronous on `stream`, synchronises and allocates nothing.
+ * Limits: NULL pointers, n_points == 0: SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS, key0 + n_points > 2^32, sample >= SPIRA_MAX_SPP: SPIRA_E_LIMIT.
+ *
+ * spira_scene_gather_*: for every valid point k and every sample s in sample0 .. sample0 + spp - 1, the path spira_scene_radiance_* traces along the ray
+ * [p, v(k, s)] at pixel key key0 + k, sample s; sum_rgb (n_points x 3, INTERLEAVED, caller-owned) takes sum = sum + L_s per channel in T, one addition
+ * per sample in ascending sample order.  So k calls of n samples leave bit for bit the sums of one call of k*n samples, and a point list gathered in chunks
+ * (key0 advanced by the points before the chunk) leaves bit for bit the sums of the whole list.  Irradiance is pi * sum / spp (the directions are
+ * cosine-weighted): that scaling is the caller's — the entry returns sums, like every accumulate entry.  out_valid[k] = 0 and nothing added for an
+ * invalid point, 1 otherwise; out_valid may be NULL, sum_rgb may not.  The struct is spira_radiance, unchanged; flags: 0, SPIRA_EXT_DIELECTRIC,
+ * SPIRA_EXT_SPECTRAL, any other bit SPIRA_E_UNSUPPORTED.  Errors, limits (n_points for n_rays), stream ordering, multi-device handles and the workspace
+ * are spira_scene_radiance_*'s: every check before any device is touched; a call enqueued after a device-form update or rebuild on another stream sees
+ * the new tree; the device form allocates only on its first call at a size (a call of one sample per point needs no workspace), and the workspace stays
+ * in the device context until spira_shutdown.  n_points * spp may exceed 2^32: the call is split into passes by samples.
+ *
+ * spira_scene_gather_visible_*: adds to visible_u32[k] the number of samples s in sample0 .. sample0 + spp - 1 for which spira_scene_occluded_* answers 0
+ * for the ray [p, t_min, v(k, s), t_max] (t_min, t_max rounded to T once; distances along the unit direction).  out_valid[k] = 0 and nothing added where
+ * the point is invalid or breaks the ray queries' origin rule (scenes with a tree; the rule reads the origin only, so it holds for all samples of a point
+ * or for none), 1 otherwise.  Ambient occlusion is 1 - visible / spp.  flags: 0, the refilled traversal sessions of the ray queries over generated rays,
+ * or SPIRA_CAST_INPLACE, one lane per (point, sample) — identical bytes; scenes without a tree run one lane per item either way.
+ * Errors, all decided before any device is touched: NULL points, struct or visible_u32, n_points == 0, spp == 0, a NaN in t_min / t_max, t_min < 0,
+ * t_max < t_min (t_max = +Inf is allowed), unknown flag bits, a NULL or destroyed handle, one of the other precision or of another device:
+ * SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS, key0 + n_points > 2^32, sample0 + spp > SPIRA_MAX_SPP: SPIRA_E_LIMIT.  The host form copies points in,
+ * visible_u32 in AND out, out_valid out.  The *_device_* form is asynchronous on `stream`, synchronises and allocates nothing, and is ordered like every
+ * entry.  spira_get_counters is not affected by any of these entries. */
+typedef struct spira_gather_visible {
+    uint32_t spp, sample0;
+    uint64_t seed;
+    uint32_t key0, flags;            /* 0 or SPIRA_CAST_INPLACE */
+    double   t_min, t_max;
+} spira_gather_visible;              /* 40 bytes */
+int spira_gather_rays_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6);
+int spira_gather_rays_f64(const double *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *rays6);
+int spira_gather_rays_device_f32(const float *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *d_rays6, void *stream);
+int spira_gather_rays_device_f64(const double *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *d_rays6, void *stream);
+int spira_scene_gather_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_radiance *rp,
+                           float *sum_rgb, uint8_t *out_valid);
+int spira_scene_gather_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_radiance *rp,
+                           double *sum_rgb, uint8_t *out_valid);
+int spira_scene_gather_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_radiance *rp,
+                                  float *d_sum_rgb, uint8_t *d_out_valid, void *stream);
+int spira_scene_gather_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_radiance *rp,
+                                  double *d_sum_rgb, uint8_t *d_out_valid, void *stream);
+int spira_scene_gather_visible_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_gather_visible *gv,
+                                   uint32_t *visible_u32, uint8_t *out_valid);
+int spira_scene_gather_visible_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_gather_visible *gv,
+                                   uint32_t *visible_u32, uint8_t *out_valid);
+int spira_scene_gather_visible_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_gather_visible *gv,
+                                          uint32_t *d_visible_u32, uint8_t *d_out_valid, void *stream);
+int spira_scene_gather_visible_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_gather_visible *gv,
+                                          uint32_t *d_visible_u32, uint8_t *d_out_valid, void *stream);
+
 /* ---- progressive accumulation (checkpoint / resume / adaptive sampling) ----
  * The contract the reference's kernel was designed for and no host code uses: `current_sample_index`,
  * persisted `rng_states`, `output_hdr_image[p] += L` (src/spira_path_trace_kernel.metal:143-145, :252-268).

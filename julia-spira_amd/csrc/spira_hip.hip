@@ -44,6 +44,7 @@
 #include "spira_lbvh.h"
 #include "spira_query.h"
 #include "spira_radiance.h"
+#include "spira_gather.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -80,6 +81,10 @@ int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uin
                   bool any, bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
+int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
+int gather_visible_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                            bool on_device, void *user_stream);
+int gather_rays_impl_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6, bool on_device, void *user_stream);
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
@@ -161,6 +166,7 @@ struct Ctx {
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
     DevBuf cast_io;                               // spira_scene_cast_* / spira_scene_occluded_*: the host form's staged rays and outputs
     DevBuf radiance_io;                           // spira_scene_radiance_*: the host form's staged rays, sums and valid bytes (its workspace is L)
+    DevBuf gather_io;                             // spira_scene_gather_* / spira_scene_gather_visible_*: the host form's staged points, sums / counts and valid bytes
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
     uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
     DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
@@ -1680,6 +1686,187 @@ int camera_rays_entry(const T *camera12, const spira_lens *lens, T *rays6, bool 
         return camera_rays_impl<T>(camera12, lens, rays6, on_device, user_stream);
 }
 
+// ======================================================================= spira_scene_gather_* / spira_scene_gather_visible_* / spira_gather_rays_*: hemisphere gather at surface points
+// Kernels and the sampling rule: spira_gather.h; launch arithmetic: spira_plan.h (make_gather_plan).  The radiance gather is radiance_impl's call over
+// points: one k_gather launch per pass (+ k_gather_sum where a pass holds more than one sample per point), the workspace of such a pass the context's L.
+// The visibility gather runs the same passes with one launch each and no workspace: its device form allocates nothing.  The host forms stage points,
+// sums or counts and valid bytes in gather_io.  The counters of the last render are left as they are.
+spira::GatherKnobs read_gather_knobs() {
+    spira::GatherKnobs k;
+    k.waves_per_cu = env_u32("SPIRA_GATHER_WAVES_PER_CU", SPIRA_GATHER_WAVES_PER_CU);
+    k.max_items = env_u32("SPIRA_GATHER_MAX_ITEMS", SPIRA_GATHER_MAX_ITEMS);
+    return k;
+}
+template <class T>
+int launch_gather(dim3 grid, size_t lds, hipStream_t st, const spira::GatherArgs<T> &a) {
+    const dim3 block(spira::kBlock);
+    const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    if (a.scene.n_bvh_tris) return ext ? launch_lds(spira::k_gather<T, true, true>, grid, block, lds, st, a) : launch_lds(spira::k_gather<T, true, false>, grid, block, lds, st, a);
+    return ext ? launch_lds(spira::k_gather<T, false, true>, grid, block, lds, st, a) : launch_lds(spira::k_gather<T, false, false>, grid, block, lds, st, a);
+}
+template <class T>
+int gather_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::gather_check(points6 != nullptr, rp != nullptr, sum_rgb != nullptr, n_points, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
+                                     rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
+    if (int rc = check_handle<T>(h)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
+
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)c.num_cus, spira::kBlock, read_gather_knobs());
+    if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
+    spira::GatherArgs<T> a{};
+    scene_pointers<T>(h->store, a.scene);
+    spira_params fake{};
+    fake.flags = rp->flags;
+    if (int rc = attach_spd<T>(c, st, &fake, a.scene)) return rc;
+    spira::seed_halves(rp->seed, a.rc.sA, a.rc.sB);
+    a.rc.flags = rp->flags; a.rc.max_depth = rp->max_depth; a.rc.spp = rp->spp;
+    a.points = points6; a.n_points = n_points; a.sum = sum_rgb; a.valid = out_valid; a.key0 = rp->key0;
+    a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
+    const size_t n = n_points, pt_b = 6 * n * sizeof(T), sum_b = 3 * n * sizeof(T);
+    if (!on_device) {
+        // [points | sums | valid]: every block starts at a multiple of sizeof(T)
+        if (int rc = c.gather_io.ensure(pt_b + sum_b + n)) return rc;
+        char *base = (char *)c.gather_io.p;
+        HIP_TRY(hipMemcpyAsync(base, points6, pt_b, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + pt_b, sum_rgb, sum_b, hipMemcpyHostToDevice, st));
+        a.points = (const T *)base;
+        a.sum = (T *)(base + pt_b);
+        a.valid = out_valid ? (uint8_t *)(base + pt_b + sum_b) : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t items = pl.items(pass);
+        if (items > spira::kRadianceMaxItems) return fail(SPIRA_E_LIMIT, "internal: a gather pass holds more items than an index reaches");
+        a.sample_first = rp->sample0 + pl.first(pass);
+        a.spp_pass = pl.count(pass);
+        a.n_items = (uint32_t)items;
+        a.fd_spp = spira::fastdiv_make(a.spp_pass);
+        a.write_valid = pass == 0 ? 1u : 0u;
+        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+        if (a.ws && items * sizeof(spira::Pack3<T>) > c.L.cap) return fail(SPIRA_E_LIMIT, "internal: the gather workspace is smaller than the pass");
+        if (int rc = launch_gather<T>(dim3(pl.grid), lds, st, a)) return rc;
+        if (a.ws) hipLaunchKernelGGL(spira::k_gather_sum<T>, dim3(pl.grid_flat), dim3(spira::kBlock), 0, st, a);
+    }
+    if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(sum_rgb, a.sum, sum_b, hipMemcpyDeviceToHost, st));
+        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
+    }
+    return s.close();
+}
+template <class T>
+int gather_entry(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::gather_impl_f32(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
+    else
+#endif
+        return gather_impl<T>(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
+}
+
+template <class T>
+int launch_gather_visible(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::GatherVisibleArgs<T> &a) {
+    const dim3 block(spira::kBlock), flat(cp.grid_flat);
+    if (a.scene.n_bvh_tris && !inplace)
+        return launch_lds(spira::k_gather_visible_session<T>, dim3(cp.grid), block, lds + (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb, st, a);
+    if (a.scene.n_bvh_tris) return launch_lds(spira::k_gather_visible<T, true, false>, flat, block, lds, st, a);
+    if (a.scene.n_triangles) return launch_lds(spira::k_gather_visible<T, false, true>, flat, block, lds, st, a);
+    return launch_lds(spira::k_gather_visible<T, false, false>, flat, block, lds, st, a);
+}
+template <class T>
+int gather_visible_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                        bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::gather_visible_check(points6 != nullptr, gv != nullptr, visible != nullptr, n_points, gv ? gv->spp : 1, gv ? gv->sample0 : 0, gv ? gv->key0 : 0,
+                                             gv ? gv->flags : 0, gv ? gv->t_min : 0.0, gv ? gv->t_max : 0.0, &msg)) return fail(rc, msg);
+    if (int rc = check_handle<T>(h)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
+
+    const spira::GatherKnobs knobs = read_gather_knobs();
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, gv->spp, (uint32_t)c.num_cus, spira::kBlock, knobs);
+    spira::GatherVisibleArgs<T> a{};
+    scene_pointers<T>(h->store, a.scene);
+    a.scene.spd = nullptr;
+    spira::seed_halves(gv->seed, a.sA, a.sB);
+    a.points = points6; a.n_points = n_points; a.visible = visible; a.valid = out_valid; a.key0 = gv->key0;
+    a.t_min = (T)gv->t_min; a.t_max = (T)gv->t_max;
+    const size_t n = n_points, pt_b = 6 * n * sizeof(T), cnt_b = n * sizeof(uint32_t);
+    if (!on_device) {
+        // [points | counts | valid]: every block starts at a multiple of 4
+        if (int rc = c.gather_io.ensure(pt_b + cnt_b + n)) return rc;
+        char *base = (char *)c.gather_io.p;
+        HIP_TRY(hipMemcpyAsync(base, points6, pt_b, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(base + pt_b, visible, cnt_b, hipMemcpyHostToDevice, st));
+        a.points = (const T *)base;
+        a.visible = (uint32_t *)(base + pt_b);
+        a.valid = out_valid ? (uint8_t *)(base + pt_b + cnt_b) : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    const bool inplace = (gv->flags & SPIRA_CAST_INPLACE) != 0;
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t items = pl.items(pass);
+        if (items > spira::kRadianceMaxItems) return fail(SPIRA_E_LIMIT, "internal: a gather pass holds more items than an index reaches");
+        a.sample_first = gv->sample0 + pl.first(pass);
+        a.spp_pass = pl.count(pass);
+        a.n_items = (uint32_t)items;
+        a.fd_spp = spira::fastdiv_make(a.spp_pass);
+        a.write_valid = pass == 0 ? 1u : 0u;
+        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+        const spira::CastPlan cp = spira::make_gather_visible_plan(a.n_items, (uint32_t)c.num_cus, spira::kBlock, knobs, read_cast_knobs());
+        a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+        if (int rc = launch_gather_visible<T>(cp, inplace, lds, st, a)) return rc;
+    }
+    if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(visible, a.visible, cnt_b, hipMemcpyDeviceToHost, st));
+        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
+    }
+    return s.close();
+}
+template <class T>
+int gather_visible_entry(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                         bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::gather_visible_impl_f32(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
+    else
+#endif
+        return gather_visible_impl<T>(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
+}
+
+// The generator: the host form runs gather_ray_generate<T> here, the device form launches k_gather_rays<T> over the same function.
+template <class T>
+int gather_rays_impl(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::gather_rays_check(points6 != nullptr, rays6 != nullptr, n_points, sample, key0, &msg)) return fail(rc, msg);
+    uint32_t sA, sB;
+    spira::seed_halves(seed, sA, sB);
+    if (!on_device) {
+        for (uint32_t k = 0; k < n_points; ++k) spira::gather_ray_generate<T>(points6 + 6 * (size_t)k, sA, sB, key0 + k, sample, rays6 + 6 * (size_t)k);
+        return 0;
+    }
+    Session s;
+    if (int rc = Session::open(s, true, user_stream)) return rc;
+    spira::GatherRaysArgs<T> a{};
+    a.points = points6; a.rays = rays6; a.n = n_points; a.sample = sample; a.sA = sA; a.sB = sB; a.key0 = key0;
+    hipLaunchKernelGGL(spira::k_gather_rays<T>, dim3((n_points + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
+    return s.close();
+}
+template <class T>
+int gather_rays_entry(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::gather_rays_impl_f32(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
+    else
+#endif
+        return gather_rays_impl<T>(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
+}
+
 // ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
 // The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
 // walk or the node format is involved: a refit rewrites boxes, and the walk only prunes with them.
@@ -2732,6 +2919,16 @@ int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32
 int spira_tu::camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream) {
     return camera_rays_impl<float>(camera12, lens, rays6, on_device, user_stream);
 }
+int spira_tu::gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    return gather_impl<float>(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
+}
+int spira_tu::gather_visible_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                                      bool on_device, void *user_stream) {
+    return gather_visible_impl<float>(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
+}
+int spira_tu::gather_rays_impl_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6, bool on_device, void *user_stream) {
+    return gather_rays_impl<float>(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
+}
 int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                                float *out_hdr, float *out_img, bool on_device, void *user_stream) {
     return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
@@ -2829,6 +3026,56 @@ int spira_debug_radiance_plan(uint32_t n_rays, uint32_t spp, uint32_t num_cus, u
     if (!out8 || n_rays == 0 || n_rays > SPIRA_MAX_RAYS || spp == 0 || spp > SPIRA_MAX_SPP)
         return fail(SPIRA_E_INVALID, "spira_debug_radiance_plan: out8 is NULL, n_rays outside 1 .. SPIRA_MAX_RAYS or spp outside 1 .. SPIRA_MAX_SPP");
     const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, spp, num_cus, spira::kBlock, read_radiance_knobs());
+    const uint32_t v[8] = {pl.grid, pl.wpb, pl.spp_pass, pl.n_pass, pl.direct ? 1u : 0u, (uint32_t)pl.ws_entries, (uint32_t)(pl.ws_entries >> 32), pl.max_items};
+    std::memcpy(out8, v, sizeof v);
+    return 0;
+}
+
+// ---- hemisphere gather at surface points (spira_gather.h)
+int spira_gather_rays_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6) {
+    return gather_rays_entry<float>(points6, n_points, sample, seed, key0, rays6, false, nullptr);
+}
+int spira_gather_rays_f64(const double *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *rays6) {
+    return gather_rays_entry<double>(points6, n_points, sample, seed, key0, rays6, false, nullptr);
+}
+int spira_gather_rays_device_f32(const float *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *d_rays6, void *stream) {
+    return gather_rays_entry<float>(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
+}
+int spira_gather_rays_device_f64(const double *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *d_rays6, void *stream) {
+    return gather_rays_entry<double>(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
+}
+int spira_scene_gather_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid) {
+    return gather_entry<float>(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
+}
+int spira_scene_gather_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_radiance *rp, double *sum_rgb, uint8_t *out_valid) {
+    return gather_entry<double>(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
+}
+int spira_scene_gather_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_radiance *rp, float *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
+    return gather_entry<float>(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
+}
+int spira_scene_gather_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_radiance *rp, double *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
+    return gather_entry<double>(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
+}
+int spira_scene_gather_visible_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible_u32, uint8_t *out_valid) {
+    return gather_visible_entry<float>(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
+}
+int spira_scene_gather_visible_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible_u32, uint8_t *out_valid) {
+    return gather_visible_entry<double>(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
+}
+int spira_scene_gather_visible_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *d_visible_u32,
+                                          uint8_t *d_out_valid, void *stream) {
+    return gather_visible_entry<float>(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
+}
+int spira_scene_gather_visible_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *d_visible_u32,
+                                          uint8_t *d_out_valid, void *stream) {
+    return gather_visible_entry<double>(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
+}
+// Test support, outside the ABI like spira_debug_radiance_plan: the plan a gather of n_points x spp gets on a device of num_cus CUs, with the knobs of the
+// environment as the entries read them.  out8: grid, wpb, spp_pass, n_pass, direct, workspace entries (low, high word), the item cap.  No device needed.
+int spira_debug_gather_plan(uint32_t n_points, uint32_t spp, uint32_t num_cus, uint32_t *out8) {
+    if (!out8 || n_points == 0 || n_points > SPIRA_MAX_RAYS || spp == 0 || spp > SPIRA_MAX_SPP)
+        return fail(SPIRA_E_INVALID, "spira_debug_gather_plan: out8 is NULL, n_points outside 1 .. SPIRA_MAX_RAYS or spp outside 1 .. SPIRA_MAX_SPP");
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, spp, num_cus, spira::kBlock, read_gather_knobs());
     const uint32_t v[8] = {pl.grid, pl.wpb, pl.spp_pass, pl.n_pass, pl.direct ? 1u : 0u, (uint32_t)pl.ws_entries, (uint32_t)(pl.ws_entries >> 32), pl.max_items};
     std::memcpy(out8, v, sizeof v);
     return 0;
@@ -2950,7 +3197,7 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release(); c.cast_io.release(); c.radiance_io.release();
+        c.refit_status.release(); c.cast_io.release(); c.radiance_io.release(); c.gather_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);

@@ -467,4 +467,70 @@ inline int camera_rays_check(uint32_t model, uint32_t width, uint32_t height, ui
     return 0;
 }
 
+// ---- hemisphere gather at surface points (spira_scene_gather_*, spira_scene_gather_visible_*, spira_gather_rays_*); kernels in spira_gather.h.
+// A work item is (point, sample), sample-minor, and a pass is split by samples under an item cap exactly as a radiance call's is: the plan IS
+// make_radiance_plan's with the gather's own knobs.  n_points <= 2^26 and spp <= 2^24 multiply to 2^50 items in a call; no pass ever holds more than
+// max(n_points, max_items) <= 2^26 of them, and every product here is formed in 64 bits.  The visibility entries split into the same passes and lay a
+// CastPlan (make_cast_plan) over each pass's items for the session kernel.
+struct GatherKnobs { uint32_t waves_per_cu = 64, max_items = kRadianceMaxItems; };      // SPIRA_GATHER_WAVES_PER_CU (0: one workgroup), SPIRA_GATHER_MAX_ITEMS
+using GatherPlan = RadiancePlan;
+// n_points in 1 .. SPIRA_MAX_RAYS, spp in 1 .. SPIRA_MAX_SPP (gather_check)
+inline GatherPlan make_gather_plan(uint32_t n_points, uint32_t spp, uint32_t num_cus, uint32_t block, const GatherKnobs &k) {
+    RadianceKnobs rk;
+    rk.waves_per_cu = k.waves_per_cu; rk.max_items = k.max_items;
+    return make_radiance_plan(n_points, spp, num_cus, block, rk);
+}
+// the session plan of one pass of a visibility gather: n_items of the pass, one workgroup where the gather's waves_per_cu is 0
+inline CastPlan make_gather_visible_plan(uint32_t n_items, uint32_t num_cus, uint32_t block, const GatherKnobs &k, const CastKnobs &ck) {
+    if (k.waves_per_cu != 0) return make_cast_plan(n_items, num_cus, block, ck);
+    CastKnobs one = ck;
+    one.waves_per_cu = std::max<uint32_t>(1, block / 64);
+    CastPlan p = make_cast_plan(n_items, 1, block, one);
+    p.grid_flat = 1;
+    return p;
+}
+inline int gather_points_check(bool points, uint32_t n_points, uint32_t key0, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (n_points > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) points"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)key0 + n_points > (1ull << 32)) { *msg = "key0 + n_points exceeds 2^32"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+// spira_gather_rays_*
+inline int gather_rays_check(bool points, bool rays, uint32_t n_points, uint32_t sample, uint32_t key0, const char **msg) {
+    if (!rays) { *msg = "the ray array is NULL"; return SPIRA_E_INVALID; }
+    if (int rc = gather_points_check(points, n_points, key0, msg)) return rc;
+    if (sample >= SPIRA_MAX_SPP) { *msg = "sample index must be below 2^24"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+// spira_scene_gather_*: radiance_check's rules and order, on a point list
+inline int gather_check(bool points, bool params, bool sums, uint32_t n_points, uint32_t spp, uint32_t max_depth, uint32_t flags, uint32_t sample0, uint32_t key0,
+                        uint32_t reserved, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (!params) { *msg = "the spira_radiance struct is NULL"; return SPIRA_E_INVALID; }
+    if (!sums) { *msg = "sum_rgb is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (spp == 0) { *msg = "spp is 0"; return SPIRA_E_INVALID; }
+    if (max_depth < 1 || max_depth > SPIRA_MAX_DEPTH) { *msg = "max_depth must be 1 .. SPIRA_MAX_DEPTH (255)"; return SPIRA_E_INVALID; }
+    if (reserved != 0) { *msg = "spira_radiance::reserved must be 0"; return SPIRA_E_INVALID; }
+    if (flags & ~(SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) { *msg = "flags: 0, SPIRA_EXT_DIELECTRIC and SPIRA_EXT_SPECTRAL are all the gather entries take"; return SPIRA_E_UNSUPPORTED; }
+    if (int rc = gather_points_check(true, n_points, key0, msg)) return rc;
+    if ((uint64_t)sample0 + spp > SPIRA_MAX_SPP) { *msg = "sample0 + spp exceeds 2^24"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+// spira_scene_gather_visible_*
+inline int gather_visible_check(bool points, bool params, bool counts, uint32_t n_points, uint32_t spp, uint32_t sample0, uint32_t key0, uint32_t flags,
+                                double t_min, double t_max, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (!params) { *msg = "the spira_gather_visible struct is NULL"; return SPIRA_E_INVALID; }
+    if (!counts) { *msg = "visible_u32 is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (spp == 0) { *msg = "spp is 0"; return SPIRA_E_INVALID; }
+    if (t_min != t_min || t_max != t_max || t_min < 0 || t_max < t_min) { *msg = "t_min and t_max: no NaN, 0 <= t_min <= t_max (t_max may be +Inf)"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (int rc = gather_points_check(true, n_points, key0, msg)) return rc;
+    if ((uint64_t)sample0 + spp > SPIRA_MAX_SPP) { *msg = "sample0 + spp exceeds 2^24"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+
 }  // namespace spira

@@ -19,7 +19,7 @@ using Colors
 
 export Scene, Camera, Ray, Sphere, Material, Point3, Vec3, Color,
        render_hybrid_gpu, render_with_cpu, render, render_multi, create_scene, prepare_scene_data,
-       SceneHandle, destroy!, update!, rebuild!, save_png, save_exr
+       SceneHandle, destroy!, update!, rebuild!, gather_rays, gather_rays!, save_png, save_exr
 
 const libspira = get(ENV, "SPIRA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libspira_hip.so"))
 
@@ -223,6 +223,38 @@ function rebuild!(h::SceneHandle, d_triangles::Ptr{Float64}; stream::Ptr{Cvoid}=
     rc = ccall((:spira_scene_rebuild_device_f64, libspira), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), h.ptr, d_triangles, stream)
     rc == 0 || spira_error(rc)
     return h
+end
+
+# The hemisphere rays of one sample of every surface point (spira_gather_rays_*): points6 = 6 n values [px py pz nx ny nz] per point, the result 6 n values
+# [p, v] per point, v cosine-weighted about the point's normal and not normalised (six zeros for an invalid point); point k draws under pixel key key0 + k.
+# Host arithmetic: no device needed.  The list is what spira_scene_radiance_* / spira_scene_occluded_* take; the gather entries themselves
+# (spira_scene_gather_*, spira_scene_gather_visible_*) draw these directions inside their kernels.
+function gather_rays(points6::Vector{Float32}; sample::Integer=0, seed::Integer=0, key0::Integer=0)
+    rays = Vector{Float32}(undef, length(points6))
+    rc = ccall((:spira_gather_rays_f32, libspira), Cint, (Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{Float32}),
+               points6, length(points6) ÷ 6, sample, seed, key0, rays)
+    rc == 0 || spira_error(rc)
+    return rays
+end
+function gather_rays(points6::Vector{Float64}; sample::Integer=0, seed::Integer=0, key0::Integer=0)
+    rays = Vector{Float64}(undef, length(points6))
+    rc = ccall((:spira_gather_rays_f64, libspira), Cint, (Ptr{Float64}, UInt32, UInt32, UInt64, UInt32, Ptr{Float64}),
+               points6, length(points6) ÷ 6, sample, seed, key0, rays)
+    rc == 0 || spira_error(rc)
+    return rays
+end
+# The device forms: n points in DEVICE memory to n rays in DEVICE memory, asynchronous on `stream`.
+function gather_rays!(d_rays::Ptr{Float32}, d_points6::Ptr{Float32}, n::Integer; sample::Integer=0, seed::Integer=0, key0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_gather_rays_device_f32, libspira), Cint, (Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{Float32}, Ptr{Cvoid}),
+               d_points6, n, sample, seed, key0, d_rays, stream)
+    rc == 0 || spira_error(rc)
+    return d_rays
+end
+function gather_rays!(d_rays::Ptr{Float64}, d_points6::Ptr{Float64}, n::Integer; sample::Integer=0, seed::Integer=0, key0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_gather_rays_device_f64, libspira), Cint, (Ptr{Float64}, UInt32, UInt32, UInt64, UInt32, Ptr{Float64}, Ptr{Cvoid}),
+               d_points6, n, sample, seed, key0, d_rays, stream)
+    rc == 0 || spira_error(rc)
+    return d_rays
 end
 
 function render_hybrid_gpu(width::Int, height::Int, h::SceneHandle, camera::Camera;

@@ -52,6 +52,9 @@ EXPORTS = [
     "spira_scene_occluded_f32", "spira_scene_occluded_f64", "spira_scene_occluded_device_f32", "spira_scene_occluded_device_f64",
     "spira_scene_radiance_f32", "spira_scene_radiance_f64", "spira_scene_radiance_device_f32", "spira_scene_radiance_device_f64",
     "spira_camera_rays_f32", "spira_camera_rays_f64", "spira_camera_rays_device_f32", "spira_camera_rays_device_f64",
+    "spira_gather_rays_f32", "spira_gather_rays_f64", "spira_gather_rays_device_f32", "spira_gather_rays_device_f64",
+    "spira_scene_gather_f32", "spira_scene_gather_f64", "spira_scene_gather_device_f32", "spira_scene_gather_device_f64",
+    "spira_scene_gather_visible_f32", "spira_scene_gather_visible_f64", "spira_scene_gather_visible_device_f32", "spira_scene_gather_visible_device_f64",
 ]
 
 
@@ -98,6 +101,12 @@ class Lens(C.Structure):
     """spira_lens: camera model, image size, sample, seed and row range of a generated ray list."""
     _fields_ = [("model", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("sample", C.c_uint32),
                 ("seed", C.c_uint64), ("row0", C.c_uint32), ("rows", C.c_uint32), ("lens_radius", C.c_double)]
+
+
+class GatherVisible(C.Structure):
+    """spira_gather_visible: the samples, seed, pixel keys and distance range of a visibility gather on a point list."""
+    _fields_ = [("spp", C.c_uint32), ("sample0", C.c_uint32), ("seed", C.c_uint64), ("key0", C.c_uint32), ("flags", C.c_uint32),
+                ("t_min", C.c_double), ("t_max", C.c_double)]
 
 
 _lib = None
@@ -477,6 +486,94 @@ class Scene:
         fn = lib().spira_scene_radiance_device_f32 if self.prec == "f32" else lib().spira_scene_radiance_device_f64
         _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.byref(rp), C.c_void_p(d_sums_ptr or None), C.c_void_p(d_valid_ptr or None),
                   C.c_void_p(stream_ptr or None)))
+
+
+    def _points(self, points6):
+        npdt, _ = _dt(self.prec)
+        p = np.ascontiguousarray(points6, dtype=npdt)
+        if p.ndim != 2 or p.shape[1] != 6:
+            raise ValueError("points6: n_points x [px py pz nx ny nz]")
+        return p
+
+    def gather(self, points6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
+        """spira_scene_gather_*: path-traced radiance over the hemisphere of every point of points6 (n x [px py pz nx ny nz], host array; the library
+        draws the cosine-weighted directions itself, point k under pixel key key0 + k).  ADDS samples sample0 .. sample0 + spp - 1, in order, to sums
+        ([n, 3], in place; None: a fresh zero array); irradiance is pi * sums / spp.  Returns sums, or (sums, valid uint8 [n]) with want_valid."""
+        npdt, _ = _dt(self.prec)
+        p = self._points(points6)
+        n = len(p)
+        if sums is None:
+            sums = np.zeros((n, 3), dtype=npdt)
+        if sums.dtype != npdt or not sums.flags["C_CONTIGUOUS"] or sums.shape != (n, 3):
+            raise ValueError("sums: a contiguous [n_points, 3] array of the handle's precision")
+        valid = np.empty(n, dtype=np.uint8) if want_valid else None
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        fn = lib().spira_scene_gather_f32 if self.prec == "f32" else lib().spira_scene_gather_f64
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(rp), sums.ctypes.data_as(C.c_void_p),
+                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        return (sums, valid) if want_valid else sums
+
+    def gather_device(self, d_points_ptr, n_points, spp, max_depth, d_sums_ptr, seed=0, sample0=0, key0=0, flags=0, d_valid_ptr=0, stream_ptr=0):
+        """spira_scene_gather_device_*: DEVICE addresses (d_valid_ptr 0 / None: not wanted), asynchronous on the stream; the sums are added to in place."""
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        fn = lib().spira_scene_gather_device_f32 if self.prec == "f32" else lib().spira_scene_gather_device_f64
+        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.byref(rp), C.c_void_p(d_sums_ptr or None), C.c_void_p(d_valid_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
+    def gather_visible(self, points6, spp, t_min=1e-3, t_max=float("inf"), seed=0, sample0=0, key0=0, counts=None, want_valid=False, inplace=False):
+        """spira_scene_gather_visible_*: ADDS to counts (uint32 [n], in place; None: a fresh zero array) the number of samples sample0 .. sample0 + spp - 1
+        whose hemisphere direction is unoccluded within [t_min, t_max] — what Scene.occluded answers 0 for.  Returns counts, or (counts, valid uint8 [n])
+        with want_valid (0: an invalid point, or one beyond the origin bound of a scene with a tree).  inplace: the comparison organisation."""
+        p = self._points(points6)
+        n = len(p)
+        if counts is None:
+            counts = np.zeros(n, dtype=np.uint32)
+        if counts.dtype != np.uint32 or not counts.flags["C_CONTIGUOUS"] or counts.shape != (n,):
+            raise ValueError("counts: a contiguous uint32 [n_points] array")
+        valid = np.empty(n, dtype=np.uint8) if want_valid else None
+        gv = GatherVisible(spp, sample0, seed, key0, CAST_INPLACE if inplace else 0, t_min, t_max)
+        fn = lib().spira_scene_gather_visible_f32 if self.prec == "f32" else lib().spira_scene_gather_visible_f64
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(gv), counts.ctypes.data_as(C.c_void_p),
+                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        return (counts, valid) if want_valid else counts
+
+    def gather_visible_device(self, d_points_ptr, n_points, spp, d_counts_ptr, t_min=1e-3, t_max=float("inf"), seed=0, sample0=0, key0=0, d_valid_ptr=0,
+                              stream_ptr=0, inplace=False):
+        """spira_scene_gather_visible_device_*: DEVICE addresses, asynchronous on the stream; nothing is synchronised or allocated."""
+        gv = GatherVisible(spp, sample0, seed, key0, CAST_INPLACE if inplace else 0, t_min, t_max)
+        fn = lib().spira_scene_gather_visible_device_f32 if self.prec == "f32" else lib().spira_scene_gather_visible_device_f64
+        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.byref(gv), C.c_void_p(d_counts_ptr or None), C.c_void_p(d_valid_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
+
+def gather_rays(points6, sample=0, seed=0, key0=0, prec="f32"):
+    """spira_gather_rays_*: the hemisphere rays of one sample of every point of points6 (n x [px py pz nx ny nz]) as a host array [n, 6] = [p, v], v not
+    normalised; six zeros for an invalid point.  Point k draws under pixel key key0 + k.  Host arithmetic; no device needed."""
+    npdt, _ = _dt(prec)
+    p = np.ascontiguousarray(points6, dtype=npdt)
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError("points6: n_points x [px py pz nx ny nz]")
+    out = np.empty((len(p), 6), dtype=npdt)
+    fn = lib().spira_gather_rays_f32 if prec == "f32" else lib().spira_gather_rays_f64
+    _check(fn(p.ctypes.data_as(C.c_void_p), C.c_uint32(len(p)), C.c_uint32(sample), C.c_uint64(seed), C.c_uint32(key0), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def gather_rays_device(d_points_ptr, n_points, d_rays_ptr, sample=0, seed=0, key0=0, stream_ptr=0, prec="f32"):
+    """spira_gather_rays_device_*: the same from and into DEVICE arrays of n_points * 6 values, asynchronous on the stream."""
+    _dt(prec)
+    fn = lib().spira_gather_rays_device_f32 if prec == "f32" else lib().spira_gather_rays_device_f64
+    _check(fn(C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(sample), C.c_uint64(seed), C.c_uint32(key0), C.c_void_p(d_rays_ptr or None),
+              C.c_void_p(stream_ptr or None)))
+
+
+def gather_plan(n_points, spp, num_cus):
+    """The launch plan a gather of n_points x spp gets on a device of num_cus compute units (test support; no device needed): the dict of radiance_plan —
+    pass p covers the samples [p * spp_pass, min((p + 1) * spp_pass, spp)) of every point."""
+    out = (C.c_uint32 * 8)()
+    _check(lib().spira_debug_gather_plan(C.c_uint32(n_points), C.c_uint32(spp), C.c_uint32(num_cus), out))
+    v = [int(x) for x in out]
+    return {"grid": v[0], "wpb": v[1], "spp_pass": v[2], "n_pass": v[3], "direct": bool(v[4]), "ws_entries": v[5] | (v[6] << 32), "max_items": v[7]}
 
 
 def make_lens(model, width, height, sample=0, seed=0, row0=0, rows=0, lens_radius=0.0):
