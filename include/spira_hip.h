@@ -358,6 +358,53 @@ int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_ray
 int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags,
                                     uint8_t *d_out_hit, void *stream);
 
+/* ---- closest-point queries on a scene handle: for the CALLER'S points, the nearest point of the scene's surface (distance fields, proximity, snapping) ----
+ * What Embree calls a point query, on the tree that create, update and rebuild maintain, which only prunes: prim, dist and point are bit for bit a scan's.
+ * points4: n_points x [px py pz r_max], in the call's precision T.  The scan runs over spheres [0..) then triangles [0..) in the caller's order with
+ * best = r_max * r_max (in T): object k replaces the winner exactly when d2_k <= best, then best = d2_k — the minimal squared distance wins, ties go to the
+ * later object, an object at exactly r_max counts, a NaN d2 never wins.  All arithmetic in T, in the written order, nothing fused; every dot product is
+ * (x x + y y) + z z.
+ * Triangle, on v0, e1 = v1 - v0, e2 = v2 - v0 (differences in T), with ap = p - v0, bp = ap - e1, cp = ap - e2 — Ericson's region walk, tests in this order:
+ *   1. d1 = e1.ap, d2 = e2.ap:                       d1 <= 0 && d2 <= 0               q = v0
+ *   2. d3 = e1.bp, d4 = e2.bp:                       d3 >= 0 && d4 <= d3              q = v0 + e1
+ *   3. vc = d1 d4 - d3 d2:                           vc <= 0 && d1 >= 0 && d3 <= 0    v = d1 / (d1 - d3),  q = v0 + e1 v
+ *   4. d5 = e1.cp, d6 = e2.cp:                       d6 >= 0 && d5 <= d6              q = v0 + e2
+ *   5. vb = d5 d2 - d1 d6:                           vb <= 0 && d2 >= 0 && d6 <= 0    w = d2 / (d2 - d6),  q = v0 + e2 w
+ *   6. va = d3 d6 - d5 d4, g = d4 - d3, h = d5 - d6: va <= 0 && g >= 0 && h >= 0      w = g / (g + h),     q = (v0 + e1) + (e2 - e1) w
+ *   7. otherwise:                                    s = 1 / ((va + vb) + vc), v = vb s, w = vc s,         q = (v0 + e1 v) + e2 w
+ * (the three quotients and the one reciprocal are the only divisions), then r = p - q, d2 = (r.x r.x + r.y r.y) + r.z r.z.  A triangle of zero area may
+ * give NaN and is then never picked.  Sphere (centre c, radius r as given): w = p - c, l = sqrt(w.w); l >= the smallest normal number of T: q = c + w (r / l),
+ * else q = c + (r, 0, 0); then r' = p - q and d2 by the same formula.  spira_closest_point_triangle_* is the triangle function as host arithmetic (no
+ * device is touched): out_q and out_d2 may each be NULL.
+ * Outputs, caller-owned, each may be NULL but not all of out_prim, out_dist and out_point: out_prim the object index, spheres first, as for cast; out_dist
+ * sqrt(d2) of the winner (IEEE); out_point (n_points x 3, interleaved) the winner's q; out_trips (optional, diagnostic, outside the bit-for-bit contract)
+ * the walk trips — node visits plus leaf tests — the point's lane took, 0 for scenes without a tree.
+ * A miss (no object within r_max): prim SPIRA_RAY_MISS, dist = the point's r_max copied, point 0.  An INVALID point — prim SPIRA_RAY_INVALID, dist 0,
+ * point 0 — never faults and never disturbs its neighbours: any of its four values NaN, a coordinate infinite, r_max < 0, or (scenes WITH a tree only) the
+ * origin rule of the ray queries broken for p: |(p_k - centre_k) * scale| <= 64 on every axis, in T.  r_max = +Inf is valid.
+ * Why 64 serves here too: the walk skips a child box only when a Float32 lower bound of the squared distance to it, shrunk by (1 - 2^-18), exceeds
+ * best scale^2 rounded up; the roundings of the normalised point (at most about 1.2e-5 + 1.2e-7 amax_n), of the dequantised box (6e-8 (1 + amax_n)) and of
+ * the leaf test's own q and r (2.3e-5 + 3.6e-7 amax_n) total about 3.6e-5 + 5.4e-7 amax_n against the builder's pad of 1e-4 max(1, amax_n) (the refit pad
+ * is never smaller): a margin of 2.7 or more (csrc/spira_nearest.h has the derivation).  The test is strict: equal distances still reach the later triangle.
+ * flags: 0, the library's organisation for scenes with a tree — persistent waves owning contiguous ranges of the point list and refilling their free lanes
+ * while the others keep walking — or SPIRA_CAST_INPLACE, one lane per point walking to the end, the comparison point.  prim, dist and point are identical
+ * bytes under both.  Scenes without a tree run one lane per point either way.
+ * Errors, all decided before any device is touched: a NULL point array, n_points == 0, unknown flag bits, out_prim, out_dist and out_point all NULL, a NULL
+ * or destroyed handle, one of the other precision or of another device: SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS: SPIRA_E_LIMIT.  A handle made by
+ * spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The *_device_* form
+ * takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a query enqueued after a
+ * device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+int spira_scene_closest_point_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags,
+                                  int *out_prim, float *out_dist, float *out_point, uint32_t *out_trips);
+int spira_scene_closest_point_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags,
+                                  int *out_prim, double *out_dist, double *out_point, uint32_t *out_trips);
+int spira_scene_closest_point_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags,
+                                         int *d_out_prim, float *d_out_dist, float *d_out_point, uint32_t *d_out_trips, void *stream);
+int spira_scene_closest_point_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags,
+                                         int *d_out_prim, double *d_out_dist, double *d_out_point, uint32_t *d_out_trips, void *stream);
+void spira_closest_point_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float p[3], float out_q[3], float *out_d2);
+void spira_closest_point_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double p[3], double out_q[3], double *out_d2);
+
 /* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
  * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
  * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.

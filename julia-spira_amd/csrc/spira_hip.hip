@@ -45,6 +45,7 @@
 #include "spira_query.h"
 #include "spira_radiance.h"
 #include "spira_gather.h"
+#include "spira_nearest.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -79,6 +80,8 @@ int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *ma
 int scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
 int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
                   bool any, bool on_device, void *user_stream);
+int nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point, uint32_t *out_trips,
+                     bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -165,6 +168,7 @@ struct Ctx {
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
     DevBuf cast_io;                               // spira_scene_cast_* / spira_scene_occluded_*: the host form's staged rays and outputs
+    DevBuf nearest_io;                            // spira_scene_closest_point_*: the host form's staged points and outputs
     DevBuf radiance_io;                           // spira_scene_radiance_*: the host form's staged rays, sums and valid bytes (its workspace is L)
     DevBuf gather_io;                             // spira_scene_gather_* / spira_scene_gather_visible_*: the host form's staged points, sums / counts and valid bytes
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
@@ -1568,6 +1572,69 @@ int cast_entry(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t f
         return cast_impl<T>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
 }
 
+// ======================================================================= spira_scene_closest_point_*: the nearest surface point for the caller's points
+// Kernels, the point preparation and the two closest-point functions: spira_nearest.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One
+// launch.  The device form touches no workspace of the context (it allocates nothing); the host form stages points and outputs in nearest_io.  The
+// counters of the last render are left as they are.
+template <class T>
+int launch_nearest(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::NearestArgs<T> &a) {
+    const dim3 block(spira::kBlock), flat(cp.grid_flat);
+    if (a.scene.n_bvh_tris && !inplace) return launch_lds(spira::k_nearest_session<T>, dim3(cp.grid), block, lds, st, a);
+    if (a.scene.n_bvh_tris) return launch_lds(spira::k_nearest<T, true, false>, flat, block, lds, st, a);
+    if (a.scene.n_triangles) return launch_lds(spira::k_nearest<T, false, true>, flat, block, lds, st, a);
+    return launch_lds(spira::k_nearest<T, false, false>, flat, block, lds, st, a);
+}
+template <class T>
+int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
+                 bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::nearest_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point, &msg)) return fail(rc, msg);
+    if (int rc = check_handle<T>(h)) return rc;
+    Session s;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    Ctx &c = *s.cp;
+    const hipStream_t st = s.st;
+
+    spira::NearestArgs<T> a{};
+    scene_pointers<T>(h->store, a.scene);
+    a.scene.spd = nullptr;
+    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)c.num_cus, spira::kBlock, read_cast_knobs());
+    a.points = points4; a.n_points = n_points; a.prim = out_prim; a.dist = out_dist; a.point = out_point; a.trips = out_trips;
+    a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_points, pt_b = 4 * n * sizeof(T), t_b = n * sizeof(T), prim_b = n * sizeof(int);
+    if (!on_device) {
+        // [points | dist | point | prim | trips]: every block starts at a multiple of sizeof(T) or more
+        if (int rc = c.nearest_io.ensure(pt_b + 4 * t_b + 2 * prim_b)) return rc;
+        char *base = (char *)c.nearest_io.p;
+        HIP_TRY(hipMemcpyAsync(base, points4, pt_b, hipMemcpyHostToDevice, st));
+        a.points = (const T *)base;
+        a.dist = out_dist ? (T *)(base + pt_b) : nullptr;
+        a.point = out_point ? (T *)(base + pt_b + t_b) : nullptr;
+        a.prim = out_prim ? (int *)(base + pt_b + 4 * t_b) : nullptr;
+        a.trips = out_trips ? (uint32_t *)(base + pt_b + 4 * t_b + prim_b) : nullptr;
+    }
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_nearest<T>(cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, st, a)) return rc;
+    if (!on_device) {
+        if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, a.dist, t_b, hipMemcpyDeviceToHost, st));
+        if (out_point) HIP_TRY(hipMemcpyAsync(out_point, a.point, 3 * t_b, hipMemcpyDeviceToHost, st));
+        if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, a.prim, prim_b, hipMemcpyDeviceToHost, st));
+        if (out_trips) HIP_TRY(hipMemcpyAsync(out_trips, a.trips, prim_b, hipMemcpyDeviceToHost, st));
+    }
+    return s.close();
+}
+
+template <class T>
+int nearest_entry(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
+                  bool on_device, void *user_stream) {
+#ifdef SPIRA_TU_MAIN
+    if constexpr (sizeof(T) == 4)
+        return spira_tu::nearest_impl_f32(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
+    else
+#endif
+        return nearest_impl<T>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
+}
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2913,6 +2980,10 @@ int spira_tu::cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n
                             bool any, bool on_device, void *user_stream) {
     return cast_impl<float>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
 }
+int spira_tu::nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                               uint32_t *out_trips, bool on_device, void *user_stream) {
+    return nearest_impl<float>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -3001,6 +3072,37 @@ int spira_debug_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t *out8) {
     const uint32_t v[8] = {cp.grid, cp.wpb, cp.waves, cp.base, cp.rem, cp.refill_free, cp.grid_flat, spira::kCastMinRaysPerWave};
     std::memcpy(out8, v, sizeof v);
     return 0;
+}
+
+// ---- closest-point queries on a scene handle (spira_nearest.h)
+int spira_scene_closest_point_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                                  uint32_t *out_trips) {
+    return nearest_entry<float>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
+}
+int spira_scene_closest_point_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags, int *out_prim, double *out_dist, double *out_point,
+                                  uint32_t *out_trips) {
+    return nearest_entry<double>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
+}
+int spira_scene_closest_point_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, float *d_out_dist,
+                                         float *d_out_point, uint32_t *d_out_trips, void *stream) {
+    return nearest_entry<float>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
+}
+int spira_scene_closest_point_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, double *d_out_dist,
+                                         double *d_out_point, uint32_t *d_out_trips, void *stream) {
+    return nearest_entry<double>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
+}
+// host arithmetic, no device: the triangle function the kernels and the scan call
+void spira_closest_point_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float p[3], float out_q[3], float *out_d2) {
+    float q[3], d2;
+    spira::closest_point_triangle<float>(v0, e1, e2, p, q, d2);
+    if (out_q) { out_q[0] = q[0]; out_q[1] = q[1]; out_q[2] = q[2]; }
+    if (out_d2) *out_d2 = d2;
+}
+void spira_closest_point_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double p[3], double out_q[3], double *out_d2) {
+    double q[3], d2;
+    spira::closest_point_triangle<double>(v0, e1, e2, p, q, d2);
+    if (out_q) { out_q[0] = q[0]; out_q[1] = q[1]; out_q[2] = q[2]; }
+    if (out_d2) *out_d2 = d2;
 }
 
 // ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)
@@ -3197,7 +3299,7 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release(); c.cast_io.release(); c.radiance_io.release(); c.gather_io.release();
+        c.refit_status.release(); c.cast_io.release(); c.nearest_io.release(); c.radiance_io.release(); c.gather_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);

@@ -386,6 +386,15 @@ inline int cast_check(bool rays, uint32_t n_rays, uint32_t flags, bool any_outpu
     if (n_rays > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) rays"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_closest_point_*: cast_check's rules for a point list
+inline int nearest_check(bool points, uint32_t n_points, uint32_t flags, bool any_output, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = "out_prim, out_dist and out_point are all NULL"; return SPIRA_E_INVALID; }
+    if (n_points > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) points"; return SPIRA_E_LIMIT; }
+    return 0;
+}
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

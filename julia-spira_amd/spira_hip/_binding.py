@@ -55,6 +55,8 @@ EXPORTS = [
     "spira_gather_rays_f32", "spira_gather_rays_f64", "spira_gather_rays_device_f32", "spira_gather_rays_device_f64",
     "spira_scene_gather_f32", "spira_scene_gather_f64", "spira_scene_gather_device_f32", "spira_scene_gather_device_f64",
     "spira_scene_gather_visible_f32", "spira_scene_gather_visible_f64", "spira_scene_gather_visible_device_f32", "spira_scene_gather_visible_device_f64",
+    "spira_scene_closest_point_f32", "spira_scene_closest_point_f64", "spira_scene_closest_point_device_f32", "spira_scene_closest_point_device_f64",
+    "spira_closest_point_triangle_f32", "spira_closest_point_triangle_f64",
 ]
 
 
@@ -459,6 +461,30 @@ class Scene:
         _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
                   C.c_void_p(stream_ptr or None)))
 
+    def closest_point(self, points4, inplace=False, want_prim=True, want_dist=True, want_point=True, want_trips=False):
+        """spira_scene_closest_point_*: for every point of points4 (n x [px py pz r_max], host array) the nearest point of the scene's surface within r_max.
+        Returns (prim int32 [n], dist [n], point [n, 3], trips uint32 [n]), None where not wanted: prim is the object index (spheres first), RAY_MISS
+        (dist = the point's r_max, point 0) or RAY_INVALID (dist 0, point 0).  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        p = np.ascontiguousarray(points4, dtype=npdt)
+        if p.ndim != 2 or p.shape[1] != 4:
+            raise ValueError("points4: n_points x [px py pz r_max]")
+        n = len(p)
+        prim = np.empty(n, dtype=np.int32) if want_prim else None
+        dist = np.empty(n, dtype=npdt) if want_dist else None
+        point = np.empty((n, 3), dtype=npdt) if want_point else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        fn = lib().spira_scene_closest_point_f32 if self.prec == "f32" else lib().spira_scene_closest_point_f64
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, trips)]))
+        return prim, dist, point, trips
+
+    def closest_point_device(self, d_points_ptr, n_points, d_prim_ptr, d_dist_ptr, d_point_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
+        """spira_scene_closest_point_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        fn = lib().spira_scene_closest_point_device_f32 if self.prec == "f32" else lib().spira_scene_closest_point_device_f64
+        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
+                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
 
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).
@@ -752,3 +778,15 @@ def tonemap(values, post):
     v = np.ascontiguousarray(values, dtype=np.float32).copy()
     _check(lib().spira_tonemap_f32(v.ctypes.data_as(C.c_void_p), C.c_uint64(v.size), C.c_uint32(post)))
     return v
+
+
+def closest_point_triangle(v0, e1, e2, p, prec):
+    """spira_closest_point_triangle_*: the library's triangle function on one triangle (v0, e1 = v1 - v0, e2 = v2 - v0) and one point, as host arithmetic
+    (no device needed).  Returns (q [3], d2) in the precision's dtype."""
+    npdt, _ = _dt(prec)
+    a = [np.ascontiguousarray(x, dtype=npdt).reshape(3) for x in (v0, e1, e2, p)]
+    q, d2 = np.empty(3, dtype=npdt), np.empty(1, dtype=npdt)
+    fn = lib().spira_closest_point_triangle_f32 if prec == "f32" else lib().spira_closest_point_triangle_f64
+    fn.restype = None
+    fn(*[x.ctypes.data_as(C.c_void_p) for x in a], q.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p))
+    return q, d2[0]

@@ -72,3 +72,22 @@ def ambient_occlusion(scene, points6, spp, t_max, t_min=1e-3, seed=0, sample0=0,
     near; rows of invalid points stay 0)."""
     counts = scene.gather_visible(points6, spp, t_min=t_min, t_max=t_max, seed=seed, sample0=sample0, key0=key0, inplace=inplace)
     return counts.astype(np.float64) / float(spp)
+
+
+def snap_to_surface(scene, points6, triangles10, r_max=float("inf"), inplace=False):
+    """Snaps points6 (n x [px py pz nx ny nz]) to the scene's surface with Scene.closest_point: the position becomes the nearest surface point within r_max,
+    and where that point lies on a triangle the normal becomes that triangle's, triangle_points' normalize(cross(e1, e2)) (triangles10: the mesh the
+    handle holds, in the caller's order).  A point whose nearest object is a sphere keeps its normal; a point with nothing within r_max, or an invalid
+    one, is left as it is.  Returns (points6 snapped, in the scene's precision; prim int32 [n])."""
+    npdt = B._dt(scene.prec)[0]
+    out = np.array(points6, dtype=npdt, copy=True).reshape(-1, 6)
+    p4 = np.concatenate([out[:, :3], np.full((len(out), 1), r_max, dtype=npdt)], axis=1)
+    prim, _, q, _ = scene.closest_point(p4, inplace=inplace, want_dist=False)
+    hit = prim >= 0
+    out[hit, :3] = q[hit]
+    ns = scene.counts[0]
+    on_tri = hit & (prim >= ns)
+    if on_tri.any():
+        nrm = triangle_points(triangles10, scene.prec)[:, 3:6]
+        out[on_tri, 3:6] = nrm[prim[on_tri] - ns]
+    return out, prim

@@ -51,3 +51,99 @@ def cast_rays(scene, rays, want_normal=False, occlusion=False, inplace=False, st
         nrm = torch.empty((n, 3), dtype=want, device=rays.device) if want_normal else None
         scene.cast_device(rays.data_ptr(), n, prim.data_ptr(), t.data_ptr(), nrm.data_ptr() if want_normal else 0, st.cuda_stream, inplace=inplace)
     return prim, t, nrm
+
+
+# ------------------------------------------------------------------ closest-point queries (spira_scene_closest_point_*; csrc/spira_nearest.h)
+def prepare_points(points4, dtype, frame=None):
+    """The validity rule of spira_nearest.h (nearest_point_prepare), bit for bit: returns (points, valid) — `points` a copy of points4 ([px py pz r_max])
+    in `dtype`, `valid` the library's verdict per point.  frame: None for a scene without a tree, else (centre[3], scale): the origin rule is applied."""
+    T = np.dtype(dtype).type
+    p = np.array(points4, dtype=T, copy=True).reshape(-1, 4)
+    with np.errstate(all="ignore"):
+        valid = ~np.isnan(p).any(axis=1)
+        valid &= np.isfinite(p[:, :3]).all(axis=1)
+        valid &= ~(p[:, 3] < T(0))
+        if frame is not None:
+            c, scale = np.asarray(frame[0], dtype=T), T(frame[1])
+            x = (p[:, :3] - c[None, :]) * scale
+            valid &= ((x >= T(-ORIGIN_BOUND)) & (x <= T(ORIGIN_BOUND))).all(axis=1)
+    return p, valid
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def closest_point_triangle(v0, e1, e2, p):
+    """The numpy twin of spira::closest_point_triangle: v0, e1 = v1 - v0, e2 = v2 - v0 and p are arrays [..., 3] of ONE dtype that broadcast against each
+    other (points x objects: p[:, None, :] against v0[None, :, :]).  Every region is evaluated and the first matching test of the library's order picks;
+    the same operations in the same order on the same values, nothing fused.  Returns (q [..., 3], d2 [...])."""
+    v0, e1, e2, p = (np.asarray(x) for x in (v0, e1, e2, p))
+    T = p.dtype.type
+    with np.errstate(all="ignore"):
+        ap = p - v0
+        d1, d2 = _dot3(e1, ap), _dot3(e2, ap)
+        bp = ap - e1
+        d3, d4 = _dot3(e1, bp), _dot3(e2, bp)
+        cp = ap - e2
+        d5, d6 = _dot3(e1, cp), _dot3(e2, cp)
+        vc = d1 * d4 - d3 * d2
+        vb = d5 * d2 - d1 * d6
+        va = d3 * d6 - d5 * d4
+        g, h = d4 - d3, d5 - d6
+        r1 = (d1 <= T(0)) & (d2 <= T(0))
+        r2 = (d3 >= T(0)) & (d4 <= d3)
+        r3 = (vc <= T(0)) & (d1 >= T(0)) & (d3 <= T(0))
+        r4 = (d6 >= T(0)) & (d5 <= d6)
+        r5 = (vb <= T(0)) & (d2 >= T(0)) & (d6 <= T(0))
+        r6 = (va <= T(0)) & (g >= T(0)) & (h >= T(0))
+        v3 = (d1 / (d1 - d3))[..., None]
+        w5 = (d2 / (d2 - d6))[..., None]
+        w6 = (g / (g + h))[..., None]
+        s = T(1) / ((va + vb) + vc)
+        v7, w7 = (vb * s)[..., None], (vc * s)[..., None]
+        v0b = np.broadcast_to(v0, np.broadcast(v0, p).shape)
+        q = (v0 + e1 * v7) + e2 * w7
+        q = np.where(r6[..., None], (v0 + e1) + (e2 - e1) * w6, q)
+        q = np.where(r5[..., None], v0 + e2 * w5, q)
+        q = np.where(r4[..., None], v0 + e2, q)
+        q = np.where(r3[..., None], v0 + e1 * v3, q)
+        q = np.where(r2[..., None], v0 + e1, q)
+        q = np.where(r1[..., None], v0b, q)
+        r = p - q
+        return q, _dot3(r, r)
+
+
+def closest_point_sphere(c, radius, p):
+    """The numpy twin of spira::closest_point_sphere: c [..., 3], radius [...], p [..., 3] of ONE dtype, broadcasting.  Returns (q [..., 3], d2 [...])."""
+    c, radius, p = np.asarray(c), np.asarray(radius), np.asarray(p)
+    T = p.dtype.type
+    with np.errstate(all="ignore"):
+        w = p - c
+        l = np.sqrt(_dot3(w, w))
+        q_far = c + w * (radius / l)[..., None]
+        rb = np.broadcast_to(radius, l.shape)
+        q_near = c + np.stack([rb, np.zeros_like(rb), np.zeros_like(rb)], axis=-1)
+        q = np.where((l >= np.finfo(T).tiny)[..., None], q_far, q_near)
+        r = p - q
+        return q, _dot3(r, r)
+
+
+def closest_points(scene, points, inplace=False, want_point=True, want_trips=False, stream=None):
+    """spira_scene_closest_point_device_* for a torch tensor of points [n, 4] ([px py pz r_max]) on the scene's device, in the scene's precision.  Enqueues
+    on `stream` (a torch.cuda.Stream; None: the current one) and returns device tensors without synchronising: (prim int32 [n], dist [n], point [n, 3]
+    or None, trips int32 [n] or None).  `points` must stay alive until the work has run."""
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise ValueError("closest_points: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
+    n = points.shape[0]
+    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    with torch.cuda.stream(st):
+        prim = torch.empty(n, dtype=torch.int32, device=points.device)
+        dist = torch.empty(n, dtype=want, device=points.device)
+        q = torch.empty((n, 3), dtype=want, device=points.device) if want_point else None
+        trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
+        scene.closest_point_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), q.data_ptr() if want_point else 0, st.cuda_stream,
+                                   inplace=inplace, d_trips_ptr=trips.data_ptr() if want_trips else 0)
+    return prim, dist, q, trips
