@@ -1,7 +1,7 @@
 // spira_gather.h — hemisphere gather at surface points on a scene handle: per-point radiance sums (spira_scene_gather_*), per-point counts of unoccluded
 // directions (spira_scene_gather_visible_*) and the generator that writes one sample's rays as a list (spira_gather_rays_*).  Included by spira_hip.hip
-// behind spira_radiance.h: the path loop is k_radiance's (trace_segment<T, BVH, EXT> of spira_device.h, unedited), the occlusion walk k_cast's
-// (cast_scan_local, bvh8_enter / bvh8_begin / bvh8_step, cast_ray_prepare of spira_query.h); no existing kernel is touched.  Launch arithmetic:
+// behind spira_radiance.h: the path loop is k_radiance's (trace_segment<T, BVH, EXT> of spira_device.h, unedited), the occlusion walk
+// k_cast_session's (SPIRA_REFILLED_SESSION, cast_scan_local, bvh8_enter / bvh8_begin / bvh8_step, cast_ray_prepare of spira_query.h).  Launch arithmetic:
 // spira_plan.h (make_gather_plan).  The first part of this file needs no HIP header: a CPU program (tests/native/gather_plan.cpp) calls the very
 // function the kernels and the host entry generate a ray with.
 //
@@ -24,12 +24,13 @@
 //   k_gather<T, BVH, EXT>            k_radiance's loop: persistent lanes with path regeneration; a work item is (point, sample), sample-minor; the lane
 //                                    GENERATES its ray at regeneration.  A pass of one sample per point: the owning lane adds to sum[k] and writes the
 //                                    valid byte.  More samples per pass: L goes to the Pack3<T> workspace, entry = item.
-//   k_gather_sum<T>                  one lane per point: adds the point's workspace entries in sample order and writes the valid byte.
-//   k_gather_visible_session<T>      scenes with a tree: k_cast_session<T, true>'s organisation over the pass's items — each wave owns a contiguous
-//                                    item range, free lanes refill (ballot / popcount) and generate their ray, all walking lanes take bvh8_step trips
-//                                    together and leave at the first accepted hit.
+//   k_gather_sum<T>                  one lane per point: adds the point's workspace entries in sample order and writes the valid byte (path_sum_loop).
+//   k_gather_visible_session<T>      scenes with a tree: k_cast_session<T, true>'s organisation over the pass's items, on the same loop
+//                                    (SPIRA_REFILLED_SESSION of spira_query.h) — each wave owns a contiguous item range, free lanes refill
+//                                    (ballot / popcount) and generate their ray, all walking lanes take bvh8_step trips together and leave at the
+//                                    first accepted hit.
 //   k_gather_visible<T, BVH, TRI>    one lane per item: scenes without a tree, and the SPIRA_CAST_INPLACE comparison point on scenes with one.
-//   k_gather_rays<T>                 one lane per point, the six values through LDS so that the workgroup's stores are contiguous (k_camera_rays).
+//   k_gather_rays<T>                 one lane per point, the six values through LDS so that the workgroup's stores are contiguous (rays_through_tile, as k_camera_rays).
 // Counts: a finished item whose ray is unoccluded adds 1 to its point's uint32 with a vector atomic; integer additions commute, so both organisations,
 // any grid and any pass split leave the same bytes.  The valid byte of a point is written by the item of its first sample in the call's first pass.
 #pragma once
@@ -168,20 +169,13 @@ __global__ __launch_bounds__(kBlock) void k_gather(const GatherArgs<T> a) {
 // The pass's workspace entries of every valid point, added in sample order.
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_gather_sum(const GatherArgs<T> a) {
-    for (uint32_t point = blockIdx.x * kBlock + threadIdx.x; point < a.n_points; point += gridDim.x * kBlock) {
+    path_sum_loop<T>(a, a.n_points, [&](uint32_t point) -> bool {
         const T *pp = a.points + 6 * (size_t)point;
         T pt[6], nh[3];
 #pragma unroll
         for (int k = 0; k < 6; ++k) pt[k] = pp[k];
-        const bool ok = radiance_ray_prepare<T>(pt, nh);
-        if (a.valid && a.write_valid) a.valid[point] = ok ? (uint8_t)1 : (uint8_t)0;
-        if (!ok) continue;
-        T *sp = a.sum + 3 * (size_t)point;
-        T x = sp[0], y = sp[1], z = sp[2];
-        const Pack3<T> *l = a.ws + (size_t)point * a.spp_pass;
-        for (uint32_t s = 0; s < a.spp_pass; ++s) { x = x + l[s].x; y = y + l[s].y; z = z + l[s].z; }
-        sp[0] = x; sp[1] = y; sp[2] = z;
-    }
+        return radiance_ray_prepare<T>(pt, nh);
+    });
 }
 
 template <class T> struct GatherVisibleArgs {
@@ -232,60 +226,45 @@ __global__ __launch_bounds__(kBlock) void k_gather_visible(const GatherVisibleAr
     }
 }
 
-// Scenes with a tree: a refilled traversal session per wave over its range of the pass's items (k_cast_session<T, true> with generated rays).
+// Scenes with a tree: a refilled traversal session per wave over its range of the pass's items (SPIRA_REFILLED_SESSION of spira_query.h; k_cast_session<T, true>'s
+// two callables with generated rays and a count in place of the hit byte).
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_gather_visible_session(const GatherVisibleArgs<T> a) {
     constexpr int KL = kCastLdsStack;
     extern __shared__ __attribute__((aligned(32))) unsigned char lds_raw[];
     const SceneLds<T> sc = stage_scene<T>(a.scene, lds_raw);     // the only workgroup barrier of the kernel
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t wid = blockIdx.x * (kBlock / 64) + wave;
-    const uint32_t begin = wid * a.base + (wid < a.rem ? wid : a.rem), end = begin + a.base + (wid < a.rem ? 1u : 0u);
-    uint32_t *lstack = reinterpret_cast<uint32_t *>(lds_raw + scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles)) + (size_t)wave * (KL > 0 ? KL : 1) * 64;
+    uint32_t begin, end;
+    session_range(a.base, a.rem, begin, end);
+    uint32_t *lstack = session_lstack<T>(lds_raw, a.scene);
     uint32_t stack[kBvhStackD - KL];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    const uint32_t lane = threadIdx.x & 63;
     const int base = (int)(sc.n_spheres + sc.n_triangles);
-    uint32_t next = begin;                                       // wave-uniform: the next item of the range nobody has taken
-    bool walking = false;
     uint32_t point = 0, slot = 0;
     Vec<T> o = mk<T>(0, 0, 0), d = mk<T>(0, 0, 1);
     T closest = 0;
     int prim = -1;
     Bvh8Ray ry{};
     Bvh8Walk<T> wk{};
-    while (true) {
-        // ---- refill: the free lanes take the next items of the range, in index order
-        const unsigned long long mf = __ballot(!walking);
-        const uint32_t n_free = (uint32_t)__popcll(mf), rank = (uint32_t)__popcll(mf & lt_mask);
-        const uint32_t take = min(n_free, end - next);
-        if (!walking && rank < take) {
+    const auto start = [&](uint32_t item) -> bool {
             prim = -1; slot = 0; closest = 0;
-            if (gather_visible_load<T>(a, sc, true, next + rank, point, o, d)) {
+            if (gather_visible_load<T>(a, sc, true, item, point, o, d)) {
                 cast_scan_local<T, false>(sc, o, d, a.t_min, a.t_max, closest, prim);
                 T t0;
-                if (prim < 0 && bvh8_enter<T>(sc, o, d, closest, ry, t0)) { bvh8_begin<T>(wk, ry, t0, a.t_min, sc.bvh_root[2].w); walking = true; }
+                if (prim < 0 && bvh8_enter<T>(sc, o, d, closest, ry, t0)) { bvh8_begin<T>(wk, ry, t0, a.t_min, sc.bvh_root[2].w); return true; }
                 else if (prim < 0) atomicAdd(a.visible + point, 1u);      // nothing in LDS and the ray misses the mesh's box
             }
-        }
-        next += take;
-        if (!__any(walking)) { if (next < end) continue; break; }
-        // ---- walk; leave the loop when enough lanes are free for a refill to pay (or, with the range exhausted, when all are done)
-        const bool more = next < end;
-        while (true) {
-            if (walking) {
-                bool on = bvh8_step<T, KL>(sc, wk, ry, o, d, a.t_min, base, closest, prim, slot, lstack, stack, lane);
-                if (prim >= 0) on = false;                       // the first accepted hit ends the walk (pending Float64 candidates are dropped)
-                if (!on) {
-                    // the screened Float64 walk (experiment build): its pending candidates are resolved before the lane counts as finished
-                    if (prim < 0) while (wk.nc) bvh8_resolve_one<T>(sc, wk, ry, o, d, a.t_min, base, closest, prim, slot);
-                    walking = false;
-                    if (prim < 0) atomicAdd(a.visible + point, 1u);
-                }
-            }
-            const uint32_t n_walk = (uint32_t)__popcll(__ballot(walking));
-            if (n_walk == 0 || (more && 64u - n_walk >= a.refill_free)) break;
-        }
-    }
+            return false;
+    };
+    const auto step = [&]() -> bool {
+            bool on = bvh8_step<T, KL>(sc, wk, ry, o, d, a.t_min, base, closest, prim, slot, lstack, stack, lane);
+            if (prim >= 0) on = false;                           // the first accepted hit ends the walk (pending Float64 candidates are dropped)
+            if (on) return true;
+            // the screened Float64 walk (experiment build): its pending candidates are resolved before the lane counts as finished
+            if (prim < 0) while (wk.nc) bvh8_resolve_one<T>(sc, wk, ry, o, d, a.t_min, base, closest, prim, slot);
+            if (prim < 0) atomicAdd(a.visible + point, 1u);
+            return false;
+    };
+    SPIRA_REFILLED_SESSION(begin, end, a.refill_free, start, step);
 }
 
 template <class T> struct GatherRaysArgs {
@@ -297,20 +276,13 @@ template <class T> struct GatherRaysArgs {
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_gather_rays(const GatherRaysArgs<T> a) {
     __shared__ T tile[kBlock * 6];
-    const uint32_t first = blockIdx.x * kBlock, k = first + threadIdx.x;      // (the grid covers n: one workgroup per kBlock points)
-    if (k < a.n) {
+    rays_through_tile<T>(tile, a.rays, a.n, [&](uint32_t k, T out6[6]) {
         const T *pp = a.points + 6 * (size_t)k;
-        T pt[6], out6[6];
+        T pt[6];
 #pragma unroll
         for (int c = 0; c < 6; ++c) pt[c] = pp[c];
         gather_ray_generate<T>(pt, a.sA, a.sB, a.key0 + k, a.sample, out6);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) tile[6 * threadIdx.x + c] = out6[c];
-    }
-    __syncthreads();
-    const uint32_t n_here = min((uint32_t)kBlock, a.n - first) * 6;             // first < n for every workgroup of the grid
-    T *dst = a.rays + 6 * (size_t)first;
-    for (uint32_t v = threadIdx.x; v < n_here; v += kBlock) dst[v] = tile[v];
+    });
 }
 
 }  // namespace spira

@@ -30,6 +30,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/spira_hip.h"
@@ -92,6 +93,26 @@ int gather_rays_impl_f32(const float *points6, uint32_t n_points, uint32_t sampl
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
 }
+
+// SPIRA_ENTRY(NAME, IMPL) defines NAME<T>(args...): IMPL<T> of whichever translation unit holds the kernels of T.  In the SPIRA_TU_MAIN unit a Float32 call
+// goes to spira_tu::IMPL_f32 (declared above, defined in the SPIRA_TU_F32 unit) and IMPL<float> is never instantiated there; every other build calls IMPL<T>.
+// The arguments are taken as the caller wrote them and held against the signature of the function they go to HERE, so a call that does not fit (a literal 0
+// for a pointer, a missing argument: an entry has no defaults of its own) fails at the entry, under the entry's name.
+#ifdef SPIRA_TU_MAIN
+constexpr bool kF32InItsOwnUnit = true;
+#else
+constexpr bool kF32InItsOwnUnit = false;
+#endif
+#define SPIRA_ENTRY(NAME, IMPL)                                                                                                                          \
+    template <class T, class... Args> int NAME(Args... args) {                                                                                           \
+        if constexpr (kF32InItsOwnUnit && sizeof(T) == 4) {                                                                                              \
+            static_assert(std::is_invocable_r_v<int, decltype(&spira_tu::IMPL##_f32), Args...>, #NAME ": the arguments do not fit " #IMPL "_f32");      \
+            return spira_tu::IMPL##_f32(args...);                                                                                                        \
+        } else {                                                                                                                                         \
+            static_assert(std::is_invocable_r_v<int, decltype(&IMPL<T>), Args...>, #NAME ": the arguments do not fit " #IMPL);                           \
+            return IMPL<T>(args...);                                                                                                                     \
+        }                                                                                                                                                \
+    }
 
 namespace spira_host {
 
@@ -167,10 +188,9 @@ struct Ctx {
     DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
     uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
     DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
-    DevBuf cast_io;                               // spira_scene_cast_* / spira_scene_occluded_*: the host form's staged rays and outputs
-    DevBuf nearest_io;                            // spira_scene_closest_point_*: the host form's staged points and outputs
-    DevBuf radiance_io;                           // spira_scene_radiance_*: the host form's staged rays, sums and valid bytes (its workspace is L)
-    DevBuf gather_io;                             // spira_scene_gather_* / spira_scene_gather_visible_*: the host form's staged points, sums / counts and valid bytes
+    DevBuf list_io;                               // the list calls (cast, closest point, radiance, the gathers): a host form's staged list and outputs.  ONE buffer for all
+                                                  // of them: a host-form call synchronises before it returns, so a later call of another kind may reuse or regrow it
+                                                  // (ensure only grows); the device forms never touch it
     DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
     uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
     DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
@@ -701,9 +721,9 @@ int acquire_scene(Ctx &c, hipStream_t st, const spira_scene *h, const T *spheres
 
 // SPIRA_EXT_SPECTRAL: the SPD table of include/spira_spd.h in the render precision, resident per context.
 template <class T>
-int attach_spd(Ctx &c, hipStream_t st, const spira_params *p, spira::SceneGlobal<T> &g) {
+int attach_spd(Ctx &c, hipStream_t st, uint32_t flags, spira::SceneGlobal<T> &g) {
     g.spd = nullptr;
-    if (!(p->flags & SPIRA_EXT_SPECTRAL)) return 0;
+    if (!(flags & SPIRA_EXT_SPECTRAL)) return 0;
     DevBuf &b = sizeof(T) == 4 ? c.spd32 : c.spd64;
     if (!b.p) {
         static_assert(SPIRA_SPD_N == spira::kSpdN && SPIRA_SPD_ROWS == spira::kSpdRows, "SPD table shape");
@@ -717,6 +737,8 @@ int attach_spd(Ctx &c, hipStream_t st, const spira_params *p, spira::SceneGlobal
     g.spd = (const T *)b.p;
     return 0;
 }
+template <class T>
+int attach_spd(Ctx &c, hipStream_t st, const spira_params *p, spira::SceneGlobal<T> &g) { return attach_spd<T>(c, st, p->flags, g); }
 
 template <class T>
 int check_handle(const spira_scene *h) {
@@ -1211,18 +1233,7 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     return rc;
 }
 
-// render_impl<T> of whichever translation unit holds the kernels of T
-template <class T>
-int render_entry_plain(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                       T *out_hdr, T *out_img, bool out_on_device, void *user_stream, bool progressive = false, uint32_t sample0 = 0, uint32_t *rng_states = nullptr,
-                       const SlabCtl *slab = nullptr) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::render_impl_f32(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, slab);
-    else
-#endif
-        return render_impl<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, slab);
-}
+SPIRA_ENTRY(render_entry_plain, render_impl)
 
 #ifdef SPIRA_TU_MAIN
 // A large frame for a host-pointer caller, rendered as row slabs: slab k's planes go device -> pinned staging on a second stream while slab k + 1
@@ -1306,7 +1317,7 @@ int render_entry(const spira_scene *h, const T *spheres5, const T *materials8, c
         if (done || rc) return rc;
     }
 #endif
-    return render_entry_plain<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states);
+    return render_entry_plain<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, nullptr);
 }
 
 // ---- adaptive sampling (spira_render_adaptive_*; spira_adaptive.h).  Round 0 is a plain render of min_spp samples on the slot-major plan (PlanIn::adaptive)
@@ -1427,17 +1438,7 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
     return s.close();
 }
 
-// render_adaptive_impl<T> of whichever translation unit holds the kernels of T
-template <class T>
-int render_adaptive_entry(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                          const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::render_adaptive_impl_f32(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
-    else
-#endif
-        return render_adaptive_impl<T>(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
-}
+SPIRA_ENTRY(render_adaptive_entry, render_adaptive_impl)
 
 // The rule as host arithmetic: 1 converged, 0 not, or a negative code
 template <class T>
@@ -1491,227 +1492,197 @@ int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, 
     return s.close();
 }
 
+SPIRA_ENTRY(features_entry, features_impl)
+
+// ======================================================================= the list calls on a scene handle: what cast, closest point, radiance and the gathers share
+// Each answers a caller's list (rays or points) entry by entry.  Written once for all of them: the opening, the staging of a host caller's arrays, the
+// pass loop of the calls that split their samples, and the two choices of a kernel by the scene's shape.  The counters of the last render are left as they are.
 template <class T>
-int features_entry(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                   T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::features_impl_f32(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
-    else
-#endif
-        return features_impl<T>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
+int open_list_call(Session &s, const spira_scene *h, bool on_device, void *user_stream, spira::SceneGlobal<T> &g) {
+    if (int rc = check_handle<T>(h)) return rc;
+    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+    scene_pointers<T>(h->store, g);
+    g.spd = nullptr;
+    return 0;
+}
+
+// The arrays of a list call.  Device form: the caller's pointers pass through, no buffer of the context is touched and nothing is allocated.  Host form: the
+// blocks lie back to back in the context's list_io in the order given — a NULL block keeps its place and stays NULL, so every block starts where the
+// entry's layout comment says — stage_in copies the kStageIn ones in, stage_out (after the launches) copies the kStageOut ones back, in the order given.
+enum : unsigned { kStageIn = 1, kStageOut = 2 };
+struct StageBlock { void *host; size_t bytes; unsigned dir; void *dev; };
+template <int N>
+int stage_in(Session &s, StageBlock (&b)[N]) {
+    if (!s.host_out) { for (StageBlock &k : b) k.dev = k.host; return 0; }
+    size_t total = 0;
+    for (const StageBlock &k : b) total += k.bytes;
+    if (int rc = s.cp->list_io.ensure(total)) return rc;
+    char *at = (char *)s.cp->list_io.p;
+    for (StageBlock &k : b) {
+        k.dev = k.host ? at : nullptr;
+        if (k.host && (k.dir & kStageIn)) HIP_TRY(hipMemcpyAsync(at, k.host, k.bytes, hipMemcpyHostToDevice, s.st));
+        at += k.bytes;
+    }
+    return 0;
+}
+template <int N>
+int stage_out(Session &s, const StageBlock (&b)[N]) {
+    if (!s.host_out) return 0;
+    for (const StageBlock &k : b)
+        if (k.host && (k.dir & kStageOut)) HIP_TRY(hipMemcpyAsync(k.host, k.dev, k.bytes, hipMemcpyDeviceToHost, s.st));
+    return 0;
+}
+
+// The passes of a call that splits its samples (RadiancePlan; spira_plan.h): the pass's fields of `a` (RadianceArgs, GatherArgs or GatherVisibleArgs — the same
+// names in all three), the checks every pass gets, then launch().  ws_room: the items the call's workspace holds (~0: the call has none).
+template <class A, class Launch>
+int run_passes(const spira::RadiancePlan &pl, uint32_t sample0, uint64_t ws_room, A &a, Launch launch) {
+    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
+        const uint64_t items = pl.items(pass);
+        if (items > spira::kRadianceMaxItems) return fail(SPIRA_E_LIMIT, "internal: a pass holds more items than an index reaches");
+        a.sample_first = sample0 + pl.first(pass);
+        a.spp_pass = pl.count(pass);
+        a.n_items = (uint32_t)items;
+        a.fd_spp = spira::fastdiv_make(a.spp_pass);
+        a.write_valid = pass == 0 ? 1u : 0u;
+        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
+        if (items > ws_room) return fail(SPIRA_E_LIMIT, "internal: the workspace is smaller than the pass");
+        if (int rc = launch()) return rc;
+    }
+    return 0;
+}
+
+// The kernels of a list query by the scene's shape.  A scene with a tree: the refilled sessions on cp.grid workgroups (lds_stack: with the waves' LDS stack
+// levels behind the scene, where kCastLdsStack asks for some), or under SPIRA_CAST_INPLACE the one-lane-per-item kernel walking the tree; without a tree
+// that kernel with the LDS triangle scan, or over spheres alone.  The one-lane-per-item kernels stride a flat grid.
+template <class A> struct ListKernels { void (*session)(A), (*tree)(A), (*tri)(A), (*spheres)(A); bool lds_stack; };
+template <class A>
+int launch_list(const ListKernels<A> &k, const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const A &a) {
+    const dim3 block(spira::kBlock), flat(cp.grid_flat);
+    if (a.scene.n_bvh_tris && !inplace)
+        return launch_lds(k.session, dim3(cp.grid), block, lds + (k.lds_stack ? (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb : 0), st, a);
+    return launch_lds(a.scene.n_bvh_tris ? k.tree : a.scene.n_triangles ? k.tri : k.spheres, flat, block, lds, st, a);
+}
+// The kernels of a path loop, k[BVH][EXT]: a scene with a tree or without, the material extensions or not.
+template <class A>
+int launch_paths(void (*const (&k)[2][2])(A), dim3 grid, size_t lds, hipStream_t st, const A &a) {
+    const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
+    return launch_lds(k[a.scene.n_bvh_tris ? 1 : 0][ext ? 1 : 0], grid, dim3(spira::kBlock), lds, st, a);
 }
 
 // ======================================================================= spira_scene_cast_* / spira_scene_occluded_*: the caller's rays against a handle
 // Kernels and the ray preparation: spira_query.h; launch arithmetic: spira_plan.h (make_cast_plan).  One launch.  The device form touches no workspace of
-// the context (it allocates nothing); the host form stages rays and outputs in cast_io.  The counters of the last render are left as they are.
+// the context (it allocates nothing); the host form stages rays and outputs.
 spira::CastKnobs read_cast_knobs() {
     spira::CastKnobs k;
     k.refill = env_u32("SPIRA_CAST_REFILL", SPIRA_CAST_REFILL);
     k.waves_per_cu = env_u32("SPIRA_CAST_WAVES_PER_CU", SPIRA_CAST_WAVES_PER_CU);
     return k;
 }
-template <class T, bool ANY>
-int launch_cast(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::CastArgs<T> &a) {
-    const dim3 block(spira::kBlock), flat(cp.grid_flat);
-    if (a.scene.n_bvh_tris && !inplace)
-        return launch_lds(spira::k_cast_session<T, ANY>, dim3(cp.grid), block, lds + (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb, st, a);
-    if (a.scene.n_bvh_tris) return launch_lds(spira::k_cast<T, true, false, ANY>, flat, block, lds, st, a);
-    if (a.scene.n_triangles) return launch_lds(spira::k_cast<T, false, true, ANY>, flat, block, lds, st, a);
-    return launch_lds(spira::k_cast<T, false, false, ANY>, flat, block, lds, st, a);
-}
 template <class T>
 int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
               bool any, bool on_device, void *user_stream) {
+    using A = spira::CastArgs<T>;
+    const ListKernels<A> closest = {spira::k_cast_session<T, false>, spira::k_cast<T, true, false, false>, spira::k_cast<T, false, true, false>, spira::k_cast<T, false, false, false>, true};
+    const ListKernels<A> occluded = {spira::k_cast_session<T, true>, spira::k_cast<T, true, false, true>, spira::k_cast<T, false, true, true>, spira::k_cast<T, false, false, true>, true};
     const char *msg = nullptr;
     if (int rc = spira::cast_check(rays8 != nullptr, n_rays, flags, any ? out_hit != nullptr : (out_prim || out_t || out_normal), &msg)) return fail(rc, msg);
-    if (int rc = check_handle<T>(h)) return rc;
     Session s;
-    if (int rc = Session::open(s, on_device, user_stream)) return rc;
-    Ctx &c = *s.cp;
-    const hipStream_t st = s.st;
-
-    spira::CastArgs<T> a{};
-    scene_pointers<T>(h->store, a.scene);
-    a.scene.spd = nullptr;
-    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)c.num_cus, spira::kBlock, read_cast_knobs());
-    a.rays = rays8; a.n_rays = n_rays; a.prim = out_prim; a.t = out_t; a.normal = out_normal; a.hit = out_hit;
-    a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
-    const size_t n = n_rays, ray_b = 8 * n * sizeof(T), t_b = n * sizeof(T), prim_b = n * sizeof(int);
-    if (!on_device) {
-        // [rays | t | normal | prim | hit]: every block starts at a multiple of sizeof(T) or more
-        if (int rc = c.cast_io.ensure(ray_b + 4 * t_b + prim_b + n)) return rc;
-        char *base = (char *)c.cast_io.p;
-        HIP_TRY(hipMemcpyAsync(base, rays8, ray_b, hipMemcpyHostToDevice, st));
-        a.rays = (const T *)base;
-        a.t = out_t ? (T *)(base + ray_b) : nullptr;
-        a.normal = out_normal ? (T *)(base + ray_b + t_b) : nullptr;
-        a.prim = out_prim ? (int *)(base + ray_b + 4 * t_b) : nullptr;
-        a.hit = out_hit ? (uint8_t *)(base + ray_b + 4 * t_b + prim_b) : nullptr;
-    }
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n_rays = n_rays; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_rays, t_b = n * sizeof(T);
+    // [rays | t | normal | prim | hit]: every block starts at a multiple of sizeof(T) or more
+    StageBlock io[] = {{(void *)rays8, 8 * t_b, kStageIn}, {out_t, t_b, kStageOut}, {out_normal, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut}, {out_hit, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.rays = (const T *)io[0].dev; a.t = (T *)io[1].dev; a.normal = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.hit = (uint8_t *)io[4].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    const bool inplace = (flags & SPIRA_CAST_INPLACE) != 0;
-    if (int rc = any ? launch_cast<T, true>(cp, inplace, lds, st, a) : launch_cast<T, false>(cp, inplace, lds, st, a)) return rc;
-    if (!on_device) {
-        if (out_t) HIP_TRY(hipMemcpyAsync(out_t, a.t, t_b, hipMemcpyDeviceToHost, st));
-        if (out_normal) HIP_TRY(hipMemcpyAsync(out_normal, a.normal, 3 * t_b, hipMemcpyDeviceToHost, st));
-        if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, a.prim, prim_b, hipMemcpyDeviceToHost, st));
-        if (out_hit) HIP_TRY(hipMemcpyAsync(out_hit, a.hit, n, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = launch_list(any ? occluded : closest, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
-
-template <class T>
-int cast_entry(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
-               bool any, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::cast_impl_f32(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
-    else
-#endif
-        return cast_impl<T>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
-}
+SPIRA_ENTRY(cast_entry, cast_impl)
 
 // ======================================================================= spira_scene_closest_point_*: the nearest surface point for the caller's points
 // Kernels, the point preparation and the two closest-point functions: spira_nearest.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One
-// launch.  The device form touches no workspace of the context (it allocates nothing); the host form stages points and outputs in nearest_io.  The
-// counters of the last render are left as they are.
-template <class T>
-int launch_nearest(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::NearestArgs<T> &a) {
-    const dim3 block(spira::kBlock), flat(cp.grid_flat);
-    if (a.scene.n_bvh_tris && !inplace) return launch_lds(spira::k_nearest_session<T>, dim3(cp.grid), block, lds, st, a);
-    if (a.scene.n_bvh_tris) return launch_lds(spira::k_nearest<T, true, false>, flat, block, lds, st, a);
-    if (a.scene.n_triangles) return launch_lds(spira::k_nearest<T, false, true>, flat, block, lds, st, a);
-    return launch_lds(spira::k_nearest<T, false, false>, flat, block, lds, st, a);
-}
+// launch.  The device form touches no workspace of the context (it allocates nothing); the host form stages points and outputs.
 template <class T>
 int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
                  bool on_device, void *user_stream) {
+    using A = spira::NearestArgs<T>;
+    const ListKernels<A> kernels = {spira::k_nearest_session<T>, spira::k_nearest<T, true, false>, spira::k_nearest<T, false, true>, spira::k_nearest<T, false, false>, false};
     const char *msg = nullptr;
     if (int rc = spira::nearest_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point, &msg)) return fail(rc, msg);
-    if (int rc = check_handle<T>(h)) return rc;
     Session s;
-    if (int rc = Session::open(s, on_device, user_stream)) return rc;
-    Ctx &c = *s.cp;
-    const hipStream_t st = s.st;
-
-    spira::NearestArgs<T> a{};
-    scene_pointers<T>(h->store, a.scene);
-    a.scene.spd = nullptr;
-    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)c.num_cus, spira::kBlock, read_cast_knobs());
-    a.points = points4; a.n_points = n_points; a.prim = out_prim; a.dist = out_dist; a.point = out_point; a.trips = out_trips;
-    a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
-    const size_t n = n_points, pt_b = 4 * n * sizeof(T), t_b = n * sizeof(T), prim_b = n * sizeof(int);
-    if (!on_device) {
-        // [points | dist | point | prim | trips]: every block starts at a multiple of sizeof(T) or more
-        if (int rc = c.nearest_io.ensure(pt_b + 4 * t_b + 2 * prim_b)) return rc;
-        char *base = (char *)c.nearest_io.p;
-        HIP_TRY(hipMemcpyAsync(base, points4, pt_b, hipMemcpyHostToDevice, st));
-        a.points = (const T *)base;
-        a.dist = out_dist ? (T *)(base + pt_b) : nullptr;
-        a.point = out_point ? (T *)(base + pt_b + t_b) : nullptr;
-        a.prim = out_prim ? (int *)(base + pt_b + 4 * t_b) : nullptr;
-        a.trips = out_trips ? (uint32_t *)(base + pt_b + 4 * t_b + prim_b) : nullptr;
-    }
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_points, t_b = n * sizeof(T);
+    // [points | dist | point | prim | trips]: every block starts at a multiple of sizeof(T) or more
+    StageBlock io[] = {{(void *)points4, 4 * t_b, kStageIn}, {out_dist, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut},
+                       {out_trips, n * sizeof(uint32_t), kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.trips = (uint32_t *)io[4].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_nearest<T>(cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, st, a)) return rc;
-    if (!on_device) {
-        if (out_dist) HIP_TRY(hipMemcpyAsync(out_dist, a.dist, t_b, hipMemcpyDeviceToHost, st));
-        if (out_point) HIP_TRY(hipMemcpyAsync(out_point, a.point, 3 * t_b, hipMemcpyDeviceToHost, st));
-        if (out_prim) HIP_TRY(hipMemcpyAsync(out_prim, a.prim, prim_b, hipMemcpyDeviceToHost, st));
-        if (out_trips) HIP_TRY(hipMemcpyAsync(out_trips, a.trips, prim_b, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
-
-template <class T>
-int nearest_entry(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
-                  bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::nearest_impl_f32(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
-    else
-#endif
-        return nearest_impl<T>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
-}
+SPIRA_ENTRY(nearest_entry, nearest_impl)
 
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
-// the host form stages rays, sums and valid bytes in radiance_io.  The counters of the last render are left as they are.
+// the host form stages rays, sums and valid bytes.
 spira::RadianceKnobs read_radiance_knobs() {
     spira::RadianceKnobs k;
     k.waves_per_cu = env_u32("SPIRA_RADIANCE_WAVES_PER_CU", SPIRA_RADIANCE_WAVES_PER_CU);
     k.max_items = env_u32("SPIRA_RADIANCE_MAX_ITEMS", SPIRA_RADIANCE_MAX_ITEMS);
     return k;
 }
-template <class T>
-int launch_radiance(dim3 grid, size_t lds, hipStream_t st, const spira::RadianceArgs<T> &a) {
-    const dim3 block(spira::kBlock);
-    const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
-    if (a.scene.n_bvh_tris) return ext ? launch_lds(spira::k_radiance<T, true, true>, grid, block, lds, st, a) : launch_lds(spira::k_radiance<T, true, false>, grid, block, lds, st, a);
-    return ext ? launch_lds(spira::k_radiance<T, false, true>, grid, block, lds, st, a) : launch_lds(spira::k_radiance<T, false, false>, grid, block, lds, st, a);
-}
-template <class T>
-int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
-    const char *msg = nullptr;
-    if (int rc = spira::radiance_check(rays6 != nullptr, rp != nullptr, sum_rgb != nullptr, n_rays, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
-                                       rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
-    if (int rc = check_handle<T>(h)) return rc;
-    Session s;
-    if (int rc = Session::open(s, on_device, user_stream)) return rc;
+// What radiance_impl and gather_impl do with their Args (RadianceArgs, GatherArgs) once the list's own two fields are set: the path constants, the
+// workspace, the staged list / sums / valid bytes, the passes.  list, n: the caller's rays or points (six values each) and where Args keeps the staged pointer.
+template <class T, class A>
+int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radiance *rp, A &a, const T *list, const T *A::*staged, uint32_t n, T *sum_rgb, uint8_t *out_valid,
+                   void (*const (&paths)[2][2])(A), void (*sum)(A)) {
     Ctx &c = *s.cp;
-    const hipStream_t st = s.st;
-
-    const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, rp->spp, (uint32_t)c.num_cus, spira::kBlock, read_radiance_knobs());
     if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
-    spira::RadianceArgs<T> a{};
-    scene_pointers<T>(h->store, a.scene);
-    spira_params fake{};
-    fake.flags = rp->flags;
-    if (int rc = attach_spd<T>(c, st, &fake, a.scene)) return rc;
+    if (int rc = attach_spd<T>(c, s.st, rp->flags, a.scene)) return rc;
     spira::seed_halves(rp->seed, a.rc.sA, a.rc.sB);
     a.rc.flags = rp->flags; a.rc.max_depth = rp->max_depth; a.rc.spp = rp->spp;
-    a.rays = rays6; a.n_rays = n_rays; a.sum = sum_rgb; a.valid = out_valid; a.key0 = rp->key0;
+    a.key0 = rp->key0;
     a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
-    const size_t n = n_rays, ray_b = 6 * n * sizeof(T), sum_b = 3 * n * sizeof(T);
-    if (!on_device) {
-        // [rays | sums | valid]: every block starts at a multiple of sizeof(T)
-        if (int rc = c.radiance_io.ensure(ray_b + sum_b + n)) return rc;
-        char *base = (char *)c.radiance_io.p;
-        HIP_TRY(hipMemcpyAsync(base, rays6, ray_b, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(base + ray_b, sum_rgb, sum_b, hipMemcpyHostToDevice, st));
-        a.rays = (const T *)base;
-        a.sum = (T *)(base + ray_b);
-        a.valid = out_valid ? (uint8_t *)(base + ray_b + sum_b) : nullptr;
-    }
+    const size_t sum_b = 3 * (size_t)n * sizeof(T);
+    // [rays or points | sums | valid]: every block starts at a multiple of sizeof(T)
+    StageBlock io[] = {{(void *)list, 2 * sum_b, kStageIn}, {sum_rgb, sum_b, kStageIn | kStageOut}, {out_valid, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.*staged = (const T *)io[0].dev; a.sum = (T *)io[1].dev; a.valid = (uint8_t *)io[2].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        a.sample_first = rp->sample0 + pl.first(pass);
-        a.spp_pass = pl.count(pass);
-        a.n_items = (uint32_t)pl.items(pass);
-        a.fd_spp = spira::fastdiv_make(a.spp_pass);
-        a.write_valid = pass == 0 ? 1u : 0u;
-        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-        if (a.ws && (uint64_t)a.n_items * sizeof(spira::Pack3<T>) > c.L.cap) return fail(SPIRA_E_LIMIT, "internal: the radiance workspace is smaller than the pass");
-        if (int rc = launch_radiance<T>(dim3(pl.grid), lds, st, a)) return rc;
-        if (a.ws) hipLaunchKernelGGL(spira::k_radiance_sum<T>, dim3(pl.grid_flat), dim3(spira::kBlock), 0, st, a);
-    }
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(sum_rgb, a.sum, sum_b, hipMemcpyDeviceToHost, st));
-        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = run_passes(pl, rp->sample0, a.ws ? c.L.cap / sizeof(spira::Pack3<T>) : ~0ull, a, [&]() -> int {
+            if (int rc2 = launch_paths(paths, dim3(pl.grid), lds, s.st, a)) return rc2;
+            if (a.ws) hipLaunchKernelGGL(sum, dim3(pl.grid_flat), dim3(spira::kBlock), 0, s.st, a);
+            return 0;
+        })) return rc;
+    if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
 template <class T>
-int radiance_entry(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::radiance_impl_f32(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
-    else
-#endif
-        return radiance_impl<T>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
+int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    using A = spira::RadianceArgs<T>;
+    void (*const paths[2][2])(A) = {{spira::k_radiance<T, false, false>, spira::k_radiance<T, false, true>}, {spira::k_radiance<T, true, false>, spira::k_radiance<T, true, true>}};
+    const char *msg = nullptr;
+    if (int rc = spira::radiance_check(rays6 != nullptr, rp != nullptr, sum_rgb != nullptr, n_rays, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
+                                       rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    a.n_rays = n_rays;
+    const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_radiance_knobs());
+    return path_list_call<T>(s, pl, rp, a, rays6, &A::rays, n_rays, sum_rgb, out_valid, paths, spira::k_radiance_sum<T>);
 }
+SPIRA_ENTRY(radiance_entry, radiance_impl)
 
 // The generator: the host form runs camera_ray_generate<T> here, the device form launches k_camera_rays<T> over the same function.
 template <class T>
@@ -1743,21 +1714,13 @@ int camera_rays_impl(const T *camera12, const spira_lens *lens, T *rays6, bool o
     hipLaunchKernelGGL(spira::k_camera_rays<T>, dim3((n + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
     return s.close();
 }
-template <class T>
-int camera_rays_entry(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::camera_rays_impl_f32(camera12, lens, rays6, on_device, user_stream);
-    else
-#endif
-        return camera_rays_impl<T>(camera12, lens, rays6, on_device, user_stream);
-}
+SPIRA_ENTRY(camera_rays_entry, camera_rays_impl)
 
 // ======================================================================= spira_scene_gather_* / spira_scene_gather_visible_* / spira_gather_rays_*: hemisphere gather at surface points
 // Kernels and the sampling rule: spira_gather.h; launch arithmetic: spira_plan.h (make_gather_plan).  The radiance gather is radiance_impl's call over
-// points: one k_gather launch per pass (+ k_gather_sum where a pass holds more than one sample per point), the workspace of such a pass the context's L.
-// The visibility gather runs the same passes with one launch each and no workspace: its device form allocates nothing.  The host forms stage points,
-// sums or counts and valid bytes in gather_io.  The counters of the last render are left as they are.
+// points (path_list_call): one k_gather launch per pass (+ k_gather_sum where a pass holds more than one sample per point), the workspace of such a pass the
+// context's L.  The visibility gather runs the same passes with one launch each and no workspace: its device form allocates nothing.  The host forms stage
+// points, sums or counts and valid bytes.
 spira::GatherKnobs read_gather_knobs() {
     spira::GatherKnobs k;
     k.waves_per_cu = env_u32("SPIRA_GATHER_WAVES_PER_CU", SPIRA_GATHER_WAVES_PER_CU);
@@ -1765,146 +1728,55 @@ spira::GatherKnobs read_gather_knobs() {
     return k;
 }
 template <class T>
-int launch_gather(dim3 grid, size_t lds, hipStream_t st, const spira::GatherArgs<T> &a) {
-    const dim3 block(spira::kBlock);
-    const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
-    if (a.scene.n_bvh_tris) return ext ? launch_lds(spira::k_gather<T, true, true>, grid, block, lds, st, a) : launch_lds(spira::k_gather<T, true, false>, grid, block, lds, st, a);
-    return ext ? launch_lds(spira::k_gather<T, false, true>, grid, block, lds, st, a) : launch_lds(spira::k_gather<T, false, false>, grid, block, lds, st, a);
-}
-template <class T>
 int gather_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+    using A = spira::GatherArgs<T>;
+    void (*const paths[2][2])(A) = {{spira::k_gather<T, false, false>, spira::k_gather<T, false, true>}, {spira::k_gather<T, true, false>, spira::k_gather<T, true, true>}};
     const char *msg = nullptr;
     if (int rc = spira::gather_check(points6 != nullptr, rp != nullptr, sum_rgb != nullptr, n_points, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
                                      rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
-    if (int rc = check_handle<T>(h)) return rc;
     Session s;
-    if (int rc = Session::open(s, on_device, user_stream)) return rc;
-    Ctx &c = *s.cp;
-    const hipStream_t st = s.st;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    a.n_points = n_points;
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_gather_knobs());
+    return path_list_call<T>(s, pl, rp, a, points6, &A::points, n_points, sum_rgb, out_valid, paths, spira::k_gather_sum<T>);
+}
+SPIRA_ENTRY(gather_entry, gather_impl)
 
-    const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)c.num_cus, spira::kBlock, read_gather_knobs());
-    if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
-    spira::GatherArgs<T> a{};
-    scene_pointers<T>(h->store, a.scene);
-    spira_params fake{};
-    fake.flags = rp->flags;
-    if (int rc = attach_spd<T>(c, st, &fake, a.scene)) return rc;
-    spira::seed_halves(rp->seed, a.rc.sA, a.rc.sB);
-    a.rc.flags = rp->flags; a.rc.max_depth = rp->max_depth; a.rc.spp = rp->spp;
-    a.points = points6; a.n_points = n_points; a.sum = sum_rgb; a.valid = out_valid; a.key0 = rp->key0;
-    a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
-    const size_t n = n_points, pt_b = 6 * n * sizeof(T), sum_b = 3 * n * sizeof(T);
-    if (!on_device) {
-        // [points | sums | valid]: every block starts at a multiple of sizeof(T)
-        if (int rc = c.gather_io.ensure(pt_b + sum_b + n)) return rc;
-        char *base = (char *)c.gather_io.p;
-        HIP_TRY(hipMemcpyAsync(base, points6, pt_b, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(base + pt_b, sum_rgb, sum_b, hipMemcpyHostToDevice, st));
-        a.points = (const T *)base;
-        a.sum = (T *)(base + pt_b);
-        a.valid = out_valid ? (uint8_t *)(base + pt_b + sum_b) : nullptr;
-    }
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t items = pl.items(pass);
-        if (items > spira::kRadianceMaxItems) return fail(SPIRA_E_LIMIT, "internal: a gather pass holds more items than an index reaches");
-        a.sample_first = rp->sample0 + pl.first(pass);
-        a.spp_pass = pl.count(pass);
-        a.n_items = (uint32_t)items;
-        a.fd_spp = spira::fastdiv_make(a.spp_pass);
-        a.write_valid = pass == 0 ? 1u : 0u;
-        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-        if (a.ws && items * sizeof(spira::Pack3<T>) > c.L.cap) return fail(SPIRA_E_LIMIT, "internal: the gather workspace is smaller than the pass");
-        if (int rc = launch_gather<T>(dim3(pl.grid), lds, st, a)) return rc;
-        if (a.ws) hipLaunchKernelGGL(spira::k_gather_sum<T>, dim3(pl.grid_flat), dim3(spira::kBlock), 0, st, a);
-    }
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(sum_rgb, a.sum, sum_b, hipMemcpyDeviceToHost, st));
-        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
-    }
-    return s.close();
-}
-template <class T>
-int gather_entry(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::gather_impl_f32(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
-    else
-#endif
-        return gather_impl<T>(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
-}
-
-template <class T>
-int launch_gather_visible(const spira::CastPlan &cp, bool inplace, size_t lds, hipStream_t st, const spira::GatherVisibleArgs<T> &a) {
-    const dim3 block(spira::kBlock), flat(cp.grid_flat);
-    if (a.scene.n_bvh_tris && !inplace)
-        return launch_lds(spira::k_gather_visible_session<T>, dim3(cp.grid), block, lds + (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb, st, a);
-    if (a.scene.n_bvh_tris) return launch_lds(spira::k_gather_visible<T, true, false>, flat, block, lds, st, a);
-    if (a.scene.n_triangles) return launch_lds(spira::k_gather_visible<T, false, true>, flat, block, lds, st, a);
-    return launch_lds(spira::k_gather_visible<T, false, false>, flat, block, lds, st, a);
-}
 template <class T>
 int gather_visible_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
                         bool on_device, void *user_stream) {
+    using A = spira::GatherVisibleArgs<T>;
+    const ListKernels<A> kernels = {spira::k_gather_visible_session<T>, spira::k_gather_visible<T, true, false>, spira::k_gather_visible<T, false, true>,
+                                           spira::k_gather_visible<T, false, false>, true};
     const char *msg = nullptr;
     if (int rc = spira::gather_visible_check(points6 != nullptr, gv != nullptr, visible != nullptr, n_points, gv ? gv->spp : 1, gv ? gv->sample0 : 0, gv ? gv->key0 : 0,
                                              gv ? gv->flags : 0, gv ? gv->t_min : 0.0, gv ? gv->t_max : 0.0, &msg)) return fail(rc, msg);
-    if (int rc = check_handle<T>(h)) return rc;
     Session s;
-    if (int rc = Session::open(s, on_device, user_stream)) return rc;
-    Ctx &c = *s.cp;
-    const hipStream_t st = s.st;
-
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const uint32_t num_cus = (uint32_t)s.cp->num_cus;
     const spira::GatherKnobs knobs = read_gather_knobs();
-    const spira::GatherPlan pl = spira::make_gather_plan(n_points, gv->spp, (uint32_t)c.num_cus, spira::kBlock, knobs);
-    spira::GatherVisibleArgs<T> a{};
-    scene_pointers<T>(h->store, a.scene);
-    a.scene.spd = nullptr;
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, gv->spp, num_cus, spira::kBlock, knobs);
     spira::seed_halves(gv->seed, a.sA, a.sB);
-    a.points = points6; a.n_points = n_points; a.visible = visible; a.valid = out_valid; a.key0 = gv->key0;
+    a.n_points = n_points; a.key0 = gv->key0;
     a.t_min = (T)gv->t_min; a.t_max = (T)gv->t_max;
-    const size_t n = n_points, pt_b = 6 * n * sizeof(T), cnt_b = n * sizeof(uint32_t);
-    if (!on_device) {
-        // [points | counts | valid]: every block starts at a multiple of 4
-        if (int rc = c.gather_io.ensure(pt_b + cnt_b + n)) return rc;
-        char *base = (char *)c.gather_io.p;
-        HIP_TRY(hipMemcpyAsync(base, points6, pt_b, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(base + pt_b, visible, cnt_b, hipMemcpyHostToDevice, st));
-        a.points = (const T *)base;
-        a.visible = (uint32_t *)(base + pt_b);
-        a.valid = out_valid ? (uint8_t *)(base + pt_b + cnt_b) : nullptr;
-    }
+    const size_t n = n_points;
+    // [points | counts | valid]: every block starts at a multiple of 4
+    StageBlock io[] = {{(void *)points6, 6 * n * sizeof(T), kStageIn}, {visible, n * sizeof(uint32_t), kStageIn | kStageOut}, {out_valid, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.points = (const T *)io[0].dev; a.visible = (uint32_t *)io[1].dev; a.valid = (uint8_t *)io[2].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
     const bool inplace = (gv->flags & SPIRA_CAST_INPLACE) != 0;
-    for (uint32_t pass = 0; pass < pl.n_pass; ++pass) {
-        const uint64_t items = pl.items(pass);
-        if (items > spira::kRadianceMaxItems) return fail(SPIRA_E_LIMIT, "internal: a gather pass holds more items than an index reaches");
-        a.sample_first = gv->sample0 + pl.first(pass);
-        a.spp_pass = pl.count(pass);
-        a.n_items = (uint32_t)items;
-        a.fd_spp = spira::fastdiv_make(a.spp_pass);
-        a.write_valid = pass == 0 ? 1u : 0u;
-        if (!fastdiv_selfcheck(a.spp_pass, a.n_items)) return fail(SPIRA_E_LIMIT, "internal: fast division self-check failed");
-        const spira::CastPlan cp = spira::make_gather_visible_plan(a.n_items, (uint32_t)c.num_cus, spira::kBlock, knobs, read_cast_knobs());
-        a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
-        if (int rc = launch_gather_visible<T>(cp, inplace, lds, st, a)) return rc;
-    }
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(visible, a.visible, cnt_b, hipMemcpyDeviceToHost, st));
-        if (out_valid) HIP_TRY(hipMemcpyAsync(out_valid, a.valid, n, hipMemcpyDeviceToHost, st));
-    }
+    if (int rc = run_passes(pl, gv->sample0, ~0ull, a, [&]() -> int {
+            const spira::CastPlan cp = spira::make_gather_visible_plan(a.n_items, num_cus, spira::kBlock, knobs, read_cast_knobs());
+            a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+            return launch_list(kernels, cp, inplace, lds, s.st, a);
+        })) return rc;
+    if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
-template <class T>
-int gather_visible_entry(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
-                         bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::gather_visible_impl_f32(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
-    else
-#endif
-        return gather_visible_impl<T>(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
-}
+SPIRA_ENTRY(gather_visible_entry, gather_visible_impl)
 
 // The generator: the host form runs gather_ray_generate<T> here, the device form launches k_gather_rays<T> over the same function.
 template <class T>
@@ -1924,15 +1796,7 @@ int gather_rays_impl(const T *points6, uint32_t n_points, uint32_t sample, uint6
     hipLaunchKernelGGL(spira::k_gather_rays<T>, dim3((n_points + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
     return s.close();
 }
-template <class T>
-int gather_rays_entry(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::gather_rays_impl_f32(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
-    else
-#endif
-        return gather_rays_impl<T>(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
-}
+SPIRA_ENTRY(gather_rays_entry, gather_rays_impl)
 
 // ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
 // The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
@@ -2088,15 +1952,7 @@ int scene_update_impl(spira_scene *h, const T *spheres5, const T *materials8, co
     return sess.close();
 }
 
-// scene_update_impl<T> of whichever translation unit holds the kernels of T
-template <class T>
-int scene_update_entry(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4) return spira_tu::scene_update_impl_f32(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
-    else
-#endif
-        return scene_update_impl<T>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
-}
+SPIRA_ENTRY(scene_update_entry, scene_update_impl)
 
 // ======================================================================= spira_scene_rebuild_*: a new triangle array for a live handle, the tree built anew on the device
 // The arithmetic is spira_lbvh.h's (frame, Morton keys, radix tree, collapse) and spira_refit.h's (records and boxes).  A rebuild produces a frame and a
@@ -2423,15 +2279,7 @@ int scene_rebuild_impl(spira_scene *h, const T *triangles10, const T *d_triangle
     return sess.close();
 }
 
-// scene_rebuild_impl<T> of whichever translation unit holds the kernels of T
-template <class T>
-int scene_rebuild_entry(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4) return spira_tu::scene_rebuild_impl_f32(h, triangles10, d_triangles10, device_form, user_stream);
-    else
-#endif
-        return scene_rebuild_impl<T>(h, triangles10, d_triangles10, device_form, user_stream);
-}
+SPIRA_ENTRY(scene_rebuild_entry, scene_rebuild_impl)
 
 // ---- the a-trous denoiser (spira_denoise_*; spira_denoise.h): prepare, then one launch per iteration between the context's two record buffers, the last
 // one writing the outputs.  The device form enqueues and returns; it allocates only when a workspace has to grow (a first call at a size).
@@ -2496,16 +2344,7 @@ int denoise_impl(const T *color, const T *variance, const T *albedo, const T *no
     return s.close();
 }
 
-template <class T>
-int denoise_entry(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
-                  T *out_hdr, T *out_img, bool on_device, void *user_stream) {
-#ifdef SPIRA_TU_MAIN
-    if constexpr (sizeof(T) == 4)
-        return spira_tu::denoise_impl_f32(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
-    else
-#endif
-        return denoise_impl<T>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
-}
+SPIRA_ENTRY(denoise_entry, denoise_impl)
 
 template <class T>
 int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
@@ -3299,7 +3138,7 @@ void spira_shutdown(void) {
         c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
         c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release(); c.cast_io.release(); c.nearest_io.release(); c.radiance_io.release(); c.gather_io.release();
+        c.refit_status.release(); c.list_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
         c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);

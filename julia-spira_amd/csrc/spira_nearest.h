@@ -1,5 +1,5 @@
 // spira_nearest.h — closest-point queries on a scene handle (spira_scene_closest_point_*): for every point of a caller's list, the nearest point of the
-// scene's surface.  Included by spira_hip.hip behind spira_query.h (CastLimits, kCastOriginBound, CastPlan's knobs); no existing kernel is touched and the
+// scene's surface.  Included by spira_hip.hip behind spira_query.h (CastLimits, kCastOriginBound, CastPlan's knobs, the refilled session's loop); the
 // tree is the one create, update and rebuild maintain — it is walked a second way.  The first part of this file needs no HIP header: a CPU program
 // (tests/native/nearest_plan.cpp) and the exported host arithmetic (spira_closest_point_triangle_*) call the very functions the kernels call.
 //
@@ -51,8 +51,10 @@
 //
 // Kernels (each stages the scene with stage_scene: one barrier):
 //   k_nearest<T, BVH, TRI>     one lane per point, grid-stride: the LDS scan over spheres and LDS triangles; BVH: then the walk to the end (SPIRA_CAST_INPLACE).
-//   k_nearest_session<T>       scenes with a tree, the default: k_cast_session's loop — persistent waves own contiguous ranges of the point list (CastPlan),
-//                              free lanes refill by ballot and popcount prefix while the others keep walking, a finished lane stores straight to out[point].
+//   k_nearest_session<T>       scenes with a tree, the default: SPIRA_REFILLED_SESSION of spira_query.h, the loop k_cast_session runs — persistent waves own
+//                              contiguous ranges of the point list (session_range over a CastPlan), free lanes refill by ballot and popcount prefix while
+//                              the others keep walking, a finished lane stores straight to out[point].  The kernel is the two callables: start = near_load,
+//                              near_scan_local, near_enter; step = near_step.
 // The walk (near_step): ONE memory round trip per trip — a triangle record for a lane with leaf children pending (the scan's own function on the record's
 // own values, in T: the tree only prunes), else a node: its eight child boxes are dequantised, each child's squared distance is computed, children
 // proven farther than best are dropped, the surviving leaves become the pending triangles and the NEAREST surviving child node is visited next.
@@ -129,7 +131,7 @@ template <class T> SPIRA_HD inline bool nearest_point_prepare(const T *pt, bool 
 }  // namespace spira
 
 #if defined(__HIPCC__)
-// Refill threshold and waves per CU of the session kernel: k_cast_session's loop, so its knobs (SPIRA_CAST_REFILL, SPIRA_CAST_WAVES_PER_CU; CastKnobs, read
+// Refill threshold and waves per CU of the session kernel: the loop k_cast_session runs, so its knobs (SPIRA_CAST_REFILL, SPIRA_CAST_WAVES_PER_CU; CastKnobs, read
 // per call as cast reads them) are the starting point; docs/experiments.md, "closest-point queries", says what a sweep on the device kept.
 namespace spira {
 
@@ -329,49 +331,35 @@ __global__ __launch_bounds__(kBlock) void k_nearest(const NearestArgs<T> a) {
     }
 }
 
-// Scenes with a tree: a refilled session per wave over its range of the caller's list (k_cast_session's loop).
+// Scenes with a tree: a refilled session per wave over its range of the caller's list (SPIRA_REFILLED_SESSION of spira_query.h).
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_nearest_session(const NearestArgs<T> a) {
     extern __shared__ __attribute__((aligned(32))) unsigned char lds_raw[];
     const SceneLds<T> sc = stage_scene<T>(a.scene, lds_raw);     // the only workgroup barrier of the kernel
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t wid = blockIdx.x * (kBlock / 64) + wave;
-    const uint32_t begin = wid * a.base + (wid < a.rem ? wid : a.rem), end = begin + a.base + (wid < a.rem ? 1u : 0u);
+    uint32_t begin, end;
+    session_range(a.base, a.rem, begin, end);
     uint32_t stack[kBvhStackD];
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     const int base = (int)(sc.n_spheres + sc.n_triangles);
-    uint32_t next = begin;                                       // wave-uniform: the next point of the range nobody has taken
-    bool walking = false;
     uint32_t pt = 0;
     T r_max = 0;
     NearWalk<T> w{};
-    while (true) {
-        // ---- refill: the free lanes take the next points of the range, in index order
-        const unsigned long long mf = __ballot(!walking);
-        const uint32_t n_free = (uint32_t)__popcll(mf), rank = (uint32_t)__popcll(mf & lt_mask);
-        const uint32_t take = min(n_free, end - next);
-        if (!walking && rank < take) {
-            pt = next + rank;
+    const auto start = [&](uint32_t item) -> bool {
+            pt = item;
             const bool ok = near_load<T>(a, sc, true, pt, w, r_max);
+            bool walks = false;
             if (ok) {
                 near_scan_local<T, false>(a, sc, w);
-                if (near_enter<T>(sc, w)) walking = true;
+                walks = near_enter<T>(sc, w);
             }
-            if (!walking) near_store<T>(a, pt, ok, w, r_max);
-        }
-        next += take;
-        if (!__any(walking)) { if (next < end) continue; break; }
-        // ---- walk; leave the loop when enough lanes are free for a refill to pay (or, with the range exhausted, when all are done)
-        const bool more = next < end;
-        while (true) {
-            if (walking && !near_step<T>(sc, w, base, stack)) {
-                walking = false;
-                near_store<T>(a, pt, true, w, r_max);
-            }
-            const uint32_t n_walk = (uint32_t)__popcll(__ballot(walking));
-            if (n_walk == 0 || (more && 64u - n_walk >= a.refill_free)) break;
-        }
-    }
+            if (!walks) near_store<T>(a, pt, ok, w, r_max);
+            return walks;
+    };
+    const auto step = [&]() -> bool {
+            if (near_step<T>(sc, w, base, stack)) return true;
+            near_store<T>(a, pt, true, w, r_max);
+            return false;
+    };
+    SPIRA_REFILLED_SESSION(begin, end, a.refill_free, start, step);
 }
 
 }  // namespace spira

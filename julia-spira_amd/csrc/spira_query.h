@@ -29,6 +29,8 @@
 //                                 lane takes the next ray of the range (ballot / popcount prefix, a wave-uniform `next`), prepares it, runs the LDS scan,
 //                                 enters the tree; all walking lanes take bvh8_step trips together; the walk loop is left when refill_free lanes are free
 //                                 and rays remain, or none walks.  A finished lane stores straight to out[ray]: no compaction, no queue.
+//                                 The same loop runs k_nearest_session (spira_nearest.h) and k_gather_visible_session (spira_gather.h): for those two it
+//                                 is written once, SPIRA_REFILLED_SESSION below, with the helpers session_range and session_lstack.
 //   ANY = true                    occlusion: only `hit` is written; a lane whose LDS scan hit never walks, a walking lane leaves after the first trip that
 //                                 set prim >= 0.
 // Both organisations run the scan's own leaf test on the same values — the tree only prunes — so they give identical bytes.
@@ -147,7 +149,54 @@ __global__ __launch_bounds__(kBlock) void k_cast(const CastArgs<T> a) {
     }
 }
 
-// Scenes with a tree: a refilled traversal session per wave over its range of the caller's list.
+// A wave's range of a list split by a CastPlan: wave w owns base + (w < rem) items from w base + min(w, rem).
+__device__ __forceinline__ void session_range(uint32_t base, uint32_t rem, uint32_t &begin, uint32_t &end) {
+    const uint32_t wid = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    begin = wid * base + (wid < rem ? wid : rem); end = begin + base + (wid < rem ? 1u : 0u);
+}
+// The wave's LDS stack levels ([level][lane], kCastLdsStack of them) behind the staged scene: what bvh8_step takes as lstack.
+template <class T>
+__device__ __forceinline__ uint32_t *session_lstack(unsigned char *lds_raw, const SceneGlobal<T> &g) {
+    return reinterpret_cast<uint32_t *>(lds_raw + scene_lds_bytes<T>(g.n_spheres, g.n_materials, g.n_triangles)) + (size_t)(threadIdx.x >> 6) * (kCastLdsStack > 0 ? kCastLdsStack : 1) * 64;
+}
+
+// The refilled session of one wave over the items [begin, end) — the loop of k_nearest_session and k_gather_visible_session (and k_cast_session's, which keeps its own copy below), and nothing
+// else: the lane's query (ray or point, closest and prim, the walk, the stack) stays in the kernel, in locals the two callables capture by reference.
+//   start(item) -> bool    a free lane takes `item`: loads and classifies it, scans LDS, tries to enter the tree.  true: the lane now walks; false: it
+//                          finished at once and has stored its answer itself.
+//   step() -> bool         one trip of a walking lane.  false: that was its last — the answer is stored, the lane is free.
+// Free lanes take the next items in index order (ballot / popcount prefix; `next` is wave-uniform); the walk loop is left when refill_free lanes are
+// free and items remain, or when nobody walks.
+// A macro, not a function template, on a measurement (docs/experiments.md section 32): a function holding this loop is simplified on its own
+// before it is inlined into the kernel, with the lane's state behind the closures' pointers; the values forwarded there stay beside the registers the
+// kernel's locals become — 10 more VGPRs in Float64, one occupancy step, 10 % of the rays per second.  Expanded in the kernel it compiles as written out.
+#define SPIRA_REFILLED_SESSION(begin, end, refill_free, start, step)                                                                         \
+    do {                                                                                                                                     \
+        const unsigned long long lt_mask_ = (1ull << (threadIdx.x & 63)) - 1ull;                                                             \
+        const uint32_t end_ = (end), refill_free_ = (refill_free);                                                                           \
+        uint32_t next_ = (begin);                                /* wave-uniform: the next item of the range nobody has taken */            \
+        bool walking_ = false;                                                                                                               \
+        while (true) {                                                                                                                       \
+            /* ---- refill: the free lanes take the next items of the range, in index order */                                             \
+            const unsigned long long mf_ = __ballot(!walking_);                                                                              \
+            const uint32_t n_free_ = (uint32_t)__popcll(mf_), rank_ = (uint32_t)__popcll(mf_ & lt_mask_);                                    \
+            const uint32_t take_ = min(n_free_, end_ - next_);                                                                               \
+            if (!walking_ && rank_ < take_) walking_ = start(next_ + rank_);                                                                 \
+            next_ += take_;                                                                                                                  \
+            if (!__any(walking_)) { if (next_ < end_) continue; break; }                                                                     \
+            /* ---- walk; leave the loop when enough lanes are free for a refill to pay (or, with the range exhausted, when all are done) */ \
+            const bool more_ = next_ < end_;                                                                                                 \
+            while (true) {                                                                                                                   \
+                if (walking_) walking_ = step();                                                                                             \
+                const uint32_t n_walk_ = (uint32_t)__popcll(__ballot(walking_));                                                             \
+                if (n_walk_ == 0 || (more_ && 64u - n_walk_ >= refill_free_)) break;                                                         \
+            }                                                                                                                                \
+        }                                                                                                                                    \
+    } while (0)
+
+// Scenes with a tree: a refilled traversal session per wave over its range of the caller's list.  The loop is written out here and not taken from SPIRA_REFILLED_SESSION:
+// with the macro the closest-hit Float32 instantiation lost 1.5 % on coherent camera rays (docs/experiments.md section 32.4); a change to the loop's exits
+// is made in both places.
 template <class T, bool ANY>
 __global__ __launch_bounds__(kBlock) void k_cast_session(const CastArgs<T> a) {
     constexpr int KL = kCastLdsStack;

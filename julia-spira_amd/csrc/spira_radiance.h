@@ -31,6 +31,9 @@
 //                             and writes the valid byte.  More samples per pass: L goes to the Pack3<T> workspace, entry = item.
 //   k_radiance_sum<T>         one lane per ray: adds the ray's workspace entries in sample order and writes the valid byte.
 //   k_camera_rays<T>          one lane per ray, the six values through LDS so that the workgroup's stores are contiguous.
+// Two bodies are written once, here, for these kernels and their twins of spira_gather.h: path_sum_loop (the two sum kernels: the callable is the validity
+// of an entry) and rays_through_tile (the two generators: the callable writes the six values of ray k).  k_radiance and k_gather keep a loop each: one body
+// for both, taking the fresh-item block as a callable, measured 1-4 % slower on the Float64 instantiations (docs/experiments.md section 32).
 #pragma once
 #include <cstdint>
 
@@ -161,6 +164,38 @@ __device__ __forceinline__ bool radiance_load(const T *rays, uint32_t ray, Vec<T
     return ok;
 }
 
+// The body of k_radiance_sum and k_gather_sum: one lane per list entry; the pass's workspace entries of every entry valid(k) accepts, added in sample order.
+template <class T, class Args, class Valid>
+__device__ __forceinline__ void path_sum_loop(const Args &a, uint32_t n, Valid valid) {
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < n; k += gridDim.x * kBlock) {
+        const bool ok = valid(k);
+        if (a.valid && a.write_valid) a.valid[k] = ok ? (uint8_t)1 : (uint8_t)0;
+        if (!ok) continue;
+        T *sp = a.sum + 3 * (size_t)k;
+        T x = sp[0], y = sp[1], z = sp[2];
+        const Pack3<T> *l = a.ws + (size_t)k * a.spp_pass;
+        for (uint32_t s = 0; s < a.spp_pass; ++s) { x = x + l[s].x; y = y + l[s].y; z = z + l[s].z; }
+        sp[0] = x; sp[1] = y; sp[2] = z;
+    }
+}
+
+// The body of k_camera_rays and k_gather_rays: one lane per ray, gen(k, out6) for k < n, the six values through the workgroup's LDS tile so that its stores
+// are contiguous.  The grid covers n: one workgroup per kBlock rays.
+template <class T, class Gen>
+__device__ __forceinline__ void rays_through_tile(T *tile, T *rays, uint32_t n, Gen gen) {
+    const uint32_t first = blockIdx.x * kBlock, k = first + threadIdx.x;
+    if (k < n) {
+        T out6[6];
+        gen(k, out6);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) tile[6 * threadIdx.x + c] = out6[c];
+    }
+    __syncthreads();
+    const uint32_t n_here = min((uint32_t)kBlock, n - first) * 6;              // first < n for every workgroup of the grid
+    T *dst = rays + 6 * (size_t)first;
+    for (uint32_t v = threadIdx.x; v < n_here; v += kBlock) dst[v] = tile[v];
+}
+
 // Launch bounds: the workgroup size alone, as k_mega — the body is k_mega's, and the resource report shows the same registers.
 template <class T, bool BVH, bool EXT>
 __global__ __launch_bounds__(kBlock) void k_radiance(const RadianceArgs<T> a) {
@@ -207,17 +242,10 @@ __global__ __launch_bounds__(kBlock) void k_radiance(const RadianceArgs<T> a) {
 // The pass's workspace entries of every valid ray, added in sample order.
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_radiance_sum(const RadianceArgs<T> a) {
-    for (uint32_t ray = blockIdx.x * kBlock + threadIdx.x; ray < a.n_rays; ray += gridDim.x * kBlock) {
+    path_sum_loop<T>(a, a.n_rays, [&](uint32_t ray) -> bool {
         Vec<T> o, d;
-        const bool ok = radiance_load<T>(a.rays, ray, o, d);
-        if (a.valid && a.write_valid) a.valid[ray] = ok ? (uint8_t)1 : (uint8_t)0;
-        if (!ok) continue;
-        T *sp = a.sum + 3 * (size_t)ray;
-        T x = sp[0], y = sp[1], z = sp[2];
-        const Pack3<T> *l = a.ws + (size_t)ray * a.spp_pass;
-        for (uint32_t s = 0; s < a.spp_pass; ++s) { x = x + l[s].x; y = y + l[s].y; z = z + l[s].z; }
-        sp[0] = x; sp[1] = y; sp[2] = z;
-    }
+        return radiance_load<T>(a.rays, ray, o, d);
+    });
 }
 
 template <class T> struct CameraRaysArgs {
@@ -231,18 +259,10 @@ template <class T> struct CameraRaysArgs {
 template <class T>
 __global__ __launch_bounds__(kBlock) void k_camera_rays(const CameraRaysArgs<T> a) {
     __shared__ T tile[kBlock * 6];
-    const uint32_t first = blockIdx.x * kBlock, k = first + threadIdx.x;      // (the grid covers n: one workgroup per kBlock rays)
-    if (k < a.n) {
+    rays_through_tile<T>(tile, a.rays, a.n, [&](uint32_t k, T out6[6]) {
         const uint32_t r = fastdiv(k, a.fd_width), ix = k - r * a.width;
-        T out6[6];
         camera_ray_generate<T>(a.cam, a.model, a.width, a.height, a.sA, a.sB, ix, a.row0 + r, a.sample, a.lens_radius, out6);
-#pragma unroll
-        for (int c = 0; c < 6; ++c) tile[6 * threadIdx.x + c] = out6[c];
-    }
-    __syncthreads();
-    const uint32_t n_here = min((uint32_t)kBlock, a.n - first) * 6;             // first < n for every workgroup of the grid
-    T *dst = a.rays + 6 * (size_t)first;
-    for (uint32_t v = threadIdx.x; v < n_here; v += kBlock) dst[v] = tile[v];
+    });
 }
 
 }  // namespace spira

@@ -168,6 +168,32 @@ def test_open_sky_is_all_visible_and_the_closed_box_is_all_occluded(gpu, prec):
         assert (h.gather_visible(inside, 64, t_max=0.5, seed=SEED) == 64).all()         # ... and nothing within half a unit of them
 
 
+@pytest.mark.parametrize("refill", ["1", "64"])
+@pytest.mark.parametrize("n_points,spp", [(125, 8), (111, 9)])
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_visible_session_refills_at_both_ends_of_the_threshold(gpu, prec, n_points, spp, refill, monkeypatch):
+    """k_gather_visible_session against its in-place twin, by bytes, on the smallest tree (the 33-triangle shell of tests/nearest_support.py) at the two ends
+    of the walk loop's exit condition: SPIRA_CAST_REFILL 64 refills only when the whole wave is free, 1 after every finished lane.  SPIRA_CAST_WAVES_PER_CU 1
+    and 128 items per wave at the least leave 4 waves of about 250 items: every wave refills.  125 x 8 = 1 000 items divide among them evenly; 111 x 9 = 999
+    leave rem = 3, so the ranges of base + 1 items are walked as well.  Points on and off the shell, normals outward and inward: rays that miss the mesh's
+    box, rays that walk and escape, rays that hit."""
+    from nearest_support import ico_scene
+    s = ico_scene(33)
+    tri = bake.triangle_points(s["triangles10"])
+    lifted = [np.concatenate([tri[:, 0:3] + off * tri[:, 3:6], sign * tri[:, 3:6]], axis=1) for off, sign in ((0.01, 1.0), (0.01, -1.0), (0.3, -1.0), (-0.3, 1.0))]
+    pts = np.concatenate(lifted)[:n_points]
+    n = n_points * spp
+    monkeypatch.setenv("SPIRA_CAST_REFILL", refill)
+    monkeypatch.setenv("SPIRA_CAST_WAVES_PER_CU", "1")
+    plan = gpu.cast_plan(n, 256)
+    assert plan["refill_free"] == int(refill) and plan["base"] > 64 and plan["base"] * plan["waves"] + plan["rem"] == n and (plan["rem"] != 0) == (n == 999), plan
+    with _handle(gpu, s, prec) as h:
+        got, valid = h.gather_visible(pts, spp, t_min=1e-3, seed=SEED, key0=7, want_valid=True)
+        inpl, v_inpl = h.gather_visible(pts, spp, t_min=1e-3, seed=SEED, key0=7, want_valid=True, inplace=True)
+    assert got.dtype == np.uint32 and got.tobytes() == inpl.tobytes() and valid.tobytes() == v_inpl.tobytes() and valid.all()
+    assert got.max() == spp and got.min() < spp // 2                 # open sky above some points, the shell or the ground around others
+
+
 # ---------------------------------------------------------------------------------- contracts, bitwise
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_sample_ranges_passes_and_grids(gpu, prec, monkeypatch):

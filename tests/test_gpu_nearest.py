@@ -90,6 +90,32 @@ def test_invalid_points_never_disturb_their_neighbours(gpu, prec):
             assert np.array_equal(prim[at[:-1] + 1], ref["prim"][at[:-1] + 1]) and (prim[at[:-1] + 1] >= 0).all()
 
 
+@pytest.mark.parametrize("refill", [1, 64])
+@pytest.mark.parametrize("n", [1000, 999])
+@pytest.mark.parametrize("prec", ["f32", "f64"])
+def test_session_refills_at_both_ends_of_the_threshold(gpu, prec, n, refill):
+    """k_nearest_session against its in-place twin, by bytes, on the smallest tree (33 triangles) at the two ends of the walk loop's exit condition:
+    SPIRA_CAST_REFILL 64 refills only when the whole wave is free, 1 after every finished lane.  SPIRA_CAST_WAVES_PER_CU 1 and 128 points per wave at the
+    least leave 4 waves of about 250 points: every wave refills.  1 000 divides among them evenly; 999 leaves rem = 3, so the ranges of base + 1 points are
+    walked as well.  Both organisations are also held to the scan."""
+    from test_gpu_bvh import _with_env
+    ref = N.reference("ico33", prec)
+    pick = np.arange(n) * 37 % len(ref["points"])                    # points of every kind
+    pts = ref["points"][pick]
+
+    def go():
+        plan = gpu.cast_plan(n, 256)
+        assert plan["refill_free"] == refill and plan["base"] > 64 and plan["base"] * plan["waves"] + plan["rem"] == n and (plan["rem"] != 0) == (n == 999), plan
+        with _open(gpu, N.scene("ico33"), prec) as h:
+            _check(h, pts, ref["prim"][pick], ref["dist"][pick], ref["point"][pick])
+            _poison(h, n)
+            return h.closest_point(pts), h.closest_point(pts, inplace=True)
+    session, inplace = _with_env(gpu, {"SPIRA_CAST_REFILL": str(refill), "SPIRA_CAST_WAVES_PER_CU": "1"}, go)
+    for a, b in zip(session[:3], inplace[:3]):                       # prim, dist, point
+        assert a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+    assert (session[0] >= 1).sum() > n // 4                          # triangle winners: lanes that walked
+
+
 @functools.lru_cache(maxsize=None)
 def _frame_case(prec, fi, how):
     """The blob mesh in placement fi; how = create: as built; update: twisted (test_gpu_refit.deform), the validity frame stays the creation frame;
