@@ -358,6 +358,41 @@ int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_ray
 int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags,
                                     uint8_t *d_out_hit, void *stream);
 
+/* ---- multi-hit ray queries on a scene handle: the first max_hits hits of every ray, in order (thickness, x-ray sums, layered picking, crossing counts) ----
+ * rays8, the preparation, the invalid-ray rule and the origin rule are exactly those of spira_scene_cast_*.
+ * Candidates: object k — spheres [0..) then triangles [0..) in the caller's order — is a candidate of a valid ray when the reference's per-object test
+ * (hit_sphere, hit_triangle: examples/julia-raytracer.jl:113-187) accepts it with the ray's own t_min and t_max, and t_k is the t that test returns.  A
+ * sphere contributes at most one candidate: the near root, or the far root when the near one is below t_min.
+ * Order: t ascending and, among equal t, object index DESCENDING — the later object first, the closest-hit tie rule.  The answer is the first max_hits
+ * candidates of that order; with max_hits == 1, out_prim and out_t are byte for byte those of spira_scene_cast_*.
+ * Outputs, caller-owned: out_prim and out_t are n_rays x max_hits, ray-major; slot j of ray i holds the j-th hit; unused slots hold SPIRA_RAY_MISS and
+ * the ray's t_max copied; every slot of an invalid ray holds SPIRA_RAY_INVALID and 0.  out_count[i] (n_rays): without SPIRA_HITS_COUNT_ALL the number of
+ * slots filled (<= max_hits); with the flag the number of ALL candidates of the ray — the walk then prunes with t_max only; 0 for an invalid ray.  With the
+ * flag max_hits may be 0 and out_prim / out_t may be NULL (count only: out_count is then required); otherwise max_hits is in 1 .. SPIRA_MAX_HITS.  Each
+ * output may be NULL, but not all three.
+ * Pruning: once K = max_hits hits are known, an object is tested against the K-th t instead of the ray's t_max (not under SPIRA_HITS_COUNT_ALL).  That
+ * is exact: the bits of an object's t do not depend on the bound passed (both tests compute t, then compare); a candidate beyond the K-th t of the hits
+ * known so far is not among the first K of all; a sphere whose near root lies beyond the bound has its far root beyond it too; and a candidate AT the
+ * K-th t is still accepted and placed by its index.  csrc/spira_hits.h has the argument in full.
+ * flags: 0, SPIRA_CAST_INPLACE (one lane per ray walking to the end, the comparison point), SPIRA_HITS_COUNT_ALL, or both.  The order is total, so the
+ * order in which a walk meets the candidates cannot matter: both organisations give identical bytes.
+ * Errors, all decided before any device is touched: a NULL ray array, n_rays == 0, unknown flag bits, max_hits > SPIRA_MAX_HITS, max_hits == 0 without
+ * SPIRA_HITS_COUNT_ALL, every output NULL (with max_hits == 0: out_count NULL), a NULL or destroyed handle, one of the other precision or of another
+ * device: SPIRA_E_INVALID; n_rays > SPIRA_MAX_RAYS, or n_rays * max_hits > SPIRA_MAX_RAYS (the product formed in 64 bits): SPIRA_E_LIMIT.  A handle made
+ * by spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The *_device_*
+ * form takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a query enqueued
+ * after a device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+#define SPIRA_MAX_HITS        16u
+#define SPIRA_HITS_COUNT_ALL  0x2u      /* beside SPIRA_CAST_INPLACE 0x1u */
+int spira_scene_cast_hits_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags,
+                              int *out_prim, float *out_t, uint32_t *out_count);
+int spira_scene_cast_hits_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags,
+                              int *out_prim, double *out_t, uint32_t *out_count);
+int spira_scene_cast_hits_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags,
+                                     int *d_out_prim, float *d_out_t, uint32_t *d_out_count, void *stream);
+int spira_scene_cast_hits_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags,
+                                     int *d_out_prim, double *d_out_t, uint32_t *d_out_count, void *stream);
+
 /* ---- closest-point queries on a scene handle: for the CALLER'S points, the nearest point of the scene's surface (distance fields, proximity, snapping) ----
  * What Embree calls a point query, on the tree that create, update and rebuild maintain, which only prunes: prim, dist and point are bit for bit a scan's.
  * points4: n_points x [px py pz r_max], in the call's precision T.  The scan runs over spheres [0..) then triangles [0..) in the caller's order with

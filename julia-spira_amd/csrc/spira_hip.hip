@@ -47,6 +47,7 @@
 #include "spira_radiance.h"
 #include "spira_gather.h"
 #include "spira_nearest.h"
+#include "spira_hits.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -83,6 +84,8 @@ int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uin
                   bool any, bool on_device, void *user_stream);
 int nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point, uint32_t *out_trips,
                      bool on_device, void *user_stream);
+int hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count,
+                  bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -1632,6 +1635,41 @@ int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint
 }
 SPIRA_ENTRY(nearest_entry, nearest_impl)
 
+// ======================================================================= spira_scene_cast_hits_*: the first max_hits hits of every ray, in order
+// Kernels, the list and the pruning argument: spira_hits.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels whose
+// list capacity (1, 4 or 16) is the smallest that holds max_hits.  The device form touches no workspace of the context (it allocates nothing); the host
+// form stages rays and outputs.
+template <class T, int CAP>
+ListKernels<spira::HitsArgs<T>> hits_kernels() {
+    return {spira::k_hits_session<T, CAP>, spira::k_hits<T, true, false, CAP>, spira::k_hits<T, false, true, CAP>, spira::k_hits<T, false, false, CAP>, true};
+}
+template <class T>
+int hits_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, T *out_t, uint32_t *out_count,
+              bool on_device, void *user_stream) {
+    using A = spira::HitsArgs<T>;
+    const char *msg = nullptr;
+    if (max_hits == 0) { out_prim = nullptr; out_t = nullptr; }      // (count only: the lists have no slots)
+    if (int rc = spira::hits_check(rays8 != nullptr, n_rays, max_hits, flags, out_prim || out_t || out_count, &msg)) return fail(rc, msg);
+    const ListKernels<A> kernels = max_hits <= 1 ? hits_kernels<T, 1>() : max_hits <= 4 ? hits_kernels<T, 4>() : hits_kernels<T, 16>();
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n_rays = n_rays; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.max_hits = max_hits; a.count_all = (flags & SPIRA_HITS_COUNT_ALL) ? 1u : 0u;
+    const size_t n = n_rays, slots = n * max_hits, prim_b = slots * sizeof(int);
+    // [rays | t | prim | pad | count]: every block starts at a multiple of sizeof(T) or more (pad: a NULL block that rounds prim up to 8 bytes)
+    StageBlock io[] = {{(void *)rays8, 8 * n * sizeof(T), kStageIn}, {out_t, slots * sizeof(T), kStageOut}, {out_prim, prim_b, kStageOut}, {nullptr, prim_b & 4, 0},
+                       {out_count, n * sizeof(uint32_t), kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.rays = (const T *)io[0].dev; a.t = (T *)io[1].dev; a.prim = (int *)io[2].dev; a.count = (uint32_t *)io[4].dev;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
+SPIRA_ENTRY(hits_entry, hits_impl)
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2823,6 +2861,10 @@ int spira_tu::nearest_impl_f32(const spira_scene *h, const float *points4, uint3
                                uint32_t *out_trips, bool on_device, void *user_stream) {
     return nearest_impl<float>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
 }
+int spira_tu::hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count,
+                            bool on_device, void *user_stream) {
+    return hits_impl<float>(h, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -2902,6 +2944,21 @@ int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_ray
 }
 int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags, uint8_t *d_out_hit, void *stream) {
     return cast_entry<double>(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
+}
+// ---- multi-hit ray queries (spira_hits.h)
+int spira_scene_cast_hits_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count) {
+    return hits_entry<float>(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
+}
+int spira_scene_cast_hits_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, double *out_t, uint32_t *out_count) {
+    return hits_entry<double>(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
+}
+int spira_scene_cast_hits_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *d_out_prim, float *d_out_t,
+                                     uint32_t *d_out_count, void *stream) {
+    return hits_entry<float>(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
+}
+int spira_scene_cast_hits_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *d_out_prim, double *d_out_t,
+                                     uint32_t *d_out_count, void *stream) {
+    return hits_entry<double>(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
 }
 // Test support, outside the ABI like spira_debug_scene_tree: the launch plan a cast of n_rays would get on a device of num_cus CUs, with the knobs of the
 // environment as the entries read them.  out8: grid, wpb, waves, base, rem, refill_free, grid_flat, kCastMinRaysPerWave.  No device needed.

@@ -395,6 +395,18 @@ inline int nearest_check(bool points, uint32_t n_points, uint32_t flags, bool an
     if (n_points > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) points"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_cast_hits_*: cast's rules, then the list's.  any_output: out_prim, out_t or out_count is given — with max_hits == 0 only out_count is one.
+inline int hits_check(bool rays, uint32_t n_rays, uint32_t max_hits, uint32_t flags, bool any_output, const char **msg) {
+    if (!rays) { *msg = "the ray array is NULL"; return SPIRA_E_INVALID; }
+    if (n_rays == 0) { *msg = "n_rays is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~(SPIRA_CAST_INPLACE | SPIRA_HITS_COUNT_ALL)) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE and SPIRA_HITS_COUNT_ALL are the only ones)"; return SPIRA_E_INVALID; }
+    if (max_hits > SPIRA_MAX_HITS) { *msg = "max_hits is above SPIRA_MAX_HITS (16)"; return SPIRA_E_INVALID; }
+    if (max_hits == 0 && !(flags & SPIRA_HITS_COUNT_ALL)) { *msg = "max_hits is 0 without SPIRA_HITS_COUNT_ALL"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = max_hits ? "out_prim, out_t and out_count are all NULL" : "max_hits is 0 and out_count is NULL: nothing to write"; return SPIRA_E_INVALID; }
+    if (n_rays > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) rays"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)n_rays * max_hits > SPIRA_MAX_RAYS) { *msg = "n_rays * max_hits is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
+    return 0;
+}
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

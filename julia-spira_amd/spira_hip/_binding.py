@@ -27,6 +27,9 @@ EXT_DIELECTRIC, EXT_SPECTRAL = 0x20000, 0x40000
 MAX_RAYS = 1 << 26
 RAY_MISS, RAY_INVALID = -1, -3
 CAST_INPLACE = 0x1
+# ---- multi-hit ray queries (spira_scene_cast_hits_*) ----
+MAX_HITS = 16
+HITS_COUNT_ALL = 0x2
 # ---- camera models of the ray generator (spira_camera_rays_*) ----
 CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO = 0, 1, 2
 MAX_DEPTH, MAX_SPP = 255, 1 << 24
@@ -57,6 +60,7 @@ EXPORTS = [
     "spira_scene_gather_visible_f32", "spira_scene_gather_visible_f64", "spira_scene_gather_visible_device_f32", "spira_scene_gather_visible_device_f64",
     "spira_scene_closest_point_f32", "spira_scene_closest_point_f64", "spira_scene_closest_point_device_f32", "spira_scene_closest_point_device_f64",
     "spira_closest_point_triangle_f32", "spira_closest_point_triangle_f64",
+    "spira_scene_cast_hits_f32", "spira_scene_cast_hits_f64", "spira_scene_cast_hits_device_f32", "spira_scene_cast_hits_device_f64",
 ]
 
 
@@ -460,6 +464,32 @@ class Scene:
         fn = lib().spira_scene_occluded_device_f32 if self.prec == "f32" else lib().spira_scene_occluded_device_f64
         _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
                   C.c_void_p(stream_ptr or None)))
+
+    def cast_hits(self, rays8, max_hits, inplace=False, count_all=False, want_prim=True, want_t=True, want_count=True):
+        """spira_scene_cast_hits_*: the first max_hits hits of every ray of rays8 (host array, as for cast), ordered by t ascending and, among equal t, by
+        object index descending.  Returns (prim int32 [n, K], t [n, K], count uint32 [n]), None where not wanted (with max_hits = 0 the lists are None):
+        unused slots hold RAY_MISS and the ray's t_max, every slot of an invalid ray RAY_INVALID and 0.  count: the slots filled, or with count_all every
+        candidate of the ray (the walk then prunes with t_max only; max_hits may be 0).  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        r = self._rays(rays8)
+        n, k = len(r), int(max_hits)
+        room = k if 0 < k <= MAX_HITS else 1      # (a refused max_hits: the entry says so)
+        prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
+        t = np.empty((n, room), dtype=npdt) if want_t and k else None
+        count = np.empty(n, dtype=np.uint32) if want_count else None
+        fn = lib().spira_scene_cast_hits_f32 if self.prec == "f32" else lib().spira_scene_cast_hits_f64
+        flags = (CAST_INPLACE if inplace else 0) | (HITS_COUNT_ALL if count_all else 0)
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(flags),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, count)]))
+        return prim, t, count
+
+    def cast_hits_device(self, d_rays_ptr, n_rays, max_hits, d_prim_ptr, d_t_ptr, d_count_ptr, stream_ptr, inplace=False, count_all=False):
+        """spira_scene_cast_hits_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        fn = lib().spira_scene_cast_hits_device_f32 if self.prec == "f32" else lib().spira_scene_cast_hits_device_f64
+        flags = (CAST_INPLACE if inplace else 0) | (HITS_COUNT_ALL if count_all else 0)
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(max_hits), C.c_uint32(flags), C.c_void_p(d_prim_ptr or None),
+                  C.c_void_p(d_t_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(stream_ptr or None)))
 
     def closest_point(self, points4, inplace=False, want_prim=True, want_dist=True, want_point=True, want_trips=False):
         """spira_scene_closest_point_*: for every point of points4 (n x [px py pz r_max], host array) the nearest point of the scene's surface within r_max.

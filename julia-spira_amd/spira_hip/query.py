@@ -1,5 +1,5 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
-spira_scene_cast_device_* / spira_scene_occluded_device_*.
+spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries.
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
 s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s); t, t_min and t_max are distances along that unit direction."""
@@ -51,6 +51,70 @@ def cast_rays(scene, rays, want_normal=False, occlusion=False, inplace=False, st
         nrm = torch.empty((n, 3), dtype=want, device=rays.device) if want_normal else None
         scene.cast_device(rays.data_ptr(), n, prim.data_ptr(), t.data_ptr(), nrm.data_ptr() if want_normal else 0, st.cuda_stream, inplace=inplace)
     return prim, t, nrm
+
+
+# ------------------------------------------------------------------ multi-hit ray queries (spira_scene_cast_hits_*; csrc/spira_hits.h)
+def cast_all(scene, rays, max_hits, count_all=False, inplace=False, want_prim=True, want_t=True, stream=None):
+    """The first max_hits hits of every ray, ordered by t ascending and, among equal t, by object index descending: (prim int32 [n, K], t [n, K],
+    count [n]), None where not wanted.  rays: a host array [n, 8] — the host form, numpy arrays back — or a torch tensor on the scene's device in the
+    scene's precision — spira_scene_cast_hits_device_*, enqueued on `stream` (a torch.cuda.Stream; None: the current one), device tensors back without
+    synchronising (count as int32); `rays` must stay alive until the work has run.  count_all: count every candidate of the ray, not the slots filled."""
+    if isinstance(rays, np.ndarray) or not hasattr(rays, "is_cuda"):
+        return scene.cast_hits(rays, max_hits, inplace=inplace, count_all=count_all, want_prim=want_prim, want_t=want_t)
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if rays.dtype != want or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+        raise ValueError("cast_all: a contiguous device tensor of n x 8 %s values is needed" % scene.prec)
+    n, k = rays.shape[0], int(max_hits)
+    room = k if 0 < k <= B.MAX_HITS else 1
+    st = stream if stream is not None else torch.cuda.current_stream(rays.device)
+    with torch.cuda.stream(st):
+        prim = torch.empty((n, room), dtype=torch.int32, device=rays.device) if want_prim and k else None
+        t = torch.empty((n, room), dtype=want, device=rays.device) if want_t and k else None
+        count = torch.empty(n, dtype=torch.int32, device=rays.device)
+        scene.cast_hits_device(rays.data_ptr(), n, k, prim.data_ptr() if prim is not None else 0, t.data_ptr() if t is not None else 0, count.data_ptr(),
+                               st.cuda_stream, inplace=inplace, count_all=count_all)
+    return prim, t, count
+
+
+def count_hits(scene, rays, inplace=False, stream=None):
+    """The number of candidates of every ray within its [t_min, t_max] — max_hits = 0 with HITS_COUNT_ALL, no list is kept; 0 for an invalid ray.
+    Host array or device tensor, as cast_all."""
+    return cast_all(scene, rays, 0, count_all=True, inplace=inplace, stream=stream)[2]
+
+
+INSIDE_DIRECTIONS = ((0.5377, 0.7211, 0.4366), (-0.6123, 0.3142, 0.7255), (0.2873, -0.4691, -0.8351))      # fixed, parallel to no axis and no diagonal
+
+
+def inside_mesh(scene, points, max_hits=B.MAX_HITS):
+    """For every point of `points` (host array [n, 3]): is it inside the scene's mesh?  Meant for CLOSED meshes (every edge shared by two triangles, no
+    self-intersection): a ray from an inside point crosses the surface an odd number of times.  Three rays per point along INSIDE_DIRECTIONS (t_min 0,
+    t_max +Inf), the parity of each ray's TRIANGLE crossings, and the majority of the three votes — a ray exactly through an edge or a vertex may count
+    a crossing twice, which is why three directions vote.
+    A scene without spheres: the count alone decides (max_hits = 0 with HITS_COUNT_ALL, no list is kept or copied), whatever the number of crossings.
+    A scene with spheres: a sphere counts once per ray whichever side the origin is on, so its hits say nothing about parity; they are taken out by
+    subtracting the listed hits with prim < n_spheres from the count, which needs the list: max_hits (16 at most) slots per ray.  A ray is only refused
+    (ValueError) when that cannot be done — it has more candidates than slots AND fewer sphere hits listed than the scene has spheres, so a sphere hit
+    may lie beyond the list; with every sphere already listed the crossings beyond the list are all triangles and the count stands.
+    Points the library calls invalid (NaN, infinite, beyond the origin rule) are outside.  Returns bool [n]."""
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    n = len(p)
+    ns = scene.counts[0]
+    k = int(max_hits) if ns else 0
+    if ns and not 0 < k <= B.MAX_HITS:
+        raise ValueError("inside_mesh: a scene with spheres needs the list (max_hits in 1 .. %d) to take their hits out" % B.MAX_HITS)
+    votes = np.zeros(n, dtype=np.int32)
+    for d in INSIDE_DIRECTIONS:
+        rays = np.concatenate([p, np.zeros((n, 1)), np.tile(np.asarray(d, dtype=np.float64), (n, 1)), np.full((n, 1), np.inf)], axis=1)
+        prim, _, count = scene.cast_hits(rays, k, count_all=True, want_t=False)
+        crossings = count.astype(np.int64)
+        if ns:
+            listed = ((prim >= 0) & (prim < ns)).sum(axis=1)
+            if ((count > k) & (listed < ns)).any():
+                raise ValueError("inside_mesh: a ray has more than max_hits = %d candidates and a sphere hit may lie beyond the list" % k)
+            crossings -= listed
+        votes += (crossings % 2 == 1)
+    return votes >= 2
 
 
 # ------------------------------------------------------------------ closest-point queries (spira_scene_closest_point_*; csrc/spira_nearest.h)
