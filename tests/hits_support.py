@@ -50,11 +50,11 @@ def cut(cands, rays, T, K):
     return prim, t, count, total
 
 
-def shells_scene(level, n_shells=10, max_tris=None):
+def shells_scene(level, n_shells=10, max_tris=None, scale=1.0, shift=(0.0, 0.0, 0.0)):
     """Nested shells: n_shells concentric copies of blob_scene(level)'s mesh about its box centre at scales 1.0, 0.9, ... and its two spheres; a ray
     through the centre has about 2 n_shells triangle candidates.  max_tris: the triangles taken round-robin from the shells and cut to that many (<= 32:
-    they stay in LDS)."""
-    b = S.blob_scene(level)
+    they stay in LDS).  scale, shift: blob_scene's placement of everything (cast_support.FRAMES)."""
+    b = S.blob_scene(level, scale, shift)
     tri = np.asarray(b["triangles10"], dtype=np.float64)
     v = tri[:, :9].reshape(-1, 3)
     c = (v.min(axis=0) + v.max(axis=0)) / 2
@@ -124,3 +124,101 @@ def device_frame(binding, h):
     assert fn(h._h, 0, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(need)) == 0
     f = buf[16:48].view(np.float64)
     return f[:3].copy(), float(f[3])
+
+
+# ------------------------------------------------------------------ the sets of the edge tests (test_hits_edges_cpu.py, test_gpu_hits_edges.py): built once
+# per process, left unchanged, shared by the module that asserts what they reach and the module that runs them on the device
+N_SHELLS_FAR = 96
+DUP_SEED, N_DUP = 43, 96
+
+
+def totals(ref):
+    """Candidates per ray, -1 for an invalid ray."""
+    return np.array([-1 if c is None else len(c) for c in ref["cands"]])
+
+
+def straddles(cands, K):
+    """The rays whose candidates at slots K - 1 and K have bit-equal t: a list of K is cut between two candidates that only their index tells apart."""
+    return sum(1 for c in cands if c is not None and len(c) > K and c[K - 1][0] == c[K][0])
+
+
+def interleave(a, b):
+    """a[0], b[0], a[1], b[1], ..."""
+    return np.stack([a, b], axis=1).reshape((-1,) + a.shape[1:])
+
+
+@functools.lru_cache(maxsize=None)
+def nan_rays(n, prec):
+    r = np.full((n, 8), np.nan, dtype=S.dtype_of(prec))
+    r.setflags(write=False)
+    return r
+
+
+def poison(h, n, K, inplace=False):
+    """The host form stages [rays | t | prim | count] in a workspace that outlives the call: after a call with the same n and K it holds that call's
+    answers, and a slot the next call never stores would go unnoticed.  n invalid rays (NaN) with the same K through the same organisation leave
+    -3 / 0 / 0 in every staged slot first.  K = 0 (count only): through a K = 1 call of the same n."""
+    prim, t, count = h.cast_hits(nan_rays(n, h.prec), max(int(K), 1), inplace=inplace)
+    for e in (0, -1):
+        assert (prim[e] == INVALID).all() and not t[e].any() and count[e] == 0
+
+
+@functools.lru_cache(maxsize=None)
+def far_ref(prec, fi):
+    """cast_support.far_set(prec, fi) as far_joined lays it out — 256 far rays interleaved with their invalid twins, then the six t windows of the first
+    64 mesh hits — under the multi-hit yardstick."""
+    fs = S.far_set(prec, fi)
+    return reference(fs["scene"], prec, S.far_joined(fs)["rays"])
+
+
+@functools.lru_cache(maxsize=None)
+def shells_far_ref(prec, fi):
+    """Long lists at far origins: the ten nested shells (800 triangles) in placement FRAMES[fi], 96 rays from 60 .. 64 normalised units away — the odd ones
+    re-aimed near the centre, through every shell — interleaved with their invalid twins."""
+    scene = shells_scene(1, n_shells=10, scale=S.FRAMES[fi][0], shift=S.FRAMES[fi][1])
+    sc = S.Scan(_oracle(), scene, prec)
+    rng = np.random.default_rng(29 + fi)
+    rays, axis, sign = S.rays_far(rng, sc, scene, N_SHELLS_FAR)
+    lo, hi, c, ext = S.target_box(scene)
+    rays[1::2, 4:7] = (c + 0.1 * ext * (rng.random((N_SHELLS_FAR, 3)) - 0.5))[1::2] - rays[1::2, :3]
+    return dict(reference(scene, prec, interleave(rays, S.rays_far_outside(rays, axis, sign, sc))), scene=scene)
+
+
+@functools.lru_cache(maxsize=None)
+def axis_ref(prec):
+    """cast_support.axis_set(prec, 3), parts axis and planes: signed-zero directions, origins on the root box's planes."""
+    a = S.axis_set(prec, 3)
+    return dict(reference(a["scene"], prec, S.join([a["axis"], a["planes"]])["rays"]), scene=a["scene"])
+
+
+@functools.lru_cache(maxsize=None)
+def quad_ref(prec):
+    """cast_support.quad_set(prec), parts quads and axis_far: leaf boxes of zero extent, rays in their planes, axis rays from 60 units away."""
+    q = S.quad_set(prec)
+    return dict(reference(q["scene"], prec, S.join([q["quads"], q["axis_far"]])["rays"]), scene=q["scene"])
+
+
+@functools.lru_cache(maxsize=None)
+def dup_ref(prec):
+    """Ties at every slot: nearest_support's `dup` scene — blob level 3 with every triangle twice, no spheres — so that candidates come in pairs of
+    bit-equal t.  pair[i]: the other triangle with triangle i's vertices (duplicate_scene's own, drawn again from the same seed)."""
+    import nearest_support as N
+    scene = N.scene("dup")
+    twin, pair = S.duplicate_scene(S.blob_scene(3), np.random.default_rng(21))
+    assert np.array_equal(twin["triangles10"], scene["triangles10"])
+    rng = np.random.default_rng(DUP_SEED)
+    rays = S.aim_at_triangles(rng, S.rays_b(rng, scene, N_DUP), scene)
+    pair.setflags(write=False)
+    return dict(reference(scene, prec, rays), scene=scene, pair=pair)
+
+
+def pairs_hold(ref):
+    """Every ray's candidates are whole pairs: entries 2m and 2m + 1 have bit-equal t and are (later index, earlier index) of one duplicated triangle."""
+    pair = ref["pair"]
+    for c in ref["cands"]:
+        if c is None or len(c) % 2:
+            return False
+        for m in range(0, len(c), 2):
+            if not (c[m][0] == c[m + 1][0] and c[m][1] > c[m + 1][1] and pair[c[m][1]] == c[m + 1][1]):
+                return False
+    return True

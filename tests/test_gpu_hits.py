@@ -1,6 +1,6 @@
 """GPU: spira_scene_cast_hits_* (spira_hits.h: k_hits, k_hits_session) against the yardstick of tests/hits_support.py — the oracle's per-object tests on
 every object, sorted by (t ascending, index descending), cut to K — in both precisions, compared with numpy.array_equal on bytes: prim, t and count,
-for K in {1, 2, 3, 16} x flags {0, INPLACE, COUNT_ALL, both}.  Every ray set first proves, on the yardstick's output alone, that it reaches what it is
+for K in {1, 2, 3, 16} x flags {0, INPLACE, COUNT_ALL, both}, each call on a staging poisoned first.  Every ray set first proves, on the yardstick's output alone, that it reaches what it is
 for: rays with more candidates than K, with fewer, with none, and on the ties set two candidates of equal t straddling slots K - 1 / K."""
 import functools
 import os
@@ -78,17 +78,22 @@ def _totals(ref):
     return np.array([-1 if c is None else len(c) for c in ref["cands"]])
 
 
-def _check(h, ref, ks=KS, flags=FLAGS):
+def _check(h, ref, ks=KS, flags=FLAGS, also=None):
+    """Every call on a staging poisoned first (hits_support.poison): a slot the kernel never stores cannot hold the call before's right answer.
+    also(K, inplace, count_all, g_prim, g_t, g_count): further assertions on the same answers."""
     T = ref["sc"].T
     for K in ks:
         prim, t, count, total = H.cut(ref["cands"], ref["prepared"], T, K)
         for inplace, count_all in flags:
+            H.poison(h, len(ref["rays"]), K, inplace)
             g_prim, g_t, g_count = h.cast_hits(ref["rays"], K, inplace=inplace, count_all=count_all)
             want_count = total if count_all else count
             bad = np.flatnonzero((g_prim != prim).any(axis=1) | (g_count != want_count))
             print(ref["sc"].prec, "K", K, "inplace", inplace, "count_all", count_all, "rays", len(prim), "mismatching", len(bad))
             assert np.array_equal(g_prim, prim) and np.array_equal(g_t.view(np.uint8), t.view(np.uint8)) and np.array_equal(g_count, want_count), \
                 (K, inplace, count_all, bad[:8], g_prim[bad[:4]], prim[bad[:4]], g_count[bad[:8]], want_count[bad[:8]])
+            if also is not None:
+                also(K, inplace, count_all, g_prim, g_t, g_count)
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])
@@ -156,6 +161,7 @@ def test_sessions_against_in_place(gpu, prec, n):
                 plan = gpu.cast_plan(n, 256)
                 assert plan["refill_free"] == int(refill) and (n == 5 or (plan["rem"] == 0) == (n == 1000))
                 for (K, ca), w in want.items():
+                    H.poison(h, n, K, False)                     # between `want` and the session call: same n, same K, the same layout
                     got = h.cast_hits(rays, K, count_all=ca)
                     for a, b in zip(got, w):
                         assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (refill, K, ca)

@@ -48,7 +48,7 @@ def _sequences(T, seed):
     equal t meets neighbouring indices.  Each with K and t_max."""
     rng = np.random.default_rng(seed)
     out = []
-    for K in (1, 2, 5, 16):
+    for K in (1, 2, 3, 4, 5, 15, 16):
         for n in (0, 1, 3, 17, 40):
             t_max = T(rng.choice([2.5, 7.0, np.inf]))
             vals = np.array([0.0, 0.5, 1.25, np.nextafter(T(1.25), T(2)), 2.5, float(t_max) if np.isfinite(t_max) else 1e30], dtype=T)
