@@ -440,6 +440,44 @@ int spira_scene_closest_point_device_f64(const spira_scene *scene, const double 
 void spira_closest_point_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float p[3], float out_q[3], float *out_d2);
 void spira_closest_point_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double p[3], double out_q[3], double *out_d2);
 
+/* ---- K-nearest point queries on a scene handle: the max_near closest objects of every point, in order (contacts within a radius, picking among a few
+ *      candidates, smooth-min distance fields, counts within r) ----
+ * points4, the validity rule and the origin rule are exactly those of spira_scene_closest_point_*.
+ * Candidates: object k — spheres [0..) then triangles [0..) in the caller's order — is a candidate of a valid point when d2_k <= best0, with
+ * best0 = r_max * r_max in T; d2_k and q_k are those of the closest-point scan above (the same two functions on the same values, a sphere's radius as
+ * given); a NaN d2 is never a candidate.
+ * Order: d2 ascending and, among equal d2, object index DESCENDING — the later object first, the tie rule of the closest-point scan and of the multi-hit
+ * order.  The answer is the first max_near candidates of that order; with max_near == 1, out_prim, out_dist and out_point are byte for byte those of
+ * spira_scene_closest_point_*.
+ * Outputs, caller-owned, point-major: out_prim and out_dist are n_points x max_near, out_point is n_points x max_near x 3, interleaved; slot j of point i
+ * holds the j-th nearest; out_dist is sqrt(d2) (IEEE).  Unused slots hold SPIRA_RAY_MISS, the point's r_max copied, and point 0; every slot of an invalid
+ * point holds SPIRA_RAY_INVALID, 0 and 0.  out_count[i] (n_points): without SPIRA_NEAR_COUNT_ALL the number of slots filled (<= max_near); with the flag
+ * the number of ALL candidates of the point — the walk then prunes with best0 only; 0 for an invalid point.  With the flag max_near may be 0: the lists are
+ * then ignored and out_count is required; otherwise max_near is in 1 .. SPIRA_MAX_NEAR.  out_trips (n_points; optional, diagnostic, outside the bit-for-bit
+ * contract) as for closest point.  Each output may be NULL, but not all of out_prim, out_dist, out_point and out_count.
+ * Pruning: once K = max_near objects are known, the walk prunes with the K-th d2 instead of best0 (not under SPIRA_NEAR_COUNT_ALL).  That is exact: the
+ * safety argument of the closest-point walk holds for any bound in the place of the best distance; a candidate beyond the K-th d2 of the candidates known
+ * so far is not among the first K of all; the bound only shrinks, and a candidate AT the K-th d2 is still met and placed by its index.
+ * csrc/spira_knearest.h has the argument in full.
+ * flags: 0, SPIRA_CAST_INPLACE (one lane per point walking to the end, the comparison point), SPIRA_NEAR_COUNT_ALL, or both.  The order is total, so
+ * both organisations give identical bytes.
+ * Errors, all decided before any device is touched: a NULL point array, n_points == 0, unknown flag bits, max_near > SPIRA_MAX_NEAR, max_near == 0 without
+ * SPIRA_NEAR_COUNT_ALL, every output NULL (with max_near == 0: out_count NULL), a NULL or destroyed handle, one of the other precision or of another
+ * device: SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS, or n_points * max_near > SPIRA_MAX_RAYS (the product formed in 64 bits): SPIRA_E_LIMIT.  A handle
+ * made by spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The
+ * *_device_* form takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a query
+ * enqueued after a device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+#define SPIRA_MAX_NEAR        16u
+#define SPIRA_NEAR_COUNT_ALL  0x2u      /* beside SPIRA_CAST_INPLACE 0x1u */
+int spira_scene_nearest_k_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
+                              int *out_prim, float *out_dist, float *out_point, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_nearest_k_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
+                              int *out_prim, double *out_dist, double *out_point, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_nearest_k_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
+                                     int *d_out_prim, float *d_out_dist, float *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+int spira_scene_nearest_k_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
+                                     int *d_out_prim, double *d_out_dist, double *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+
 /* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
  * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
  * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.

@@ -48,6 +48,7 @@
 #include "spira_gather.h"
 #include "spira_nearest.h"
 #include "spira_hits.h"
+#include "spira_knearest.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -86,6 +87,8 @@ int nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_poin
                      bool on_device, void *user_stream);
 int hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count,
                   bool on_device, void *user_stream);
+int nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                       uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -1670,6 +1673,43 @@ int hits_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t ma
 }
 SPIRA_ENTRY(hits_entry, hits_impl)
 
+// ======================================================================= spira_scene_nearest_k_*: the max_near closest objects of every point, in order
+// Kernels, the list and the pruning argument: spira_knearest.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels
+// whose list capacity (1, 4 or 16) is the smallest that holds max_near.  The device form touches no workspace of the context (it allocates nothing); the
+// host form stages points and outputs.
+template <class T, int CAP>
+ListKernels<spira::KNearArgs<T>> knear_kernels() {
+    return {spira::k_knear_session<T, CAP>, spira::k_knear<T, true, false, CAP>, spira::k_knear<T, false, true, CAP>, spira::k_knear<T, false, false, CAP>, false};
+}
+template <class T>
+int nearest_k_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, T *out_dist, T *out_point,
+                   uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
+    using A = spira::KNearArgs<T>;
+    const char *msg = nullptr;
+    if (max_near == 0) { out_prim = nullptr; out_dist = nullptr; out_point = nullptr; }      // (count only: the lists have no slots)
+    if (int rc = spira::nearest_k_check(points4 != nullptr, n_points, max_near, flags, out_prim || out_dist || out_point || out_count, &msg)) return fail(rc, msg);
+    const ListKernels<A> kernels = max_near <= 1 ? knear_kernels<T, 1>() : max_near <= 4 ? knear_kernels<T, 4>() : knear_kernels<T, 16>();
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.max_near = max_near; a.count_all = (flags & SPIRA_NEAR_COUNT_ALL) ? 1u : 0u;
+    const size_t n = n_points, slots = n * max_near, prim_b = slots * sizeof(int);
+    // [points | dist | point | prim | pad | count | trips]: every block starts at a multiple of sizeof(T) or more (pad: a NULL block that rounds prim up to
+    // 8 bytes; count and trips hold 4-byte values)
+    StageBlock io[] = {{(void *)points4, 4 * n * sizeof(T), kStageIn}, {out_dist, slots * sizeof(T), kStageOut}, {out_point, 3 * slots * sizeof(T), kStageOut},
+                       {out_prim, prim_b, kStageOut}, {nullptr, prim_b & 4, 0}, {out_count, n * sizeof(uint32_t), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.count = (uint32_t *)io[5].dev;
+    a.trips = (uint32_t *)io[6].dev;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
+SPIRA_ENTRY(nearest_k_entry, nearest_k_impl)
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2865,6 +2905,10 @@ int spira_tu::hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n
                             bool on_device, void *user_stream) {
     return hits_impl<float>(h, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, on_device, user_stream);
 }
+int spira_tu::nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist,
+                                 float *out_point, uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
+    return nearest_k_impl<float>(h, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -2986,6 +3030,23 @@ int spira_scene_closest_point_device_f32(const spira_scene *scene, const float *
 int spira_scene_closest_point_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, double *d_out_dist,
                                          double *d_out_point, uint32_t *d_out_trips, void *stream) {
     return nearest_entry<double>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
+}
+// ---- K-nearest point queries (spira_knearest.h)
+int spira_scene_nearest_k_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist,
+                              float *out_point, uint32_t *out_count, uint32_t *out_trips) {
+    return nearest_k_entry<float>(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
+}
+int spira_scene_nearest_k_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, double *out_dist,
+                              double *out_point, uint32_t *out_count, uint32_t *out_trips) {
+    return nearest_k_entry<double>(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
+}
+int spira_scene_nearest_k_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *d_out_prim,
+                                     float *d_out_dist, float *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
+    return nearest_k_entry<float>(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
+}
+int spira_scene_nearest_k_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *d_out_prim,
+                                     double *d_out_dist, double *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
+    return nearest_k_entry<double>(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
 }
 // host arithmetic, no device: the triangle function the kernels and the scan call
 void spira_closest_point_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float p[3], float out_q[3], float *out_d2) {

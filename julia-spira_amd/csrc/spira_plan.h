@@ -407,6 +407,19 @@ inline int hits_check(bool rays, uint32_t n_rays, uint32_t max_hits, uint32_t fl
     if ((uint64_t)n_rays * max_hits > SPIRA_MAX_RAYS) { *msg = "n_rays * max_hits is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_nearest_k_*: closest point's rules, then the list's.  any_output: out_prim, out_dist, out_point or out_count is given — with max_near == 0
+// only out_count is one.
+inline int nearest_k_check(bool points, uint32_t n_points, uint32_t max_near, uint32_t flags, bool any_output, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~(SPIRA_CAST_INPLACE | SPIRA_NEAR_COUNT_ALL)) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE and SPIRA_NEAR_COUNT_ALL are the only ones)"; return SPIRA_E_INVALID; }
+    if (max_near > SPIRA_MAX_NEAR) { *msg = "max_near is above SPIRA_MAX_NEAR (16)"; return SPIRA_E_INVALID; }
+    if (max_near == 0 && !(flags & SPIRA_NEAR_COUNT_ALL)) { *msg = "max_near is 0 without SPIRA_NEAR_COUNT_ALL"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = max_near ? "out_prim, out_dist, out_point and out_count are all NULL" : "max_near is 0 and out_count is NULL: nothing to write"; return SPIRA_E_INVALID; }
+    if (n_points > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) points"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)n_points * max_near > SPIRA_MAX_RAYS) { *msg = "n_points * max_near is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
+    return 0;
+}
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

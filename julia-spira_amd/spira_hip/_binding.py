@@ -30,6 +30,9 @@ CAST_INPLACE = 0x1
 # ---- multi-hit ray queries (spira_scene_cast_hits_*) ----
 MAX_HITS = 16
 HITS_COUNT_ALL = 0x2
+# ---- K-nearest point queries (spira_scene_nearest_k_*) ----
+MAX_NEAR = 16
+NEAR_COUNT_ALL = 0x2
 # ---- camera models of the ray generator (spira_camera_rays_*) ----
 CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO = 0, 1, 2
 MAX_DEPTH, MAX_SPP = 255, 1 << 24
@@ -61,6 +64,7 @@ EXPORTS = [
     "spira_scene_closest_point_f32", "spira_scene_closest_point_f64", "spira_scene_closest_point_device_f32", "spira_scene_closest_point_device_f64",
     "spira_closest_point_triangle_f32", "spira_closest_point_triangle_f64",
     "spira_scene_cast_hits_f32", "spira_scene_cast_hits_f64", "spira_scene_cast_hits_device_f32", "spira_scene_cast_hits_device_f64",
+    "spira_scene_nearest_k_f32", "spira_scene_nearest_k_f64", "spira_scene_nearest_k_device_f32", "spira_scene_nearest_k_device_f64",
 ]
 
 
@@ -515,6 +519,39 @@ class Scene:
         fn = lib().spira_scene_closest_point_device_f32 if self.prec == "f32" else lib().spira_scene_closest_point_device_f64
         _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
                   C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+
+    def nearest_k(self, points4, max_near, inplace=False, count_all=False, want_prim=True, want_dist=True, want_point=True, want_count=True, want_trips=False):
+        """spira_scene_nearest_k_*: the max_near closest objects of every point of points4 (host array, as for closest_point), ordered by squared distance
+        ascending and, among equal ones, by object index descending.  Returns (prim int32 [n, K], dist [n, K], point [n, K, 3], count uint32 [n],
+        trips uint32 [n]), None where not wanted (with max_near = 0 the lists are None): unused slots hold RAY_MISS, the point's r_max and point 0, every
+        slot of an invalid point RAY_INVALID, 0 and 0.  count: the slots filled, or with count_all every object within r_max (the walk then prunes with
+        r_max only; max_near may be 0).  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        p = np.ascontiguousarray(points4, dtype=npdt)
+        if p.ndim != 2 or p.shape[1] != 4:
+            raise ValueError("points4: n_points x [px py pz r_max]")
+        n, k = len(p), int(max_near)
+        room = k if 0 < k <= MAX_NEAR else 1      # (a refused max_near: the entry says so)
+        prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
+        dist = np.empty((n, room), dtype=npdt) if want_dist and k else None
+        point = np.empty((n, room, 3), dtype=npdt) if want_point and k else None
+        count = np.empty(n, dtype=np.uint32) if want_count else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        fn = lib().spira_scene_nearest_k_f32 if self.prec == "f32" else lib().spira_scene_nearest_k_f64
+        flags = (CAST_INPLACE if inplace else 0) | (NEAR_COUNT_ALL if count_all else 0)
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(flags),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, count, trips)]))
+        return prim, dist, point, count, trips
+
+    def nearest_k_device(self, d_points_ptr, n_points, max_near, d_prim_ptr, d_dist_ptr, d_point_ptr, d_count_ptr, stream_ptr, inplace=False, count_all=False,
+                         d_trips_ptr=0):
+        """spira_scene_nearest_k_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        fn = lib().spira_scene_nearest_k_device_f32 if self.prec == "f32" else lib().spira_scene_nearest_k_device_f64
+        flags = (CAST_INPLACE if inplace else 0) | (NEAR_COUNT_ALL if count_all else 0)
+        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(max_near), C.c_uint32(flags), C.c_void_p(d_prim_ptr or None),
+                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(d_trips_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
 
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).

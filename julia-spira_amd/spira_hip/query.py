@@ -1,5 +1,6 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
-spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries.
+spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries and the
+K-nearest ones (k_nearest, count_within).
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
 s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s); t, t_min and t_max are distances along that unit direction."""
@@ -211,3 +212,45 @@ def closest_points(scene, points, inplace=False, want_point=True, want_trips=Fal
         scene.closest_point_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), q.data_ptr() if want_point else 0, st.cuda_stream,
                                    inplace=inplace, d_trips_ptr=trips.data_ptr() if want_trips else 0)
     return prim, dist, q, trips
+
+
+# ------------------------------------------------------------------ K-nearest point queries (spira_scene_nearest_k_*; csrc/spira_knearest.h)
+def k_nearest(scene, points, k, count_all=False, inplace=False, want_prim=True, want_dist=True, want_point=True, want_trips=False, stream=None):
+    """The k closest objects of every point ([px py pz r_max]), ordered by squared distance ascending and, among equal ones, by object index descending:
+    (prim int32 [n, K], dist [n, K], point [n, K, 3], count [n], trips [n]), None where not wanted.  points: a host array [n, 4] — the host form, numpy
+    arrays back — or a torch tensor on the scene's device in the scene's precision — spira_scene_nearest_k_device_*, enqueued on `stream` (a
+    torch.cuda.Stream; None: the current one), device tensors back without synchronising (count and trips as int32); `points` must stay alive until the
+    work has run.  count_all: count every object within r_max, not the slots filled."""
+    if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
+        return scene.nearest_k(points, k, inplace=inplace, count_all=count_all, want_prim=want_prim, want_dist=want_dist, want_point=want_point, want_trips=want_trips)
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise ValueError("k_nearest: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
+    n, k = points.shape[0], int(k)
+    room = k if 0 < k <= B.MAX_NEAR else 1
+    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    with torch.cuda.stream(st):
+        prim = torch.empty((n, room), dtype=torch.int32, device=points.device) if want_prim and k else None
+        dist = torch.empty((n, room), dtype=want, device=points.device) if want_dist and k else None
+        q = torch.empty((n, room, 3), dtype=want, device=points.device) if want_point and k else None
+        count = torch.empty(n, dtype=torch.int32, device=points.device)
+        trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
+        ptr = lambda t: t.data_ptr() if t is not None else 0
+        scene.nearest_k_device(points.data_ptr(), n, k, ptr(prim), ptr(dist), ptr(q), count.data_ptr(), st.cuda_stream, inplace=inplace, count_all=count_all,
+                               d_trips_ptr=ptr(trips))
+    return prim, dist, q, count, trips
+
+
+def count_within(scene, points, radius=None, inplace=False, stream=None):
+    """The number of objects within the radius of every point — max_near = 0 with NEAR_COUNT_ALL, no list is kept; 0 for an invalid point.  points: [n, 4]
+    with r_max in the fourth column, or [n, 3] with `radius` (a number or one per point) to go there.  Host array or device tensor, as k_nearest."""
+    if radius is not None:
+        if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
+            p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+            points = np.concatenate([p, np.broadcast_to(np.asarray(radius, dtype=np.float64), (len(p),)).reshape(-1, 1)], axis=1)
+        else:
+            import torch
+            r = torch.as_tensor(radius, dtype=points.dtype, device=points.device).expand(points.shape[0]).reshape(-1, 1)
+            points = torch.cat([points[:, :3], r], dim=1).contiguous()
+    return k_nearest(scene, points, 0, count_all=True, inplace=inplace, stream=stream)[3]
