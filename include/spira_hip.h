@@ -478,6 +478,48 @@ int spira_scene_nearest_k_device_f32(const spira_scene *scene, const float *d_po
 int spira_scene_nearest_k_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
                                      int *d_out_prim, double *d_out_dist, double *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
 
+/* ---- sphere sweeps on a scene handle: the first contact of a moving ball (character motion, projectile CCD, camera collision, clearance checks) ----
+ * "A ball of radius r moves from o along d: when and where does it first touch the scene?"  rays8 is exactly cast's list, n x [ox oy oz t_min dx dy dz
+ * t_max]; the library normalises d; t, t_min and t_max are distances of the ball's CENTRE along the unit direction, c(t) = o + d t.  radii holds n values,
+ * one per sweep.  The surface is the object: a sphere is a shell, as for the closest-point queries.
+ * Contract (csrc/spira_sweep.h states every formula in its written order and is the authority; all arithmetic in T, nothing fused): with r2 = r r,
+ * rs = r + r 2^-10, rs2 = rs rs, object k — spheres [0..) then triangles [0..) in the caller's order — yields at most one t_k.  If the squared distance from
+ * c(t_min) to the object (the closest-point function of the entries above) is <= r2, the sweep starts in overlap: t_k = t_min — a sweep with t_min = 0 is
+ * blocked at its start exactly where the K-nearest count within r of o is above 0.  Otherwise closed-form roots of "distance = r" (a triangle: its face
+ * plane offset toward the start, the three edge cylinders, the three vertex spheres; a sphere: radius R + r from outside, R - r from inside) are PROPOSALS,
+ * and the smallest proposal t >= t_min whose closest-point evaluation at c(t) gives d2 <= rs2 is t_k; q_k is that evaluation's point.  Object k is a
+ * candidate when !(t_k < t_min || t_k > closest), closest starting at t_max; the minimal t wins and ties go to the LATER object.
+ * Outputs, caller-owned: out_prim (the object index), out_t = t_k, out_point = q_k (n x 3: the contact point on the surface), out_normal (n x 3) =
+ * (c(t_k) - q_k) / sqrt(d2), or -d where that length is below the smallest normal number; out_trips (optional, diagnostic, outside the bit-for-bit
+ * contract) as for closest point.  A miss: prim SPIRA_RAY_MISS, t = the ray's t_max copied, point 0, normal 0.  An INVALID sweep — prim
+ * SPIRA_RAY_INVALID, t 0, point 0, normal 0; blocked 255 — never faults and never disturbs its neighbours: the ray is invalid by cast's rule (the origin
+ * rule included), or r is NaN, infinite or negative, or — scenes with a tree only — rs * scale > 64 in T (scale: the tree's frame, as in the origin rule).
+ * spira_scene_sweep_blocked_*: out_hit[i] is 1 exactly where the sweep gives prim >= 0, else 0; its kernels stop at the first candidate.
+ * spira_sweep_sphere_triangle_* is the leaf function as host arithmetic (no device): d_unit must be of unit length; out_hit = the triangle is a candidate
+ * at closest = t_max, out_t = t_k (else t_max copied), out_q = q_k (else 0); each output may be NULL.
+ * flags: 0, or SPIRA_CAST_INPLACE (one lane per sweep walking to the end, the comparison point); both organisations give identical bytes.
+ * Errors, all decided before any device is touched: a NULL ray or radius array, n == 0, unknown flag bits, every output NULL (out_trips alone is no
+ * output), a NULL or destroyed handle, one of the other precision or of another device: SPIRA_E_INVALID; n > SPIRA_MAX_RAYS: SPIRA_E_LIMIT.  A handle made
+ * by spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The *_device_*
+ * form takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a sweep enqueued
+ * after a device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+int spira_scene_sweep_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags,
+                          int *out_prim, float *out_t, float *out_point, float *out_normal, uint32_t *out_trips);
+int spira_scene_sweep_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags,
+                          int *out_prim, double *out_t, double *out_point, double *out_normal, uint32_t *out_trips);
+int spira_scene_sweep_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags,
+                                 int *d_out_prim, float *d_out_t, float *d_out_point, float *d_out_normal, uint32_t *d_out_trips, void *stream);
+int spira_scene_sweep_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags,
+                                 int *d_out_prim, double *d_out_t, double *d_out_point, double *d_out_normal, uint32_t *d_out_trips, void *stream);
+int spira_scene_sweep_blocked_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_sweep_blocked_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_sweep_blocked_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+int spira_scene_sweep_blocked_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+void spira_sweep_sphere_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d_unit[3], float r, float t_min, float t_max,
+                                     float *out_t, float out_q[3], int *out_hit);
+void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double o[3], const double d_unit[3], double r, double t_min, double t_max,
+                                     double *out_t, double out_q[3], int *out_hit);
+
 /* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
  * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
  * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.

@@ -49,6 +49,7 @@
 #include "spira_nearest.h"
 #include "spira_hits.h"
 #include "spira_knearest.h"
+#include "spira_sweep.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -89,6 +90,8 @@ int hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uin
                   bool on_device, void *user_stream);
 int nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
                        uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream);
+int sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point, float *out_normal,
+                   uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -1710,6 +1713,36 @@ int nearest_k_impl(const spira_scene *h, const T *points4, uint32_t n_points, ui
 }
 SPIRA_ENTRY(nearest_k_entry, nearest_k_impl)
 
+// ======================================================================= spira_scene_sweep_* / spira_scene_sweep_blocked_*: the first contact of a moving ball
+// Kernels, the contract and the margin argument: spira_sweep.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch.  The device form
+// touches no workspace of the context (it allocates nothing); the host form stages rays, radii and outputs.
+template <class T>
+int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_sweeps, uint32_t flags, int *out_prim, T *out_t, T *out_point, T *out_normal,
+               uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+    using A = spira::SweepArgs<T>;
+    const ListKernels<A> first = {spira::k_sweep_session<T, false>, spira::k_sweep<T, true, false, false>, spira::k_sweep<T, false, true, false>, spira::k_sweep<T, false, false, false>, false};
+    const ListKernels<A> blocked = {spira::k_sweep_session<T, true>, spira::k_sweep<T, true, false, true>, spira::k_sweep<T, false, true, true>, spira::k_sweep<T, false, false, true>, false};
+    const char *msg = nullptr;
+    if (int rc = spira::sweep_check(rays8 != nullptr, radii != nullptr, n_sweeps, flags, any ? out_hit != nullptr : (out_prim || out_t || out_point || out_normal), &msg)) return fail(rc, msg);
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_sweeps, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n = n_sweeps; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_sweeps, t_b = n * sizeof(T);
+    // [rays | radii | t | point | normal | prim | trips | hit]: every block starts at a multiple of sizeof(T) or more, the 4-byte ones of 4
+    StageBlock io[] = {{(void *)rays8, 8 * t_b, kStageIn}, {(void *)radii, t_b, kStageIn}, {out_t, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_normal, 3 * t_b, kStageOut},
+                       {out_prim, n * sizeof(int), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}, {out_hit, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.rays = (const T *)io[0].dev; a.radii = (const T *)io[1].dev; a.t = (T *)io[2].dev; a.point = (T *)io[3].dev; a.normal = (T *)io[4].dev; a.prim = (int *)io[5].dev;
+    a.trips = (uint32_t *)io[6].dev; a.hit = (uint8_t *)io[7].dev;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(any ? blocked : first, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
+SPIRA_ENTRY(sweep_entry, sweep_impl)
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2909,6 +2942,10 @@ int spira_tu::nearest_k_impl_f32(const spira_scene *h, const float *points4, uin
                                  float *out_point, uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
     return nearest_k_impl<float>(h, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, on_device, user_stream);
 }
+int spira_tu::sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point,
+                             float *out_normal, uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+    return sweep_impl<float>(h, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, out_hit, out_trips, any, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -3060,6 +3097,54 @@ void spira_closest_point_triangle_f64(const double v0[3], const double e1[3], co
     spira::closest_point_triangle<double>(v0, e1, e2, p, q, d2);
     if (out_q) { out_q[0] = q[0]; out_q[1] = q[1]; out_q[2] = q[2]; }
     if (out_d2) *out_d2 = d2;
+}
+
+// ---- sphere sweeps on a scene handle (spira_sweep.h)
+int spira_scene_sweep_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point,
+                          float *out_normal, uint32_t *out_trips) {
+    return sweep_entry<float>(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_sweep_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags, int *d_out_prim, float *d_out_t,
+                                 float *d_out_point, float *d_out_normal, uint32_t *d_out_trips, void *stream) {
+    return sweep_entry<float>(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_sweep_blocked_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return sweep_entry<float>(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_sweep_blocked_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return sweep_entry<float>(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+// host arithmetic, no device: the leaf function the kernels and the scan call, with bound = t_max.  A miss: t = t_max copied, q 0.
+void spira_sweep_sphere_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d_unit[3], float r, float t_min, float t_max,
+                                     float *out_t, float out_q[3], int *out_hit) {
+    float t, q[3] = {0, 0, 0};
+    const bool hit = spira::sweep_sphere_triangle<float>(v0, e1, e2, o, d_unit, r, t_min, t_max, t, q);
+    if (out_t) *out_t = hit ? t : t_max;
+    if (out_q) { out_q[0] = hit ? q[0] : 0; out_q[1] = hit ? q[1] : 0; out_q[2] = hit ? q[2] : 0; }
+    if (out_hit) *out_hit = hit ? 1 : 0;
+}
+int spira_scene_sweep_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags, int *out_prim, double *out_t, double *out_point,
+                          double *out_normal, uint32_t *out_trips) {
+    return sweep_entry<double>(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_sweep_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags, int *d_out_prim, double *d_out_t,
+                                 double *d_out_point, double *d_out_normal, uint32_t *d_out_trips, void *stream) {
+    return sweep_entry<double>(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_sweep_blocked_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return sweep_entry<double>(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_sweep_blocked_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return sweep_entry<double>(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+// host arithmetic, no device: the leaf function the kernels and the scan call, with bound = t_max.  A miss: t = t_max copied, q 0.
+void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double o[3], const double d_unit[3], double r, double t_min, double t_max,
+                                     double *out_t, double out_q[3], int *out_hit) {
+    double t, q[3] = {0, 0, 0};
+    const bool hit = spira::sweep_sphere_triangle<double>(v0, e1, e2, o, d_unit, r, t_min, t_max, t, q);
+    if (out_t) *out_t = hit ? t : t_max;
+    if (out_q) { out_q[0] = hit ? q[0] : 0; out_q[1] = hit ? q[1] : 0; out_q[2] = hit ? q[2] : 0; }
+    if (out_hit) *out_hit = hit ? 1 : 0;
 }
 
 // ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)

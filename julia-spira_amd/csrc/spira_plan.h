@@ -420,6 +420,17 @@ inline int nearest_k_check(bool points, uint32_t n_points, uint32_t max_near, ui
     if ((uint64_t)n_points * max_near > SPIRA_MAX_RAYS) { *msg = "n_points * max_near is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_sweep_* / spira_scene_sweep_blocked_*: cast_check's rules for a ray list with one radius per ray.  any_output: out_prim, out_t, out_point or
+// out_normal is given (blocked: out_hit); out_trips alone is no output.
+inline int sweep_check(bool rays, bool radii, uint32_t n, uint32_t flags, bool any_output, const char **msg) {
+    if (!rays) { *msg = "the ray array is NULL"; return SPIRA_E_INVALID; }
+    if (!radii) { *msg = "the radius array is NULL"; return SPIRA_E_INVALID; }
+    if (n == 0) { *msg = "n is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = "every output is NULL"; return SPIRA_E_INVALID; }
+    if (n > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) sweeps"; return SPIRA_E_LIMIT; }
+    return 0;
+}
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

@@ -65,6 +65,9 @@ EXPORTS = [
     "spira_closest_point_triangle_f32", "spira_closest_point_triangle_f64",
     "spira_scene_cast_hits_f32", "spira_scene_cast_hits_f64", "spira_scene_cast_hits_device_f32", "spira_scene_cast_hits_device_f64",
     "spira_scene_nearest_k_f32", "spira_scene_nearest_k_f64", "spira_scene_nearest_k_device_f32", "spira_scene_nearest_k_device_f64",
+    "spira_scene_sweep_f32", "spira_scene_sweep_f64", "spira_scene_sweep_device_f32", "spira_scene_sweep_device_f64",
+    "spira_scene_sweep_blocked_f32", "spira_scene_sweep_blocked_f64", "spira_scene_sweep_blocked_device_f32", "spira_scene_sweep_blocked_device_f64",
+    "spira_sweep_sphere_triangle_f32", "spira_sweep_sphere_triangle_f64",
 ]
 
 
@@ -553,6 +556,54 @@ class Scene:
                   C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(d_trips_ptr or None),
                   C.c_void_p(stream_ptr or None)))
 
+    def _sweeps(self, rays8, radii):
+        npdt, _ = _dt(self.prec)
+        r = self._rays(rays8)
+        rad = np.ascontiguousarray(radii, dtype=npdt)
+        if rad.ndim != 1 or len(rad) != len(r):
+            raise ValueError("radii: one radius per ray")
+        return r, rad
+
+    def sweep(self, rays8, radii, inplace=False, want_prim=True, want_t=True, want_point=True, want_normal=True, want_trips=False):
+        """spira_scene_sweep_*: the first contact of a ball of radius radii[i] whose centre moves along rays8[i] (host arrays; the rays as for cast).
+        Returns (prim int32 [n], t [n], point [n, 3], normal [n, 3], trips uint32 [n]), None where not wanted: prim is the object index (spheres first),
+        RAY_MISS (t = the ray's t_max, point 0, normal 0) or RAY_INVALID (all 0); t is the distance of the ball's centre along the unit direction, point the
+        contact on the surface, normal the unit vector from it to the centre.  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        r, rad = self._sweeps(rays8, radii)
+        n = len(r)
+        prim = np.empty(n, dtype=np.int32) if want_prim else None
+        t = np.empty(n, dtype=npdt) if want_t else None
+        point = np.empty((n, 3), dtype=npdt) if want_point else None
+        nrm = np.empty((n, 3), dtype=npdt) if want_normal else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        fn = lib().spira_scene_sweep_f32 if self.prec == "f32" else lib().spira_scene_sweep_f64
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, point, nrm, trips)]))
+        return prim, t, point, nrm, trips
+
+    def sweep_blocked(self, rays8, radii, inplace=False):
+        """spira_scene_sweep_blocked_*: uint8 [n] — 1 where the ball touches anything within [t_min, t_max], 0 where not, 255 for an invalid sweep."""
+        r, rad = self._sweeps(rays8, radii)
+        hit = np.empty(len(r), dtype=np.uint8)
+        fn = lib().spira_scene_sweep_blocked_f32 if self.prec == "f32" else lib().spira_scene_sweep_blocked_f64
+        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  hit.ctypes.data_as(C.c_void_p)))
+        return hit
+
+    def sweep_device(self, d_rays_ptr, d_radii_ptr, n, d_prim_ptr, d_t_ptr, d_point_ptr, d_normal_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
+        """spira_scene_sweep_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or allocated."""
+        fn = lib().spira_scene_sweep_device_f32 if self.prec == "f32" else lib().spira_scene_sweep_device_f64
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_void_p(d_radii_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  C.c_void_p(d_prim_ptr or None), C.c_void_p(d_t_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_normal_ptr or None),
+                  C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+
+    def sweep_blocked_device(self, d_rays_ptr, d_radii_ptr, n, d_hit_ptr, stream_ptr, inplace=False):
+        """spira_scene_sweep_blocked_device_*: DEVICE addresses, asynchronous on the stream."""
+        fn = lib().spira_scene_sweep_blocked_device_f32 if self.prec == "f32" else lib().spira_scene_sweep_blocked_device_f64
+        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_void_p(d_radii_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  C.c_void_p(d_hit_ptr or None), C.c_void_p(stream_ptr or None)))
+
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).
         Ray k, sample s is the renderer's path at pixel key key0 + k.  ADDS samples sample0 .. sample0 + spp - 1, in order, to sums ([n, 3], in place; None: a
@@ -857,3 +908,17 @@ def closest_point_triangle(v0, e1, e2, p, prec):
     fn.restype = None
     fn(*[x.ctypes.data_as(C.c_void_p) for x in a], q.ctypes.data_as(C.c_void_p), d2.ctypes.data_as(C.c_void_p))
     return q, d2[0]
+
+
+def sweep_sphere_triangle(v0, e1, e2, o, d_unit, r, t_min, t_max, prec):
+    """spira_sweep_sphere_triangle_*: the library's leaf function of the sphere sweeps on one triangle (v0, e1 = v1 - v0, e2 = v2 - v0) and one sweep
+    (origin o, UNIT direction, radius r, t_min, t_max), as host arithmetic (no device needed).  Returns (t, q [3], hit) in the precision's dtype."""
+    npdt, ct = _dt(prec)
+    a = [np.ascontiguousarray(x, dtype=npdt).reshape(3) for x in (v0, e1, e2, o, d_unit)]
+    t, q, hit = np.empty(1, dtype=npdt), np.empty(3, dtype=npdt), C.c_int(0)
+    fn = lib().spira_sweep_sphere_triangle_f32 if prec == "f32" else lib().spira_sweep_sphere_triangle_f64
+    fn.restype = None
+    fn.argtypes = [C.c_void_p] * 5 + [ct] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p]
+    fn(*[x.ctypes.data_as(C.c_void_p) for x in a], ct(npdt(r)), ct(npdt(t_min)), ct(npdt(t_max)), t.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+       C.cast(C.byref(hit), C.c_void_p))
+    return t[0], q, bool(hit.value)

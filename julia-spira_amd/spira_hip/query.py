@@ -1,6 +1,6 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
 spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries and the
-K-nearest ones (k_nearest, count_within).
+K-nearest ones (k_nearest, count_within); the sphere sweeps (sweep_spheres, sweep_segments) with the numpy twins of csrc/spira_sweep.h.
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
 s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s); t, t_min and t_max are distances along that unit direction."""
@@ -254,3 +254,178 @@ def count_within(scene, points, radius=None, inplace=False, stream=None):
             r = torch.as_tensor(radius, dtype=points.dtype, device=points.device).expand(points.shape[0]).reshape(-1, 1)
             points = torch.cat([points[:, :3], r], dim=1).contiguous()
     return k_nearest(scene, points, 0, count_all=True, inplace=inplace, stream=stream)[3]
+
+
+# ------------------------------------------------------------------ sphere sweeps (spira_scene_sweep_*; csrc/spira_sweep.h)
+SWEEP_RADIUS_BOUND = 64      # scenes with a tree: rs * scale <= 64, rs = r + r * 2^-10
+
+
+def prepare_sweeps(rays8, radii, dtype, frame=None):
+    """The validity rule of spira_sweep.h (sweep_prepare), bit for bit: returns (rays, radii, valid) — `rays` as normalize_rays gives them (unit directions
+    where the RAY is valid), `radii` in `dtype`, `valid` the library's verdict per sweep: the ray valid by cast's rule, r not NaN, finite and >= 0, and —
+    with a frame (centre[3], scale) — rs * scale <= 64."""
+    T = np.dtype(dtype).type
+    r, valid = normalize_rays(rays8, T, frame)
+    rad = np.array(radii, dtype=T, copy=True).reshape(-1)
+    if len(rad) != len(r):
+        raise ValueError("prepare_sweeps: one radius per ray is needed")
+    with np.errstate(all="ignore"):
+        valid = valid & ~np.isnan(rad) & np.isfinite(rad) & ~(rad < T(0))
+        if frame is not None:
+            rs = rad + rad * T(2.0 ** -10)
+            valid &= (rs * T(frame[1])) <= T(SWEEP_RADIUS_BOUND)
+    return r, rad, valid
+
+
+def _sweep_radii(r, T):
+    r2 = r * r
+    rs = r + r * T(2.0 ** -10)
+    return r2, rs * rs
+
+
+def _sweep_foot(a, o, d):
+    t_b = _dot3(d, a - o)
+    return t_b, (o + d * t_b[..., None]) - a
+
+
+def _sweep_root_point(m, d, rr, far_root=False):
+    md, mm = _dot3(m, d), _dot3(m, m)
+    s = np.sqrt(md * md - (mm - rr))
+    return (-md) + s if far_root else (-md) - s
+
+
+def _sweep_root_edge(m, e, d, r2, T):
+    ee, de, me, md, mm = _dot3(e, e), _dot3(d, e), _dot3(m, e), _dot3(m, d), _dot3(m, m)
+    qa, qb, qc = ee - de * de, ee * md - de * me, ee * (mm - r2) - me * me
+    tau = ((-qb) - np.sqrt(qb * qb - qa * qc)) / qa
+    f = (me + de * tau) / ee
+    return np.where((f >= T(0)) & (f <= T(1)), tau, T(np.nan))
+
+
+def _sweep_decide(closest_point, o, d, t_min, t_max, r2, rs2, q0, d20, tp, T):
+    """Steps 1, 3 and the candidate rule at closest = t_max for proposals tp [..., P]: every proposal within [t_min, t_max] of an object that does not
+    start in overlap is evaluated (closest_point(sel, pc): the object's function for the objects at index tuple sel, at the points pc), the smallest
+    verified one is t_k.  A proposal beyond t_max is no candidate verified or not, so leaving it out changes no output."""
+    start = d20 <= r2
+    ok = (tp >= t_min[..., None]) & ~(tp > t_max[..., None]) & ~start[..., None]      # NaN: never
+    at = np.nonzero(ok)
+    sel = at[:-1]
+    qc, dc = closest_point(sel, o[sel] + d[sel] * tp[at][:, None])
+    qv, dv = np.zeros(tp.shape + (3,), dtype=tp.dtype), np.full(tp.shape, np.inf, dtype=tp.dtype)
+    qv[at], dv[at] = qc, dc
+    ok &= dv <= rs2[..., None]
+    key = np.where(ok, tp, T(np.inf))
+    j = np.argmin(key, axis=-1)                                      # the first of the smallest: equal proposals evaluate the same point
+    tk = np.take_along_axis(key, j[..., None], axis=-1)[..., 0]
+    qk = np.take_along_axis(qv, j[..., None, None], axis=-2)[..., 0, :]
+    found = start | ok.any(axis=-1)
+    tk = np.where(start, t_min, tk)
+    qk = np.where(start[..., None], q0, qk)
+    hit = found & ~((tk < t_min) | (tk > t_max))
+    return np.where(hit, tk, t_max), np.where(hit[..., None], qk, T(0)), hit
+
+
+def sweep_sphere_triangle(v0, e1, e2, o, d, r, t_min, t_max):
+    """The numpy twin of spira::sweep_sphere_triangle with bound = t_max: v0, e1, e2, o, d (unit) are arrays [..., 3] and r, t_min, t_max arrays [...] of ONE
+    dtype that broadcast against each other.  Every branch is evaluated — the start overlap, the seven proposals, a verification of each — and np.where
+    selects; the same operations in the same order on the same values as the header.  Returns (t [...], q [..., 3], hit [...]): t = t_k and q = q_k where
+    the triangle is a candidate at closest = t_max, else t_max and 0."""
+    v0, e1, e2, o, d, r, t_min, t_max = np.broadcast_arrays(*[np.asarray(x) for x in (v0, e1, e2, o, d)] + [np.asarray(x)[..., None] for x in (r, t_min, t_max)])
+    single = o.ndim == 1                                             # one sweep against one triangle: a leading axis for the gather below
+    if single:
+        v0, e1, e2, o, d, r, t_min, t_max = (x[None] for x in (v0, e1, e2, o, d, r, t_min, t_max))
+    r, t_min, t_max = r[..., 0], t_min[..., 0], t_max[..., 0]
+    T = o.dtype.type
+    with np.errstate(all="ignore"):
+        r2, rs2 = _sweep_radii(r, T)
+        p0 = o + d * t_min[..., None]
+        q0, d20 = closest_point_triangle(v0, e1, e2, p0)
+        t_b, w = _sweep_foot(v0, o, d)
+        n = np.stack([e1[..., 1] * e2[..., 2] - e1[..., 2] * e2[..., 1], e1[..., 2] * e2[..., 0] - e1[..., 0] * e2[..., 2],
+                      e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]], axis=-1)
+        nl = np.sqrt(_dot3(n, n))
+        s0, nd, nw = _dot3(n, p0 - v0), _dot3(n, d), _dot3(n, w)
+        off = r * nl
+        off = np.where(s0 < T(0), -off, off)
+        tau = (off - nw) / nd
+        g = w + d * tau[..., None]
+        p1, p2, a11, a12, a22 = _dot3(e1, g), _dot3(e2, g), _dot3(e1, e1), _dot3(e1, e2), _dot3(e2, e2)
+        bv, bw, det = a22 * p1 - a12 * p2, a11 * p2 - a12 * p1, a11 * a22 - a12 * a12
+        t_face = np.where((nd == nd) & (nd != T(0)) & (bv >= T(0)) & (bw >= T(0)) & (bv + bw <= det), t_b + tau, T(np.nan))
+        w1, w2, e3 = w - e1, w - e2, e2 - e1
+        tp = np.stack([t_face, t_b + _sweep_root_edge(w, e1, d, r2, T), t_b + _sweep_root_edge(w, e2, d, r2, T), t_b + _sweep_root_edge(w1, e3, d, r2, T),
+                       t_b + _sweep_root_point(w, d, r2), t_b + _sweep_root_point(w1, d, r2), t_b + _sweep_root_point(w2, d, r2)], axis=-1)
+        cp = lambda sel, pc: closest_point_triangle(v0[sel], e1[sel], e2[sel], pc)
+        t, q, hit = _sweep_decide(cp, o, d, t_min, t_max, r2, rs2, q0, d20, tp, T)
+    return (t[0], q[0], hit[0]) if single else (t, q, hit)
+
+
+def sweep_sphere_sphere(c, radius, o, d, r, t_min, t_max):
+    """The numpy twin of spira::sweep_sphere_sphere with bound = t_max (the shell of the sphere c [..., 3], radius [...]); arguments and results as
+    sweep_sphere_triangle."""
+    c, o, d, radius, r, t_min, t_max = np.broadcast_arrays(*[np.asarray(x) for x in (c, o, d)] + [np.asarray(x)[..., None] for x in (radius, r, t_min, t_max)])
+    single = o.ndim == 1
+    if single:
+        c, o, d, radius, r, t_min, t_max = (x[None] for x in (c, o, d, radius, r, t_min, t_max))
+    radius, r, t_min, t_max = radius[..., 0], r[..., 0], t_min[..., 0], t_max[..., 0]
+    T = o.dtype.type
+    with np.errstate(all="ignore"):
+        r2, rs2 = _sweep_radii(r, T)
+        p0 = o + d * t_min[..., None]
+        q0, d20 = closest_point_sphere(c, radius, p0)
+        t_b, w = _sweep_foot(c, o, d)
+        rp, rm = radius + r, radius - r
+        tp = np.stack([t_b + _sweep_root_point(w, d, rp * rp), np.where(radius > r, t_b + _sweep_root_point(w, d, rm * rm, far_root=True), T(np.nan))], axis=-1)
+        cp = lambda sel, pc: closest_point_sphere(c[sel], radius[sel], pc)
+        t, q, hit = _sweep_decide(cp, o, d, t_min, t_max, r2, rs2, q0, d20, tp, T)
+    return (t[0], q[0], hit[0]) if single else (t, q, hit)
+
+
+def sweep_spheres(scene, rays, radii, blocked=False, inplace=False, want_point=True, want_normal=True, want_trips=False, stream=None):
+    """spira_scene_sweep_* (blocked: spira_scene_sweep_blocked_*): the first contact of a ball of radius radii[i] whose centre moves along rays[i]
+    ([ox oy oz t_min dx dy dz t_max], as for cast).  Returns (prim int32 [n], t [n], point [n, 3], normal [n, 3], trips [n]), None where not wanted, or for
+    blocked the uint8 [n] verdicts (1 blocked, 0 free, 255 invalid).  rays, radii: host arrays — the host form, numpy arrays back — or torch tensors on the
+    scene's device in the scene's precision — the device form, enqueued on `stream` (a torch.cuda.Stream; None: the current one), device tensors back
+    without synchronising (trips as int32); the inputs must stay alive until the work has run."""
+    if isinstance(rays, np.ndarray) or not hasattr(rays, "is_cuda"):
+        if blocked:
+            return scene.sweep_blocked(rays, radii, inplace=inplace)
+        return scene.sweep(rays, radii, inplace=inplace, want_point=want_point, want_normal=want_normal, want_trips=want_trips)
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if rays.dtype != want or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+        raise ValueError("sweep_spheres: a contiguous device tensor of n x 8 %s values is needed" % scene.prec)
+    n = rays.shape[0]
+    if radii.dtype != want or not radii.is_cuda or radii.dim() != 1 or radii.shape[0] != n or not radii.is_contiguous():
+        raise ValueError("sweep_spheres: radii must be a contiguous device tensor of n %s values" % scene.prec)
+    st = stream if stream is not None else torch.cuda.current_stream(rays.device)
+    with torch.cuda.stream(st):
+        if blocked:
+            hit = torch.empty(n, dtype=torch.uint8, device=rays.device)
+            scene.sweep_blocked_device(rays.data_ptr(), radii.data_ptr(), n, hit.data_ptr(), st.cuda_stream, inplace=inplace)
+            return hit
+        prim = torch.empty(n, dtype=torch.int32, device=rays.device)
+        t = torch.empty(n, dtype=want, device=rays.device)
+        point = torch.empty((n, 3), dtype=want, device=rays.device) if want_point else None
+        nrm = torch.empty((n, 3), dtype=want, device=rays.device) if want_normal else None
+        trips = torch.empty(n, dtype=torch.int32, device=rays.device) if want_trips else None
+        ptr = lambda x: x.data_ptr() if x is not None else 0
+        scene.sweep_device(rays.data_ptr(), radii.data_ptr(), n, prim.data_ptr(), t.data_ptr(), ptr(point), ptr(nrm), st.cuda_stream, inplace=inplace,
+                           d_trips_ptr=ptr(trips))
+    return prim, t, point, nrm, trips
+
+
+def sweep_segments(scene, a, b, radius):
+    """A ball of `radius` (a number or one per segment) moved from a[i] to b[i] (host arrays [n, 3]): rays with t_min 0 and t_max = |b - a|.  Returns
+    (prim int32 [n], the fraction of the segment travelled at the first contact — 1 for a free segment, 0 for one the library calls invalid, such as
+    a == b — and the contact point [n, 3])."""
+    a, b = np.asarray(a, dtype=np.float64).reshape(-1, 3), np.asarray(b, dtype=np.float64).reshape(-1, 3)
+    T = np.float32 if scene.prec == "f32" else np.float64
+    d = b - a
+    length = np.sqrt((d * d).sum(axis=1))
+    rays = np.concatenate([a, np.zeros((len(a), 1)), d, length[:, None]], axis=1).astype(T)
+    rad = np.broadcast_to(np.asarray(radius, dtype=np.float64), (len(a),)).astype(T)
+    prim, t, point, _, _ = scene.sweep(rays, rad, want_normal=False)
+    with np.errstate(all="ignore"):
+        frac = np.where(prim == B.RAY_INVALID, T(0), t / rays[:, 7])
+    return prim, frac, point
