@@ -520,6 +520,54 @@ void spira_sweep_sphere_triangle_f32(const float v0[3], const float e1[3], const
 void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double o[3], const double d_unit[3], double r, double t_min, double t_max,
                                      double *out_t, double out_q[3], int *out_hit);
 
+/* ---- box overlap queries on a scene handle: which objects touch an oriented box (voxelisation, region selection and trigger volumes, contact
+ *      broadphase, culling a mesh against a cell) ----
+ * boxes10 is n x [cx cy cz hx hy hz qx qy qz qw]: centre, half extents, and a rotation quaternion the library normalises as it normalises ray directions.
+ * Contract (csrc/spira_overlap.h states every formula in its written order and is the authority; all arithmetic in T, nothing fused): with
+ * n2 = (qx qx + qy qy) + (qz qz + qw qw) and (x, y, z, w) = q / sqrt(n2) the box axes are A0 = (1 - 2 (yy + zz), 2 (xy + zw), 2 (xz - yw)),
+ * A1 = (2 (xy - zw), 1 - 2 (xx + zz), 2 (yz + xw)), A2 = (2 (xz + yw), 2 (yz - xw), 1 - 2 (xx + yy)); a world vector a has the box-frame coordinates
+ * (dot(A0, a), dot(A1, a), dot(A2, a)); the identity quaternion gives the unit axes exactly.  A TRIANGLE is a candidate when all 13 axes of the
+ * separating-axis test overlap (the three box axes, the face normal, the nine cross(unit_i, edge_j)), evaluated on the record's own v0, e1, e2 taken to
+ * the box frame; an axis with projections p0, p1, p2 and radius rad overlaps when min(p) <= rad && max(p) >= -rad — closed, touching counts; a NaN in
+ * any projection makes the object no candidate, and so does a computed face normal of exactly (0, 0, 0) (a triangle of zero area, which the point
+ * queries never pick either).  A SPHERE is a shell, as for the point queries: with p the box-frame coordinates of its centre less the
+ * box's, dmin2 = sum max(|p_k| - h_k, 0)^2 and dmax2 = sum (|p_k| + h_k)^2, it is a candidate when dmin2 <= R R && dmax2 >= R R.
+ * Outputs, caller-owned: out_count[i] (n) is the number of ALL candidates of box i — spheres [0..) then triangles [0..) in the caller's order; out_prim
+ * (n x max_list) holds the first max_list candidates in ASCENDING object index, unused slots SPIRA_RAY_MISS; every slot of an INVALID box holds
+ * SPIRA_RAY_INVALID and its count is 0.  max_list is in 0 .. SPIRA_MAX_OVERLAP; 0 counts only, and out_count is then required.  Index order carries no
+ * spatial bound, so the walk never prunes with the list and the count is always complete (there is no count flag).  out_trips (n; optional, diagnostic,
+ * outside the bit-for-bit contract) as for closest point.  Each of out_prim and out_count may be NULL, not both.
+ * spira_scene_overlap_any_*: out_hit[i] is 1 exactly where the count is above 0, else 0, 255 for an invalid box; its kernels leave at the first candidate.
+ * A box is INVALID — it never faults and never disturbs its neighbours — when any of its ten values is NaN or infinite, some h_k < 0, n2 is not finite or
+ * below the smallest normal number of T, or — scenes with a tree only — the origin rule of the ray queries fails for its centre, or He_k * scale > 64 on
+ * some axis, He_k = (|A0_k| h0 + |A1_k| h1) + |A2_k| h2 being the enclosing axis-aligned half extent.  h = 0 is valid: a point, a segment, a rectangle.
+ * spira_overlap_box_triangle_* / spira_overlap_box_sphere_* are the leaf functions as host arithmetic (no device): 1, 0, or SPIRA_RAY_INVALID for a box
+ * that is invalid without a frame.
+ * flags: 0, or SPIRA_CAST_INPLACE (one lane per box walking to the end, the comparison point); both organisations give identical bytes.
+ * Errors, all decided before any device is touched: a NULL box array, n == 0, unknown flag bits, max_list > SPIRA_MAX_OVERLAP, every output NULL (with
+ * max_list == 0: out_count NULL; out_trips alone is no output), a NULL or destroyed handle, one of the other precision or of another device:
+ * SPIRA_E_INVALID; n > SPIRA_MAX_RAYS, or n * max_list > SPIRA_MAX_RAYS (the product formed in 64 bits): SPIRA_E_LIMIT.  A handle made by
+ * spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The *_device_*
+ * form takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a query enqueued
+ * after a device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+#define SPIRA_MAX_OVERLAP     16u
+int spira_scene_overlap_box_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                int *out_prim, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_overlap_box_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                int *out_prim, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_overlap_box_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                       int *d_out_prim, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+int spira_scene_overlap_box_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                       int *d_out_prim, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+int spira_scene_overlap_any_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_overlap_any_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_overlap_any_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+int spira_scene_overlap_any_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+int spira_overlap_box_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float box10[10]);
+int spira_overlap_box_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double box10[10]);
+int spira_overlap_box_sphere_f32(const float centre[3], float radius, const float box10[10]);
+int spira_overlap_box_sphere_f64(const double centre[3], double radius, const double box10[10]);
+
 /* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
  * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
  * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.

@@ -50,6 +50,7 @@
 #include "spira_hits.h"
 #include "spira_knearest.h"
 #include "spira_sweep.h"
+#include "spira_overlap.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -92,6 +93,8 @@ int nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_po
                        uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream);
 int sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point, float *out_normal,
                    uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
+int overlap_impl_f32(const spira_scene *h, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
+                     uint32_t *out_trips, bool any, bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -1743,6 +1746,42 @@ int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_
 }
 SPIRA_ENTRY(sweep_entry, sweep_impl)
 
+// ======================================================================= spira_scene_overlap_box_* / spira_scene_overlap_any_*: what touches an oriented box
+// Kernels, the contract and the margin argument: spira_overlap.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels
+// whose list capacity (1, 4 or 16) is the smallest that holds max_list.  The device form touches no workspace of the context (it allocates nothing); the
+// host form stages boxes and outputs.
+template <class T, bool ANY, int CAP>
+ListKernels<spira::OverlapArgs<T>> overlap_kernels() {
+    return {spira::k_overlap_session<T, ANY, CAP>, spira::k_overlap<T, true, false, ANY, CAP>, spira::k_overlap<T, false, true, ANY, CAP>, spira::k_overlap<T, false, false, ANY, CAP>, false};
+}
+template <class T>
+int overlap_impl(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
+                 uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+    using A = spira::OverlapArgs<T>;
+    const char *msg = nullptr;
+    if (any) max_list = 0;
+    if (max_list == 0) out_prim = nullptr;      // (count only: the lists have no slots)
+    if (int rc = spira::overlap_check(boxes10 != nullptr, n_boxes, max_list, flags, any ? out_hit != nullptr : (out_prim || out_count), &msg)) return fail(rc, msg);
+    const ListKernels<A> kernels = any ? overlap_kernels<T, true, 1>()
+                                       : max_list <= 1 ? overlap_kernels<T, false, 1>() : max_list <= 4 ? overlap_kernels<T, false, 4>() : overlap_kernels<T, false, 16>();
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_boxes, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n = n_boxes; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free; a.max_list = max_list;
+    const size_t n = n_boxes, slots = n * max_list;
+    // [boxes | prim | count | trips | hit]: the boxes start at a multiple of sizeof(T) or more, the 4-byte blocks of 4
+    StageBlock io[] = {{(void *)boxes10, 10 * n * sizeof(T), kStageIn}, {out_prim, slots * sizeof(int), kStageOut}, {out_count, n * sizeof(uint32_t), kStageOut},
+                       {out_trips, n * sizeof(uint32_t), kStageOut}, {out_hit, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.boxes = (const T *)io[0].dev; a.prim = (int *)io[1].dev; a.count = (uint32_t *)io[2].dev; a.trips = (uint32_t *)io[3].dev; a.hit = (uint8_t *)io[4].dev;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
+SPIRA_ENTRY(overlap_entry, overlap_impl)
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2946,6 +2985,10 @@ int spira_tu::sweep_impl_f32(const spira_scene *h, const float *rays8, const flo
                              float *out_normal, uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
     return sweep_impl<float>(h, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, out_hit, out_trips, any, on_device, user_stream);
 }
+int spira_tu::overlap_impl_f32(const spira_scene *h, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
+                               uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+    return overlap_impl<float>(h, boxes10, n, max_list, flags, out_prim, out_count, out_hit, out_trips, any, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -3145,6 +3188,57 @@ void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], con
     if (out_t) *out_t = hit ? t : t_max;
     if (out_q) { out_q[0] = hit ? q[0] : 0; out_q[1] = hit ? q[1] : 0; out_q[2] = hit ? q[2] : 0; }
     if (out_hit) *out_hit = hit ? 1 : 0;
+}
+
+// ---- box overlap queries on a scene handle (spira_overlap.h)
+int spira_scene_overlap_box_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                                uint32_t *out_trips) {
+    return overlap_entry<float>(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_overlap_box_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim, uint32_t *d_out_count,
+                                       uint32_t *d_out_trips, void *stream) {
+    return overlap_entry<float>(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_overlap_any_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return overlap_entry<float>(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_overlap_any_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return overlap_entry<float>(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+int spira_scene_overlap_box_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                                uint32_t *out_trips) {
+    return overlap_entry<double>(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_overlap_box_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim, uint32_t *d_out_count,
+                                       uint32_t *d_out_trips, void *stream) {
+    return overlap_entry<double>(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_overlap_any_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return overlap_entry<double>(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_overlap_any_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return overlap_entry<double>(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+// host arithmetic, no device: the leaf functions the kernels and the scan call, on a box prepared without a frame.  SPIRA_RAY_INVALID: the box is invalid.
+int spira_overlap_box_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float box10[10]) {
+    spira::OverlapBox<float> B; float He[3];
+    if (!spira::overlap_prepare<float>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
+    return spira::overlap_box_triangle<float>(B, v0, e1, e2) ? 1 : 0;
+}
+int spira_overlap_box_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double box10[10]) {
+    spira::OverlapBox<double> B; double He[3];
+    if (!spira::overlap_prepare<double>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
+    return spira::overlap_box_triangle<double>(B, v0, e1, e2) ? 1 : 0;
+}
+int spira_overlap_box_sphere_f32(const float centre[3], float radius, const float box10[10]) {
+    spira::OverlapBox<float> B; float He[3];
+    if (!spira::overlap_prepare<float>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
+    return spira::overlap_box_sphere<float>(B, centre, radius) ? 1 : 0;
+}
+int spira_overlap_box_sphere_f64(const double centre[3], double radius, const double box10[10]) {
+    spira::OverlapBox<double> B; double He[3];
+    if (!spira::overlap_prepare<double>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
+    return spira::overlap_box_sphere<double>(B, centre, radius) ? 1 : 0;
 }
 
 // ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)

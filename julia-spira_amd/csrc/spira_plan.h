@@ -431,6 +431,19 @@ inline int sweep_check(bool rays, bool radii, uint32_t n, uint32_t flags, bool a
     if (n > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) sweeps"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_overlap_box_* / spira_scene_overlap_any_*: nearest_k_check's rules for a box list; there is no count flag (the count is always complete), so
+// max_list may be 0 as it is.  any_output: out_prim or out_count is given — with max_list == 0 only out_count is one (the any form: out_hit); out_trips
+// alone is no output.
+inline int overlap_check(bool boxes, uint32_t n, uint32_t max_list, uint32_t flags, bool any_output, const char **msg) {
+    if (!boxes) { *msg = "the box array is NULL"; return SPIRA_E_INVALID; }
+    if (n == 0) { *msg = "n is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (max_list > SPIRA_MAX_OVERLAP) { *msg = "max_list is above SPIRA_MAX_OVERLAP (16)"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = max_list ? "every output is NULL" : "max_list is 0 and out_count is NULL: nothing to write"; return SPIRA_E_INVALID; }
+    if (n > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) boxes"; return SPIRA_E_LIMIT; }
+    if ((uint64_t)n * max_list > SPIRA_MAX_RAYS) { *msg = "n * max_list is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
+    return 0;
+}
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

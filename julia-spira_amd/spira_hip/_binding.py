@@ -33,6 +33,8 @@ HITS_COUNT_ALL = 0x2
 # ---- K-nearest point queries (spira_scene_nearest_k_*) ----
 MAX_NEAR = 16
 NEAR_COUNT_ALL = 0x2
+# ---- box overlap queries (spira_scene_overlap_box_* / spira_scene_overlap_any_*) ----
+MAX_OVERLAP = 16
 # ---- camera models of the ray generator (spira_camera_rays_*) ----
 CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO = 0, 1, 2
 MAX_DEPTH, MAX_SPP = 255, 1 << 24
@@ -68,6 +70,9 @@ EXPORTS = [
     "spira_scene_sweep_f32", "spira_scene_sweep_f64", "spira_scene_sweep_device_f32", "spira_scene_sweep_device_f64",
     "spira_scene_sweep_blocked_f32", "spira_scene_sweep_blocked_f64", "spira_scene_sweep_blocked_device_f32", "spira_scene_sweep_blocked_device_f64",
     "spira_sweep_sphere_triangle_f32", "spira_sweep_sphere_triangle_f64",
+    "spira_scene_overlap_box_f32", "spira_scene_overlap_box_f64", "spira_scene_overlap_box_device_f32", "spira_scene_overlap_box_device_f64",
+    "spira_scene_overlap_any_f32", "spira_scene_overlap_any_f64", "spira_scene_overlap_any_device_f32", "spira_scene_overlap_any_device_f64",
+    "spira_overlap_box_triangle_f32", "spira_overlap_box_triangle_f64", "spira_overlap_box_sphere_f32", "spira_overlap_box_sphere_f64",
 ]
 
 
@@ -604,6 +609,50 @@ class Scene:
         _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_void_p(d_radii_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
                   C.c_void_p(d_hit_ptr or None), C.c_void_p(stream_ptr or None)))
 
+    def _boxes(self, boxes10):
+        npdt, _ = _dt(self.prec)
+        b = np.ascontiguousarray(boxes10, dtype=npdt)
+        if b.ndim != 2 or b.shape[1] != 10:
+            raise ValueError("boxes10: n x [cx cy cz hx hy hz qx qy qz qw]")
+        return b
+
+    def overlap_box(self, boxes10, max_list, inplace=False, want_prim=True, want_count=True, want_trips=False):
+        """spira_scene_overlap_box_*: the objects that touch each oriented box of boxes10 (host array, n x [cx cy cz hx hy hz qx qy qz qw]; the library
+        normalises the quaternion).  Returns (prim int32 [n, K], count uint32 [n], trips uint32 [n]), None where not wanted (with max_list = 0 the list is
+        None): prim holds the first max_list candidates in ascending object index, unused slots RAY_MISS, every slot of an invalid box RAY_INVALID; count
+        is the number of ALL candidates (0 for an invalid box).  inplace: the comparison organisation."""
+        b = self._boxes(boxes10)
+        n, k = len(b), int(max_list)
+        room = k if 0 < k <= MAX_OVERLAP else 1      # (a refused max_list: the entry says so)
+        prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
+        count = np.empty(n, dtype=np.uint32) if want_count else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        fn = lib().spira_scene_overlap_box_f32 if self.prec == "f32" else lib().spira_scene_overlap_box_f64
+        _check(fn(self._h, b.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, count, trips)]))
+        return prim, count, trips
+
+    def overlap_any(self, boxes10, inplace=False):
+        """spira_scene_overlap_any_*: uint8 [n] — 1 where anything touches the box, 0 where nothing does, 255 for an invalid box."""
+        b = self._boxes(boxes10)
+        hit = np.empty(len(b), dtype=np.uint8)
+        fn = lib().spira_scene_overlap_any_f32 if self.prec == "f32" else lib().spira_scene_overlap_any_f64
+        _check(fn(self._h, b.ctypes.data_as(C.c_void_p), C.c_uint32(len(b)), C.c_uint32(CAST_INPLACE if inplace else 0), hit.ctypes.data_as(C.c_void_p)))
+        return hit
+
+    def overlap_box_device(self, d_boxes_ptr, n, max_list, d_prim_ptr, d_count_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
+        """spira_scene_overlap_box_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        fn = lib().spira_scene_overlap_box_device_f32 if self.prec == "f32" else lib().spira_scene_overlap_box_device_f64
+        _check(fn(self._h, C.c_void_p(d_boxes_ptr or None), C.c_uint32(n), C.c_uint32(max_list), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  C.c_void_p(d_prim_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+
+    def overlap_any_device(self, d_boxes_ptr, n, d_hit_ptr, stream_ptr, inplace=False):
+        """spira_scene_overlap_any_device_*: DEVICE addresses, asynchronous on the stream."""
+        fn = lib().spira_scene_overlap_any_device_f32 if self.prec == "f32" else lib().spira_scene_overlap_any_device_f64
+        _check(fn(self._h, C.c_void_p(d_boxes_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
+                  C.c_void_p(stream_ptr or None)))
+
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).
         Ray k, sample s is the renderer's path at pixel key key0 + k.  ADDS samples sample0 .. sample0 + spp - 1, in order, to sums ([n, 3], in place; None: a
@@ -922,3 +971,24 @@ def sweep_sphere_triangle(v0, e1, e2, o, d_unit, r, t_min, t_max, prec):
     fn(*[x.ctypes.data_as(C.c_void_p) for x in a], ct(npdt(r)), ct(npdt(t_min)), ct(npdt(t_max)), t.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
        C.cast(C.byref(hit), C.c_void_p))
     return t[0], q, bool(hit.value)
+
+
+def overlap_box_triangle(v0, e1, e2, box10, prec):
+    """spira_overlap_box_triangle_*: the library's leaf function of the box overlap queries on one triangle (v0, e1 = v1 - v0, e2 = v2 - v0) and one box
+    [cx cy cz hx hy hz qx qy qz qw], as host arithmetic (no device needed).  Returns 1, 0, or RAY_INVALID for a box that is invalid without a frame."""
+    npdt, _ = _dt(prec)
+    a = [np.ascontiguousarray(x, dtype=npdt).reshape(3) for x in (v0, e1, e2)] + [np.ascontiguousarray(box10, dtype=npdt).reshape(10)]
+    fn = lib().spira_overlap_box_triangle_f32 if prec == "f32" else lib().spira_overlap_box_triangle_f64
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 4
+    return int(fn(*[x.ctypes.data_as(C.c_void_p) for x in a]))
+
+
+def overlap_box_sphere(centre, radius, box10, prec):
+    """spira_overlap_box_sphere_*: the leaf function on one sphere (a shell) and one box, as host arithmetic.  Returns 1, 0 or RAY_INVALID."""
+    npdt, ct = _dt(prec)
+    c, b = np.ascontiguousarray(centre, dtype=npdt).reshape(3), np.ascontiguousarray(box10, dtype=npdt).reshape(10)
+    fn = lib().spira_overlap_box_sphere_f32 if prec == "f32" else lib().spira_overlap_box_sphere_f64
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, ct, C.c_void_p]
+    return int(fn(c.ctypes.data_as(C.c_void_p), ct(npdt(radius)), b.ctypes.data_as(C.c_void_p)))

@@ -1,6 +1,7 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
 spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries and the
-K-nearest ones (k_nearest, count_within); the sphere sweeps (sweep_spheres, sweep_segments) with the numpy twins of csrc/spira_sweep.h.
+K-nearest ones (k_nearest, count_within); the sphere sweeps (sweep_spheres, sweep_segments) with the numpy twins of csrc/spira_sweep.h; the box overlap
+queries (overlap_boxes, voxelize) with the numpy twins of csrc/spira_overlap.h.
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
 s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s); t, t_min and t_max are distances along that unit direction."""
@@ -429,3 +430,187 @@ def sweep_segments(scene, a, b, radius):
     with np.errstate(all="ignore"):
         frac = np.where(prim == B.RAY_INVALID, T(0), t / rays[:, 7])
     return prim, frac, point
+
+
+# ------------------------------------------------------------------ box overlap queries (spira_scene_overlap_box_* / _any_*; csrc/spira_overlap.h)
+OVERLAP_EXTENT_BOUND = 64      # scenes with a tree: He_k * scale <= 64, He the enclosing axis-aligned half extent
+
+
+def box_axes(quat):
+    """The numpy twin of spira::overlap_axes: quat [..., 4] = (qx, qy, qz, qw) of one dtype.  Returns (A [..., 3, 3], n2 [...]) — row i of A is the box
+    axis A_i in world coordinates; the library normalises the quaternion."""
+    q = np.asarray(quat)
+    T = q.dtype.type
+    with np.errstate(all="ignore"):
+        n2 = (q[..., 0] * q[..., 0] + q[..., 1] * q[..., 1]) + (q[..., 2] * q[..., 2] + q[..., 3] * q[..., 3])
+        l = np.sqrt(n2)
+        x, y, z, w = q[..., 0] / l, q[..., 1] / l, q[..., 2] / l, q[..., 3] / l
+        xx, yy, zz, xy, xz, yz, xw, yw, zw = x * x, y * y, z * z, x * y, x * z, y * z, x * w, y * w, z * w
+        one, two = T(1), T(2)
+        a0 = np.stack([one - two * (yy + zz), two * (xy + zw), two * (xz - yw)], axis=-1)
+        a1 = np.stack([two * (xy - zw), one - two * (xx + zz), two * (yz + xw)], axis=-1)
+        a2 = np.stack([two * (xz + yw), two * (yz - xw), one - two * (xx + yy)], axis=-1)
+    return np.stack([a0, a1, a2], axis=-2), n2
+
+
+def prepare_boxes(boxes10, dtype, frame=None):
+    """The validity rule of spira_overlap.h (overlap_prepare), bit for bit: returns (boxes, A, He, valid) — `boxes` a copy of boxes10
+    ([cx cy cz hx hy hz qx qy qz qw]) in `dtype`, A [n, 3, 3] the box axes, He [n, 3] the enclosing axis-aligned half extents, `valid` the library's
+    verdict per box: no NaN, nothing infinite, h >= 0, n2 finite and normal, and — with a frame (centre[3], scale) — the origin rule for the centre and
+    He_k * scale <= 64."""
+    T = np.dtype(dtype).type
+    b = np.array(boxes10, dtype=T, copy=True).reshape(-1, 10)
+    with np.errstate(all="ignore"):
+        valid = ~np.isnan(b).any(axis=1) & np.isfinite(b).all(axis=1)
+        valid &= ~(b[:, 3:6] < T(0)).any(axis=1)
+        A, n2 = box_axes(b[:, 6:10])
+        valid &= np.isfinite(n2) & ~(n2 < np.finfo(T).tiny)
+        h = b[:, 3:6]
+        He = (np.abs(A[:, 0, :]) * h[:, 0:1] + np.abs(A[:, 1, :]) * h[:, 1:2]) + np.abs(A[:, 2, :]) * h[:, 2:3]
+        if frame is not None:
+            c, scale = np.asarray(frame[0], dtype=T), T(frame[1])
+            x = (b[:, :3] - c[None, :]) * scale
+            valid &= ((x >= T(-ORIGIN_BOUND)) & (x <= T(ORIGIN_BOUND))).all(axis=1)
+            valid &= ((He * scale) <= T(OVERLAP_EXTENT_BOUND)).all(axis=1)
+    return b, A, He, valid
+
+
+def _box_frame(A, a):
+    return np.stack([_dot3(A[..., 0, :], a), _dot3(A[..., 1, :], a), _dot3(A[..., 2, :], a)], axis=-1)
+
+
+def _overlap_axis(p0, p1, p2, rad):
+    ok = ~(np.isnan(p0) | np.isnan(p1) | np.isnan(p2) | np.isnan(rad))
+    return ok & (np.minimum(np.minimum(p0, p1), p2) <= rad) & (np.maximum(np.maximum(p0, p1), p2) >= -rad)
+
+
+def overlap_box_triangle(v0, e1, e2, c, h, A):
+    """The numpy twin of spira::overlap_box_triangle: v0, e1 = v1 - v0, e2 = v2 - v0, the box centre c and half extents h are arrays [..., 3] and A
+    [..., 3, 3] (box_axes) of ONE dtype that broadcast against each other (boxes x objects: c[:, None, :] against v0[None, :, :]).  All 13 axes are
+    evaluated; the same operations in the same order on the same values as the header.  Returns the candidate verdict, bool [...]."""
+    v0, e1, e2, c, h, A = (np.asarray(x) for x in (v0, e1, e2, c, h, A))
+    with np.errstate(all="ignore"):
+        u0, f1, f2 = _box_frame(A, v0 - c), _box_frame(A, e1), _box_frame(A, e2)
+        u1, u2, f3 = u0 + f1, u0 + f2, f2 - f1
+        ok = np.ones(np.broadcast(u0[..., 0], h[..., 0]).shape, dtype=bool)
+        for k in range(3):
+            ok &= _overlap_axis(u0[..., k], u1[..., k], u2[..., k], h[..., k])
+        n = np.stack([f1[..., 1] * f2[..., 2] - f1[..., 2] * f2[..., 1], f1[..., 2] * f2[..., 0] - f1[..., 0] * f2[..., 2],
+                      f1[..., 0] * f2[..., 1] - f1[..., 1] * f2[..., 0]], axis=-1)
+        pn = _dot3(n, u0)
+        ok &= _overlap_axis(pn, pn, pn, (np.abs(n[..., 0]) * h[..., 0] + np.abs(n[..., 1]) * h[..., 1]) + np.abs(n[..., 2]) * h[..., 2])
+        ok &= (n != 0).any(axis=-1)                                   # zero area: never a candidate
+        for f in (f1, f2, f3):
+            for i in range(3):
+                a, b = (i + 1) % 3, (i + 2) % 3
+                fa, fb = f[..., a], f[..., b]
+                ok &= _overlap_axis(u0[..., b] * fa - u0[..., a] * fb, u1[..., b] * fa - u1[..., a] * fb, u2[..., b] * fa - u2[..., a] * fb,
+                                    np.abs(fb) * h[..., a] + np.abs(fa) * h[..., b])
+    return ok
+
+
+def overlap_box_sphere(centre, radius, c, h, A):
+    """The numpy twin of spira::overlap_box_sphere (the sphere is a shell): centre [..., 3], radius [...], and the box c, h, A as overlap_box_triangle."""
+    centre, radius, c, h, A = (np.asarray(x) for x in (centre, radius, c, h, A))
+    T = c.dtype.type
+    with np.errstate(all="ignore"):
+        p = _box_frame(A, centre - c)
+        a = np.abs(p)
+        e = a - h
+        e = np.where(e > T(0), e, T(0))
+        g = a + h
+        dmin2, dmax2, r2 = _dot3(e, e), _dot3(g, g), radius * radius
+        return (dmin2 <= r2) & (dmax2 >= r2)
+
+
+def overlap_boxes(scene, boxes, max_list, any=False, inplace=False, want_trips=False, stream=None):
+    """spira_scene_overlap_box_* (any: spira_scene_overlap_any_*): the objects that touch each oriented box ([cx cy cz hx hy hz qx qy qz qw]).  Returns
+    (prim int32 [n, K] — the first max_list candidates in ascending object index, None with max_list = 0 —, count [n] of ALL candidates, trips [n] or
+    None), or for `any` the uint8 [n] verdicts (1 touched, 0 not, 255 invalid).  boxes: a host array [n, 10] — the host form, numpy arrays back — or a torch
+    tensor on the scene's device in the scene's precision — the device form, enqueued on `stream` (a torch.cuda.Stream; None: the current one), device
+    tensors back without synchronising (count and trips as int32); `boxes` must stay alive until the work has run."""
+    if isinstance(boxes, np.ndarray) or not hasattr(boxes, "is_cuda"):
+        if any:
+            return scene.overlap_any(boxes, inplace=inplace)
+        return scene.overlap_box(boxes, max_list, inplace=inplace, want_trips=want_trips)
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if boxes.dtype != want or not boxes.is_cuda or boxes.dim() != 2 or boxes.shape[1] != 10 or not boxes.is_contiguous():
+        raise ValueError("overlap_boxes: a contiguous device tensor of n x 10 %s values is needed" % scene.prec)
+    n, k = boxes.shape[0], int(max_list)
+    room = k if 0 < k <= B.MAX_OVERLAP else 1
+    st = stream if stream is not None else torch.cuda.current_stream(boxes.device)
+    with torch.cuda.stream(st):
+        if any:
+            hit = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+            scene.overlap_any_device(boxes.data_ptr(), n, hit.data_ptr(), st.cuda_stream, inplace=inplace)
+            return hit
+        prim = torch.empty((n, room), dtype=torch.int32, device=boxes.device) if k else None
+        count = torch.empty(n, dtype=torch.int32, device=boxes.device)
+        trips = torch.empty(n, dtype=torch.int32, device=boxes.device) if want_trips else None
+        ptr = lambda t: t.data_ptr() if t is not None else 0
+        scene.overlap_box_device(boxes.data_ptr(), n, k, ptr(prim), count.data_ptr(), st.cuda_stream, inplace=inplace, d_trips_ptr=ptr(trips))
+    return prim, count, trips
+
+
+def boxes_from_bounds(lo, hi):
+    """Axis-aligned boxes [n, 10] with the identity quaternion from their corners lo, hi [n, 3] (numpy arrays, or torch tensors — then on their device):
+    c = (lo + hi) / 2, h = (hi - lo) / 2."""
+    if hasattr(lo, "is_cuda"):
+        import torch
+        q = torch.zeros((lo.shape[0], 4), dtype=lo.dtype, device=lo.device)
+        q[:, 3] = 1
+        return torch.cat([(lo + hi) / 2, (hi - lo) / 2, q], dim=1).contiguous()
+    lo, hi = np.asarray(lo), np.asarray(hi)
+    lo, hi = lo.reshape(-1, 3), hi.reshape(-1, 3)
+    q = np.zeros((len(lo), 4), dtype=np.result_type(lo, hi))
+    q[:, 3] = 1
+    return np.concatenate([(lo + hi) / 2, (hi - lo) / 2, q], axis=1)
+
+
+def voxel_boxes(lo, hi, dims, dtype):
+    """The cells of voxelize as host boxes [nx ny nz, 10] in `dtype`, x slowest: with half_k = fl((hi_k - lo_k) / (2 dims_k)) (Float64, then rounded to
+    dtype), cell i of axis k has the centre lo_k + (2 i + 1) half_k (in dtype: one product, one sum) and the half extent half_k."""
+    T = np.dtype(dtype).type
+    lo64, hi64 = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    dims = [int(d) for d in dims]
+    half = ((hi64 - lo64) / (2.0 * np.asarray(dims, dtype=np.float64))).astype(T)
+    lo_t = lo64.astype(T)
+    cs = [lo_t[k] + (2 * np.arange(dims[k]) + 1).astype(T) * half[k] for k in range(3)]
+    g = np.stack(np.meshgrid(*cs, indexing="ij"), axis=-1).reshape(-1, 3)
+    out = np.zeros((len(g), 10), dtype=T)
+    out[:, 0:3], out[:, 3:6], out[:, 9] = g, half[None, :], T(1)
+    return out
+
+
+def voxelize(scene, lo, hi, dims, stream=None):
+    """A surface voxelisation: the grid of dims = (nx, ny, nz) cells over the box [lo, hi]; a cell is True where its closed box touches a surface of the
+    scene (a triangle, or a sphere's shell).  The cells (voxel_boxes' arithmetic, identity quaternions) are made on the scene's device with torch and
+    answered by spira_scene_overlap_any_device_* on `stream` (a torch.cuda.Stream; None: the current one).  Returns a bool device tensor [nx, ny, nz]
+    without synchronising; cells the library calls invalid (beyond the origin or the extent rule) are False."""
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    T = np.float32 if scene.prec == "f32" else np.float64
+    dims = [int(d) for d in dims]
+    lo64, hi64 = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    half = ((hi64 - lo64) / (2.0 * np.asarray(dims, dtype=np.float64))).astype(T)
+    lo_t = lo64.astype(T)
+    dev = torch.device("cuda", torch.cuda.current_device())      # (a handle is resident on the current device)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    n = dims[0] * dims[1] * dims[2]
+    with torch.cuda.stream(st):
+        cs = []
+        for k in range(3):
+            odd = (2 * torch.arange(dims[k], device=dev) + 1).to(want)
+            cs.append(torch.tensor(lo_t[k], dtype=want, device=dev) + odd * torch.tensor(half[k], dtype=want, device=dev))
+        boxes = torch.zeros((dims[0], dims[1], dims[2], 10), dtype=want, device=dev)
+        boxes[..., 0] = cs[0][:, None, None]
+        boxes[..., 1] = cs[1][None, :, None]
+        boxes[..., 2] = cs[2][None, None, :]
+        for k in range(3):
+            boxes[..., 3 + k] = float(half[k])
+        boxes[..., 9] = 1
+        boxes = boxes.reshape(n, 10)
+        hit = overlap_boxes(scene, boxes, 0, any=True, stream=st)
+        boxes.record_stream(st)
+        return (hit == 1).reshape(dims[0], dims[1], dims[2])
