@@ -212,6 +212,22 @@ def build_set(ns, sc, seed=31, n_near=768, n_box=640, n_edge=128, n_far=64, n_r=
     return _freeze(dict(points=points, prim=prim, dist=dist, point=point, valid=valid, parts=parts, sel=sel, invalid_at=at + parts["mixed"].start))
 
 
+def frame_mesh(prec, fi, how):
+    """The blob mesh in placement fi of cast_support.FRAMES; how = create: as built; update: twisted (test_gpu_refit.deform), the validity frame stays the
+    creation frame; rebuild: twisted, then scaled by 1.7 and moved, the frame is the fresh build's of that mesh.  Returns (A, B, frame) — frame None: B's own."""
+    from test_gpu_refit import deform
+    A = S.blob_scene(2, *S.FRAMES[fi])
+    if how == "create":
+        return A, A, None
+    tri = deform(A["triangles10"])
+    if how == "rebuild":
+        tri = np.array(tri)
+        for v in range(3):
+            tri[:, 3 * v:3 * v + 3] = tri[:, 3 * v:3 * v + 3] * 1.7 + np.array([0.5, -0.25, 1.0]) * S.FRAMES[fi][0]
+    B = dict(A, triangles10=tri)
+    return A, B, S.mesh_frame(A["triangles10"], prec) if how == "update" else S.mesh_frame(tri, prec)
+
+
 @functools.lru_cache(maxsize=None)
 def scan_of(name, prec):
     return NearScan(scene(name), prec)

@@ -238,6 +238,41 @@ def build_set(ss, sc, seed=91, n_surf=1024, n_whole=24, n_thin=384, n_zero=192, 
     return N._freeze(dict(ref, boxes=boxes, parts=parts, invalid_at=at + parts["mixed"].start))
 
 
+# ------------------------------------------------------------------ the sets of the edge tests (test_overlap_edges_cpu.py, test_gpu_overlap_edges.py)
+FRAME_SET = dict(n_surf=384, n_whole=8, n_thin=128, n_zero=64, n_far=16, n_small=24, n_mixed=70)
+
+
+@functools.lru_cache(maxsize=None)
+def frame_case(prec, fi, how):
+    """nearest_support.frame_mesh — the blob mesh in placement fi of cast_support.FRAMES, as built, after an update, after a rebuild — with a box set of
+    718 boxes in the frame that holds.  Returns (A, B, the scan of B, the set)."""
+    A, B, frame = N.frame_mesh(prec, fi, how)
+    ss = OverlapScan(B, prec, frame=frame)
+    return A, B, ss, build_set(ss, B, seed=95 + fi, **FRAME_SET)
+
+
+def frame_conditions(ref):
+    """What a frame case must hold, asserted: the valid / invalid pattern of the far boxes and the small far boxes, boxes with more than 16 candidates,
+    valid ones with none, with 1 .. 4 and with 5 .. 16, invalid ones, and a valid far box that touches something.  Returns the counts."""
+    v, c = ref["valid"], ref["count"].astype(np.int64)
+    far, small = ref["parts"]["far"], ref["parts"]["small"]
+    assert v[far][0::2].all() and not v[far][1::2].any() and v[small][0::2].all() and not v[small][1::2].any()
+    out = dict(many=int((c > 16).sum()), none=int((v & (c == 0)).sum()), few=int(((c >= 1) & (c <= 4)).sum()), some=int(((c >= 5) & (c <= 16)).sum()),
+               invalid=int((~v).sum()), far_touching=int((c[far][0::2] > 0).sum()))
+    assert out["many"] >= 32 and out["none"] >= 48 and out["few"] >= 200 and out["some"] >= 100 and out["invalid"] >= 40 and out["far_touching"] >= 1, out
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def deep_set(prec):
+    """The blob at level 4 (5 120 triangles, 2 spheres): 8 boxes that contain the whole mesh and 120 boxes at its surface."""
+    sc = N.scene("s4_4")
+    ss = OverlapScan(sc, prec)
+    rng = np.random.default_rng(97)
+    boxes = np.array(np.concatenate([containing(rng, sc, 8), at_surface(rng, sc, 120)]), dtype=ss.T).astype(np.float64)
+    return ss, N._freeze(dict(ss.overlap(boxes), boxes=boxes, parts=dict(whole=slice(0, 8), surface=slice(8, 128))))
+
+
 @functools.lru_cache(maxsize=None)
 def scan_of(name, prec):
     return OverlapScan(scene(name), prec)

@@ -120,18 +120,7 @@ def test_session_refills_at_both_ends_of_the_threshold(gpu, prec, n, refill):
 def _frame_case(prec, fi, how):
     """The blob mesh in placement fi; how = create: as built; update: twisted (test_gpu_refit.deform), the validity frame stays the creation frame;
     rebuild: twisted, then scaled by 1.7 and moved, the frame is the fresh build's of that mesh.  Returns (A, B, scan of B in the frame that holds, set)."""
-    from test_gpu_refit import deform
-    A = S.blob_scene(2, *S.FRAMES[fi])
-    if how == "create":
-        B, frame = A, None
-    else:
-        tri = deform(A["triangles10"])
-        if how == "rebuild":
-            tri = np.array(tri)
-            for v in range(3):
-                tri[:, 3 * v:3 * v + 3] = tri[:, 3 * v:3 * v + 3] * 1.7 + np.array([0.5, -0.25, 1.0]) * S.FRAMES[fi][0]
-        B = dict(A, triangles10=tri)
-        frame = S.mesh_frame(A["triangles10"], prec) if how == "update" else S.mesh_frame(tri, prec)
+    A, B, frame = N.frame_mesh(prec, fi, how)                        # (shared with the K-nearest and the overlap edge tests)
     ns = N.NearScan(B, prec, frame=frame)
     return A, B, ns, N.build_set(ns, B, seed=33 + fi, n_near=256, n_box=192, n_edge=64, n_far=48, n_r=32)
 
