@@ -478,6 +478,48 @@ int spira_scene_nearest_k_device_f32(const spira_scene *scene, const float *d_po
 int spira_scene_nearest_k_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags,
                                      int *d_out_prim, double *d_out_dist, double *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
 
+/* ---- signed distance queries on a scene handle: the nearest surface of every point AND which side of it the point is on (signed distance fields,
+ *      containment, "am I inside?") ----
+ * points4 (n_points x [px py pz r_max]), the validity rule and the origin rule are exactly those of spira_scene_closest_point_*.  Every step below is in the
+ * call's precision T, in the written order, nothing fused.  Per valid point p:
+ *   1. Nearest surface: the closest-point scan of spira_scene_closest_point_* unchanged.  out_prim and out_point are byte for byte that entry's; out_dist is
+ *      that entry's value (sqrt(d2), or r_max copied on a miss) with the sign bit set where the point is inside — -0.0 can occur.
+ *   2. Inside a sphere: for sphere s, w = p - c and l = sqrt(w.w) are the values the closest-point sphere function forms, the radius is as given
+ *      (spheres5[5 s + 3]); the point is inside the sphere when l < r.
+ *   3. Inside the mesh (scenes with at least one triangle): ray j = [p, t_min 0, D_j, t_max +Inf] with D_0 = (0.5377, 0.7211, 0.4366),
+ *      D_1 = (-0.6123, 0.3142, 0.7255), D_2 = (0.2873, -0.4691, -0.8351) rounded to T, prepared as any caller's ray is (the unit direction is the one cast
+ *      would walk).  c_j is the number of TRIANGLE candidates of that ray under the multi-hit candidate rule: the per-object triangle test with the ray's own
+ *      t_min and t_max; spheres are not tested at all.  Rays 0 and 1 are always walked.  If c_0 and c_1 have the same parity, that parity decides (odd:
+ *      inside) and c_2 = SPIRA_SDF_SKIPPED; otherwise ray 2 is walked and its parity decides — the majority of three votes.  A scene without triangles: all
+ *      three slots are SPIRA_SDF_SKIPPED and the point is not inside a mesh.
+ *   4. out_inside is 1 where step 2 or step 3 says inside, else 0.  out_crossings is n_points x 3, the c_j.  out_trips (optional, diagnostic, outside the
+ *      contract): node visits plus leaf tests of all the walks the point's lane took.
+ * The sign is MEANINGFUL for closed meshes (every edge shared by two triangles, no self-intersection): a ray from an inside point crosses the surface an odd
+ * number of times; a ray exactly through an edge or a vertex may count a crossing twice, which is why three directions vote.  It is DEFINED — the rule above,
+ * bit for bit — for every mesh, open ones included.
+ * An INVALID point gives prim SPIRA_RAY_INVALID, dist 0, point 0, inside 255, crossings 0 0 0; it never faults and never disturbs its neighbours.
+ * Each output may be NULL, but not all of out_prim, out_dist, out_point, out_inside and out_crossings.  When out_prim, out_dist and out_point are all NULL the
+ * nearest walk is skipped altogether: the sign-only query, whose out_inside and out_crossings equal the full form's.
+ * flags: 0, the library's organisation for scenes with a tree — refilled sessions: a lane carries its point through the nearest walk and then the ray walks
+ * before it takes the next point — or SPIRA_CAST_INPLACE, one lane per point walking everything to the end.  Both give identical bytes.  Scenes without a tree
+ * run one lane per point either way.
+ * Errors, all decided before any device is touched: a NULL point array, n_points == 0, unknown flag bits, all five outputs NULL (out_trips alone is no
+ * output), a NULL or destroyed handle, one of the other precision or of another device: SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS: SPIRA_E_LIMIT.  A handle
+ * made by spira_scene_create_multi_* is served by device 0's copy.  The host form copies in and out and returns when the outputs are written.  The *_device_*
+ * form takes DEVICE pointers, is asynchronous on `stream`, synchronises nothing, allocates nothing, and is ordered like every entry: a query enqueued after a
+ * device-form update or rebuild on another stream sees the new tree.  spira_get_counters is not affected by these entries. */
+#define SPIRA_SDF_SKIPPED 0xFFFFFFFFu
+int spira_scene_signed_distance_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags,
+                                    int *out_prim, float *out_dist, float *out_point, uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips);
+int spira_scene_signed_distance_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags,
+                                    int *out_prim, double *out_dist, double *out_point, uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips);
+int spira_scene_signed_distance_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags,
+                                           int *d_out_prim, float *d_out_dist, float *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings,
+                                           uint32_t *d_out_trips, void *stream);
+int spira_scene_signed_distance_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags,
+                                           int *d_out_prim, double *d_out_dist, double *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings,
+                                           uint32_t *d_out_trips, void *stream);
+
 /* ---- sphere sweeps on a scene handle: the first contact of a moving ball (character motion, projectile CCD, camera collision, clearance checks) ----
  * "A ball of radius r moves from o along d: when and where does it first touch the scene?"  rays8 is exactly cast's list, n x [ox oy oz t_min dx dy dz
  * t_max]; the library normalises d; t, t_min and t_max are distances of the ball's CENTRE along the unit direction, c(t) = o + d t.  radii holds n values,

@@ -51,6 +51,7 @@
 #include "spira_knearest.h"
 #include "spira_sweep.h"
 #include "spira_overlap.h"
+#include "spira_sdf.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
@@ -95,6 +96,8 @@ int sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii,
                    uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
 int overlap_impl_f32(const spira_scene *h, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
                      uint32_t *out_trips, bool any, bool on_device, void *user_stream);
+int signed_distance_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                             uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream);
 int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
 int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
 int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
@@ -1782,6 +1785,41 @@ int overlap_impl(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint3
 }
 SPIRA_ENTRY(overlap_entry, overlap_impl)
 
+// ======================================================================= spira_scene_signed_distance_*: the nearest surface of every point and which side of it
+// Kernels and the contract: spira_sdf.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels with or without the nearest
+// walk (out_prim, out_dist and out_point all NULL: the sign-only query).  The device form touches no workspace of the context (it allocates nothing); the
+// host form stages points and outputs.
+static_assert(spira::kSdfSkipped == SPIRA_SDF_SKIPPED, "spira_sdf.h and the header disagree on SPIRA_SDF_SKIPPED");
+template <class T, bool NEAR>
+ListKernels<spira::SdfArgs<T>> sdf_kernels() {
+    return {spira::k_sdf_session<T, NEAR>, spira::k_sdf<T, true, false, NEAR>, spira::k_sdf<T, false, true, NEAR>, spira::k_sdf<T, false, false, NEAR>, false};
+}
+template <class T>
+int signed_distance_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint8_t *out_inside,
+                         uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream) {
+    using A = spira::SdfArgs<T>;
+    const char *msg = nullptr;
+    if (int rc = spira::signed_distance_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point || out_inside || out_crossings, &msg)) return fail(rc, msg);
+    const ListKernels<A> kernels = spira::signed_distance_wants_nearest(out_prim, out_dist, out_point) ? sdf_kernels<T, true>() : sdf_kernels<T, false>();
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    const size_t n = n_points, t_b = n * sizeof(T);
+    // [points | dist | point | prim | crossings | trips | inside]: every block starts at a multiple of its element size or more
+    StageBlock io[] = {{(void *)points4, 4 * t_b, kStageIn}, {out_dist, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut},
+                       {out_crossings, 3 * n * sizeof(uint32_t), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}, {out_inside, n, kStageOut}};
+    if (int rc = stage_in(s, io)) return rc;
+    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.crossings = (uint32_t *)io[4].dev;
+    a.trips = (uint32_t *)io[5].dev; a.inside = (uint8_t *)io[6].dev;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
+SPIRA_ENTRY(signed_distance_entry, signed_distance_impl)
+
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
 // (+ k_radiance_sum where a pass holds more than one sample per ray).  The workspace of such a pass is the context's L, grown on the first call at a size;
@@ -2989,6 +3027,10 @@ int spira_tu::overlap_impl_f32(const spira_scene *h, const float *boxes10, uint3
                                uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
     return overlap_impl<float>(h, boxes10, n, max_list, flags, out_prim, out_count, out_hit, out_trips, any, on_device, user_stream);
 }
+int spira_tu::signed_distance_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                                       uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream) {
+    return signed_distance_impl<float>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, on_device, user_stream);
+}
 int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
 }
@@ -3239,6 +3281,24 @@ int spira_overlap_box_sphere_f64(const double centre[3], double radius, const do
     spira::OverlapBox<double> B; double He[3];
     if (!spira::overlap_prepare<double>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
     return spira::overlap_box_sphere<double>(B, centre, radius) ? 1 : 0;
+}
+
+// ---- signed distance queries on a scene handle (spira_sdf.h)
+int spira_scene_signed_distance_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
+                                    uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips) {
+    return signed_distance_entry<float>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
+}
+int spira_scene_signed_distance_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, float *d_out_dist,
+                                           float *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings, uint32_t *d_out_trips, void *stream) {
+    return signed_distance_entry<float>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
+}
+int spira_scene_signed_distance_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags, int *out_prim, double *out_dist, double *out_point,
+                                    uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips) {
+    return signed_distance_entry<double>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
+}
+int spira_scene_signed_distance_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, double *d_out_dist,
+                                           double *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings, uint32_t *d_out_trips, void *stream) {
+    return signed_distance_entry<double>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
 }
 
 // ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)

@@ -444,6 +444,17 @@ inline int overlap_check(bool boxes, uint32_t n, uint32_t max_list, uint32_t fla
     if ((uint64_t)n * max_list > SPIRA_MAX_RAYS) { *msg = "n * max_list is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_signed_distance_*: closest point's rules; any_output: out_prim, out_dist, out_point, out_inside or out_crossings is given (out_trips alone is no
+// output).  With out_prim, out_dist and out_point all NULL the call is the sign-only query: the nearest walk is not run (signed_distance_wants_nearest).
+inline int signed_distance_check(bool points, uint32_t n_points, uint32_t flags, bool any_output, const char **msg) {
+    if (!points) { *msg = "the point array is NULL"; return SPIRA_E_INVALID; }
+    if (n_points == 0) { *msg = "n_points is 0"; return SPIRA_E_INVALID; }
+    if (flags & ~SPIRA_CAST_INPLACE) { *msg = "unknown flag bits (SPIRA_CAST_INPLACE is the only one)"; return SPIRA_E_INVALID; }
+    if (!any_output) { *msg = "out_prim, out_dist, out_point, out_inside and out_crossings are all NULL"; return SPIRA_E_INVALID; }
+    if (n_points > SPIRA_MAX_RAYS) { *msg = "more than SPIRA_MAX_RAYS (2^26) points"; return SPIRA_E_LIMIT; }
+    return 0;
+}
+inline bool signed_distance_wants_nearest(bool prim, bool dist, bool point) { return prim || dist || point; }
 inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block, const CastKnobs &k) {
     CastPlan p;
     p.n_rays = n_rays;

@@ -35,6 +35,8 @@ MAX_NEAR = 16
 NEAR_COUNT_ALL = 0x2
 # ---- box overlap queries (spira_scene_overlap_box_* / spira_scene_overlap_any_*) ----
 MAX_OVERLAP = 16
+# ---- signed distance queries (spira_scene_signed_distance_*) ----
+SDF_SKIPPED = 0xFFFFFFFF
 # ---- camera models of the ray generator (spira_camera_rays_*) ----
 CAM_PINHOLE, CAM_THIN_LENS, CAM_ORTHO = 0, 1, 2
 MAX_DEPTH, MAX_SPP = 255, 1 << 24
@@ -73,6 +75,7 @@ EXPORTS = [
     "spira_scene_overlap_box_f32", "spira_scene_overlap_box_f64", "spira_scene_overlap_box_device_f32", "spira_scene_overlap_box_device_f64",
     "spira_scene_overlap_any_f32", "spira_scene_overlap_any_f64", "spira_scene_overlap_any_device_f32", "spira_scene_overlap_any_device_f64",
     "spira_overlap_box_triangle_f32", "spira_overlap_box_triangle_f64", "spira_overlap_box_sphere_f32", "spira_overlap_box_sphere_f64",
+    "spira_scene_signed_distance_f32", "spira_scene_signed_distance_f64", "spira_scene_signed_distance_device_f32", "spira_scene_signed_distance_device_f64",
 ]
 
 
@@ -652,6 +655,37 @@ class Scene:
         fn = lib().spira_scene_overlap_any_device_f32 if self.prec == "f32" else lib().spira_scene_overlap_any_device_f64
         _check(fn(self._h, C.c_void_p(d_boxes_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
                   C.c_void_p(stream_ptr or None)))
+
+    def signed_distance(self, points4, inplace=False, want_point=True, want_crossings=False, want_trips=False, want_prim=True, want_dist=True, want_inside=True):
+        """spira_scene_signed_distance_*: for every point of points4 (host array, as for closest_point) the nearest surface and which side of it the point is
+        on.  Returns (prim int32 [n], dist [n], point [n, 3], inside uint8 [n], crossings uint32 [n, 3], trips uint32 [n]), None where not wanted: prim and
+        point are closest_point's, dist is closest_point's with the sign bit set where the point is inside; inside is 1, 0 or 255 (an invalid point);
+        crossings the triangle candidates of the three rays (SDF_SKIPPED: ray not walked).  With prim, dist and point all unwanted the nearest walk is not
+        run (the sign-only query).  inplace: the comparison organisation."""
+        npdt, _ = _dt(self.prec)
+        p = np.ascontiguousarray(points4, dtype=npdt)
+        if p.ndim != 2 or p.shape[1] != 4:
+            raise ValueError("points4: n_points x [px py pz r_max]")
+        n = len(p)
+        prim = np.empty(n, dtype=np.int32) if want_prim else None
+        dist = np.empty(n, dtype=npdt) if want_dist else None
+        point = np.empty((n, 3), dtype=npdt) if want_point else None
+        inside = np.empty(n, dtype=np.uint8) if want_inside else None
+        crossings = np.empty((n, 3), dtype=np.uint32) if want_crossings else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        fn = lib().spira_scene_signed_distance_f32 if self.prec == "f32" else lib().spira_scene_signed_distance_f64
+        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
+                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, inside, crossings, trips)]))
+        return prim, dist, point, inside, crossings, trips
+
+    def signed_distance_device(self, d_points_ptr, n_points, d_prim_ptr, d_dist_ptr, d_point_ptr, d_inside_ptr, stream_ptr, inplace=False, d_crossings_ptr=0,
+                               d_trips_ptr=0):
+        """spira_scene_signed_distance_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        fn = lib().spira_scene_signed_distance_device_f32 if self.prec == "f32" else lib().spira_scene_signed_distance_device_f64
+        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
+                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_inside_ptr or None), C.c_void_p(d_crossings_ptr or None),
+                  C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
 
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).

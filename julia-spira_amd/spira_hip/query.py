@@ -1,7 +1,8 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
 spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries and the
 K-nearest ones (k_nearest, count_within); the sphere sweeps (sweep_spheres, sweep_segments) with the numpy twins of csrc/spira_sweep.h; the box overlap
-queries (overlap_boxes, voxelize) with the numpy twins of csrc/spira_overlap.h.
+queries (overlap_boxes, voxelize) with the numpy twins of csrc/spira_overlap.h; the signed distance queries (signed_distance, inside_points,
+distance_field) with the numpy restatement of their sign rule.
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
 s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s); t, t_min and t_max are distances along that unit direction."""
@@ -614,3 +615,127 @@ def voxelize(scene, lo, hi, dims, stream=None):
         hit = overlap_boxes(scene, boxes, 0, any=True, stream=st)
         boxes.record_stream(st)
         return (hit == 1).reshape(dims[0], dims[1], dims[2])
+
+
+# ------------------------------------------------------------------ signed distance queries (spira_scene_signed_distance_*; csrc/spira_sdf.h)
+def inside_spheres(spheres5, points, dtype):
+    """Step 2 of the contract in numpy: w = p - c, l = sqrt(w.w) (closest_point_sphere's values), inside when l < r as given.  spheres5 [ns, 5] and
+    points [n, 3] are taken in `dtype`.  Returns bool [n]."""
+    T = np.dtype(dtype).type
+    sp = np.asarray(spheres5, dtype=T).reshape(-1, 5)
+    p = np.asarray(points, dtype=T).reshape(-1, 3)
+    if not len(sp):
+        return np.zeros(len(p), dtype=bool)
+    with np.errstate(all="ignore"):
+        w = p[:, None, :] - sp[None, :, 0:3]
+        l = np.sqrt(_dot3(w, w))
+        return (l < sp[None, :, 3]).any(axis=1)
+
+
+def signed_distance_rules(valid, prim, dist, point, in_sphere, counts, has_triangles):
+    """Steps 2 to 4 of the contract in numpy, given the closest-point scan's outputs (prim, dist, point: miss and invalid rows as that entry writes them),
+    the sphere verdict of step 2 (bool [n]) and the triangle candidates of the three rays (counts [n, 3], every ray counted).  Returns (prim, dist, point,
+    inside uint8 [n], crossings uint32 [n, 3]) as spira_scene_signed_distance_* writes them: ray 2's slot is SDF_SKIPPED where the first two parities
+    agree, all three where the scene has no triangle; an invalid point has inside 255 and crossings 0."""
+    valid = np.asarray(valid, dtype=bool)
+    n = len(valid)
+    cr = np.full((n, 3), B.SDF_SKIPPED, dtype=np.uint32)
+    mesh = np.zeros(n, dtype=bool)
+    if has_triangles:
+        c = np.asarray(counts).reshape(n, 3).astype(np.uint32)
+        agree = ((c[:, 0] ^ c[:, 1]) & 1) == 0
+        cr[:, 0], cr[:, 1] = c[:, 0], c[:, 1]
+        cr[:, 2] = np.where(agree, np.uint32(B.SDF_SKIPPED), c[:, 2])
+        mesh = (np.where(agree, c[:, 0], c[:, 2]) & 1) == 1
+    inside = valid & (np.asarray(in_sphere, dtype=bool) | mesh)
+    cr[~valid] = 0
+    d = np.array(dist, copy=True)
+    d[inside] = -np.abs(d[inside])                                   # the sign bit set: -0.0 can occur
+    return np.array(prim, copy=True), d, np.array(point, copy=True), np.where(valid, inside.astype(np.uint8), np.uint8(255)), cr
+
+
+def signed_distance(scene, points, inplace=False, want_point=True, want_crossings=False, want_trips=False, stream=None):
+    """The nearest surface of every point ([px py pz r_max]) and which side of it the point is on: (prim int32 [n], dist [n] — negative inside —,
+    point [n, 3], inside uint8 [n] (1, 0, 255 for an invalid point), crossings [n, 3], trips [n]), None where not wanted.  The sign is meaningful for
+    closed meshes and defined for every mesh, as inside_mesh's; a point inside a sphere of the scene is inside.  points: a host array [n, 4] — the host
+    form, numpy arrays back — or a torch tensor on the scene's device in the scene's precision — spira_scene_signed_distance_device_*, enqueued on
+    `stream` (a torch.cuda.Stream; None: the current one), device tensors back without synchronising (crossings and trips as int32: SDF_SKIPPED reads -1);
+    `points` must stay alive until the work has run."""
+    if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
+        return scene.signed_distance(points, inplace=inplace, want_point=want_point, want_crossings=want_crossings, want_trips=want_trips)
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+        raise ValueError("signed_distance: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
+    n = points.shape[0]
+    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    with torch.cuda.stream(st):
+        prim = torch.empty(n, dtype=torch.int32, device=points.device)
+        dist = torch.empty(n, dtype=want, device=points.device)
+        q = torch.empty((n, 3), dtype=want, device=points.device) if want_point else None
+        inside = torch.empty(n, dtype=torch.uint8, device=points.device)
+        cr = torch.empty((n, 3), dtype=torch.int32, device=points.device) if want_crossings else None
+        trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
+        ptr = lambda t: t.data_ptr() if t is not None else 0
+        scene.signed_distance_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), ptr(q), inside.data_ptr(), st.cuda_stream, inplace=inplace,
+                                     d_crossings_ptr=ptr(cr), d_trips_ptr=ptr(trips))
+    return prim, dist, q, inside, cr, trips
+
+
+def inside_points(scene, points, stream=None):
+    """The sign-only form: is every point ([n, 3], or [n, 4] whose fourth column is ignored) inside the scene — inside a sphere, or inside the mesh by the
+    vote of signed_distance?  No nearest walk is run.  Host array: bool numpy array back; device tensor: a bool device tensor, enqueued on `stream` without
+    synchronising.  Points the library calls invalid are outside."""
+    if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
+        p = np.asarray(points, dtype=np.float64)
+        p = p.reshape(-1, p.shape[-1])[:, :3]
+        p4 = np.concatenate([p, np.zeros((len(p), 1))], axis=1)
+        inside = scene.signed_distance(p4, want_prim=False, want_dist=False, want_point=False)[3]
+        return inside == 1
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise ValueError("inside_points: a device tensor of n x 3 or n x 4 %s values is needed" % scene.prec)
+    n = points.shape[0]
+    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    with torch.cuda.stream(st):
+        p4 = torch.zeros((n, 4), dtype=want, device=points.device)
+        p4[:, :3] = points[:, :3]
+        inside = torch.empty(n, dtype=torch.uint8, device=points.device)
+        scene.signed_distance_device(p4.data_ptr(), n, 0, 0, 0, inside.data_ptr(), st.cuda_stream)
+        p4.record_stream(st)
+        return inside == 1
+
+
+def distance_field(scene, lo, hi, dims, band=None, stream=None):
+    """A signed distance field: the grid of dims = (nx, ny, nz) cells over the box [lo, hi], each cell's CENTRE (voxel_boxes' arithmetic, made on the
+    scene's device with torch) answered by one spira_scene_signed_distance_device_* call on `stream` (a torch.cuda.Stream; None: the current one) with
+    r_max = band, or +Inf when band is None: negative inside, band (signed) where nothing lies within it.  Returns a device tensor [nx, ny, nz] in the
+    scene's precision without synchronising; cells the library calls invalid (beyond the origin rule) are NaN."""
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    T = np.float32 if scene.prec == "f32" else np.float64
+    dims = [int(d) for d in dims]
+    lo64, hi64 = np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)
+    half = ((hi64 - lo64) / (2.0 * np.asarray(dims, dtype=np.float64))).astype(T)
+    lo_t = lo64.astype(T)
+    dev = torch.device("cuda", torch.cuda.current_device())      # (a handle is resident on the current device)
+    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    n = dims[0] * dims[1] * dims[2]
+    with torch.cuda.stream(st):
+        cs = []
+        for k in range(3):
+            odd = (2 * torch.arange(dims[k], device=dev) + 1).to(want)
+            cs.append(torch.tensor(lo_t[k], dtype=want, device=dev) + odd * torch.tensor(half[k], dtype=want, device=dev))
+        pts = torch.empty((dims[0], dims[1], dims[2], 4), dtype=want, device=dev)
+        pts[..., 0] = cs[0][:, None, None]
+        pts[..., 1] = cs[1][None, :, None]
+        pts[..., 2] = cs[2][None, None, :]
+        pts[..., 3] = float("inf") if band is None else float(T(band))
+        pts = pts.reshape(n, 4)
+        dist = torch.empty(n, dtype=want, device=dev)
+        inside = torch.empty(n, dtype=torch.uint8, device=dev)
+        scene.signed_distance_device(pts.data_ptr(), n, 0, dist.data_ptr(), 0, inside.data_ptr(), st.cuda_stream)
+        pts.record_stream(st)
+        field = torch.where(inside == 255, torch.full_like(dist, float("nan")), dist)
+        return field.reshape(dims[0], dims[1], dims[2])
