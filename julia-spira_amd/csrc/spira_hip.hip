@@ -1509,9 +1509,10 @@ int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, 
 
 SPIRA_ENTRY(features_entry, features_impl)
 
-// ======================================================================= the list calls on a scene handle: what cast, closest point, radiance and the gathers share
-// Each answers a caller's list (rays or points) entry by entry.  Written once for all of them: the opening, the staging of a host caller's arrays, the
-// pass loop of the calls that split their samples, and the two choices of a kernel by the scene's shape.  The counters of the last render are left as they are.
+// ======================================================================= the list calls on a scene handle: what the queries, radiance and the gathers share
+// Each answers a caller's list (rays, points, sweeps or boxes) entry by entry.  Written once for all of them: the opening, the staging of a host caller's
+// arrays, the pass loop of the calls that split their samples, the two choices of a kernel by the scene's shape, and the whole call of a query that is
+// one launch (list_query_call).  The counters of the last render are left as they are.
 template <class T>
 int open_list_call(Session &s, const spira_scene *h, bool on_device, void *user_stream, spira::SceneGlobal<T> &g) {
     if (int rc = check_handle<T>(h)) return rc;
@@ -1521,22 +1522,30 @@ int open_list_call(Session &s, const spira_scene *h, bool on_device, void *user_
     return 0;
 }
 
-// The arrays of a list call.  Device form: the caller's pointers pass through, no buffer of the context is touched and nothing is allocated.  Host form: the
-// blocks lie back to back in the context's list_io in the order given — a NULL block keeps its place and stays NULL, so every block starts where the
-// entry's layout comment says — stage_in copies the kStageIn ones in, stage_out (after the launches) copies the kStageOut ones back, in the order given.
+// The arrays of a list call.  A block names the caller's array, its size, its direction and the pointer field of the call's Args that the kernels read it
+// through; stage_in fills that field, so no entry binds a staged address by its place in a table.  Device form: the caller's pointers pass through, no
+// buffer of the context is touched and nothing is allocated.  Host form: the blocks lie in the context's list_io in the order given, each at a multiple
+// of 16 bytes from its base (spira::stage_layout; list_io comes from hipMalloc), a NULL block taking no room and staying NULL — stage_in copies the
+// kStageIn ones in, stage_out (after the launches) copies the kStageOut ones back, in the order given.
 enum : unsigned { kStageIn = 1, kStageOut = 2 };
-struct StageBlock { void *host; size_t bytes; unsigned dir; void *dev; };
+struct StageBlock {
+    void *host; size_t bytes; unsigned dir;
+    void *slot;      // the P * field of the Args
+    void *dev = nullptr;
+    template <class P>
+    StageBlock(P *&field, P *array, size_t bytes_, unsigned dir_) : host((void *)array), bytes(bytes_), dir(dir_), slot(&field) {}
+    void bind(void *d) { dev = d; std::memcpy(slot, &d, sizeof d); }
+};
 template <int N>
 int stage_in(Session &s, StageBlock (&b)[N]) {
-    if (!s.host_out) { for (StageBlock &k : b) k.dev = k.host; return 0; }
-    size_t total = 0;
-    for (const StageBlock &k : b) total += k.bytes;
-    if (int rc = s.cp->list_io.ensure(total)) return rc;
-    char *at = (char *)s.cp->list_io.p;
-    for (StageBlock &k : b) {
-        k.dev = k.host ? at : nullptr;
-        if (k.host && (k.dir & kStageIn)) HIP_TRY(hipMemcpyAsync(at, k.host, k.bytes, hipMemcpyHostToDevice, s.st));
-        at += k.bytes;
+    if (!s.host_out) { for (StageBlock &k : b) k.bind(k.host); return 0; }
+    size_t bytes[N], at[N];
+    bool present[N];
+    for (int k = 0; k < N; ++k) { bytes[k] = b[k].bytes; present[k] = b[k].host != nullptr; }
+    if (int rc = s.cp->list_io.ensure(spira::stage_layout(bytes, present, N, at))) return rc;
+    for (int k = 0; k < N; ++k) {
+        b[k].bind(present[k] ? (char *)s.cp->list_io.p + at[k] : nullptr);
+        if (present[k] && (b[k].dir & kStageIn)) HIP_TRY(hipMemcpyAsync(b[k].dev, b[k].host, b[k].bytes, hipMemcpyHostToDevice, s.st));
     }
     return 0;
 }
@@ -1578,6 +1587,28 @@ int launch_list(const ListKernels<A> &k, const spira::CastPlan &cp, bool inplace
         return launch_lds(k.session, dim3(cp.grid), block, lds + (k.lds_stack ? (size_t)spira::kCastLdsStack * 64 * sizeof(uint32_t) * cp.wpb : 0), st, a);
     return launch_lds(a.scene.n_bvh_tris ? k.tree : a.scene.n_triangles ? k.tri : k.spheres, flat, block, lds, st, a);
 }
+spira::CastKnobs read_cast_knobs() {
+    spira::CastKnobs k;
+    k.refill = env_u32("SPIRA_CAST_REFILL", SPIRA_CAST_REFILL);
+    k.waves_per_cu = env_u32("SPIRA_CAST_WAVES_PER_CU", SPIRA_CAST_WAVES_PER_CU);
+    return k;
+}
+// A query answered by one launch over the caller's n items (cast, closest point, multi-hit, K-nearest, sweep, box overlap, signed distance), once its
+// entry has checked the arguments — so an argument error needs no device —, chosen the kernels, set the fields of `a` that are its own and listed the
+// arrays: the session, the launch arithmetic (make_cast_plan; base, rem and refill_free have these names in every Args), the staging, the launch.  The
+// device form touches no workspace of the context (it allocates nothing); the host form stages the blocks of io.
+template <class T, class A, int N>
+int list_query_call(const spira_scene *h, uint32_t n, uint32_t flags, bool on_device, void *user_stream, A &a, StageBlock (&io)[N], const ListKernels<A> &kernels) {
+    Session s;
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    const spira::CastPlan cp = spira::make_cast_plan(n, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
+    a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    if (int rc = stage_in(s, io)) return rc;
+    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
+    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
+    if (int rc = stage_out(s, io)) return rc;
+    return s.close();
+}
 // The kernels of a path loop, k[BVH][EXT]: a scene with a tree or without, the material extensions or not.
 template <class A>
 int launch_paths(void (*const (&k)[2][2])(A), dim3 grid, size_t lds, hipStream_t st, const A &a) {
@@ -1586,14 +1617,7 @@ int launch_paths(void (*const (&k)[2][2])(A), dim3 grid, size_t lds, hipStream_t
 }
 
 // ======================================================================= spira_scene_cast_* / spira_scene_occluded_*: the caller's rays against a handle
-// Kernels and the ray preparation: spira_query.h; launch arithmetic: spira_plan.h (make_cast_plan).  One launch.  The device form touches no workspace of
-// the context (it allocates nothing); the host form stages rays and outputs.
-spira::CastKnobs read_cast_knobs() {
-    spira::CastKnobs k;
-    k.refill = env_u32("SPIRA_CAST_REFILL", SPIRA_CAST_REFILL);
-    k.waves_per_cu = env_u32("SPIRA_CAST_WAVES_PER_CU", SPIRA_CAST_WAVES_PER_CU);
-    return k;
-}
+// Kernels and the ray preparation: spira_query.h; the call: list_query_call.
 template <class T>
 int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
               bool any, bool on_device, void *user_stream) {
@@ -1602,26 +1626,17 @@ int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t fl
     const ListKernels<A> occluded = {spira::k_cast_session<T, true>, spira::k_cast<T, true, false, true>, spira::k_cast<T, false, true, true>, spira::k_cast<T, false, false, true>, true};
     const char *msg = nullptr;
     if (int rc = spira::cast_check(rays8 != nullptr, n_rays, flags, any ? out_hit != nullptr : (out_prim || out_t || out_normal), &msg)) return fail(rc, msg);
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n_rays = n_rays; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.n_rays = n_rays;
     const size_t n = n_rays, t_b = n * sizeof(T);
-    // [rays | t | normal | prim | hit]: every block starts at a multiple of sizeof(T) or more
-    StageBlock io[] = {{(void *)rays8, 8 * t_b, kStageIn}, {out_t, t_b, kStageOut}, {out_normal, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut}, {out_hit, n, kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.rays = (const T *)io[0].dev; a.t = (T *)io[1].dev; a.normal = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.hit = (uint8_t *)io[4].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(any ? occluded : closest, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    StageBlock io[] = {{a.rays, rays8, 8 * t_b, kStageIn}, {a.t, out_t, t_b, kStageOut}, {a.normal, out_normal, 3 * t_b, kStageOut}, {a.prim, out_prim, n * sizeof(int), kStageOut},
+                       {a.hit, out_hit, n, kStageOut}};
+    return list_query_call<T>(h, n_rays, flags, on_device, user_stream, a, io, any ? occluded : closest);
 }
 SPIRA_ENTRY(cast_entry, cast_impl)
 
 // ======================================================================= spira_scene_closest_point_*: the nearest surface point for the caller's points
-// Kernels, the point preparation and the two closest-point functions: spira_nearest.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One
-// launch.  The device form touches no workspace of the context (it allocates nothing); the host form stages points and outputs.
+// Kernels, the point preparation and the two closest-point functions: spira_nearest.h; the call: list_query_call.
 template <class T>
 int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
                  bool on_device, void *user_stream) {
@@ -1629,28 +1644,18 @@ int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint
     const ListKernels<A> kernels = {spira::k_nearest_session<T>, spira::k_nearest<T, true, false>, spira::k_nearest<T, false, true>, spira::k_nearest<T, false, false>, false};
     const char *msg = nullptr;
     if (int rc = spira::nearest_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point, &msg)) return fail(rc, msg);
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.n_points = n_points;
     const size_t n = n_points, t_b = n * sizeof(T);
-    // [points | dist | point | prim | trips]: every block starts at a multiple of sizeof(T) or more
-    StageBlock io[] = {{(void *)points4, 4 * t_b, kStageIn}, {out_dist, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut},
-                       {out_trips, n * sizeof(uint32_t), kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.trips = (uint32_t *)io[4].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    StageBlock io[] = {{a.points, points4, 4 * t_b, kStageIn}, {a.dist, out_dist, t_b, kStageOut}, {a.point, out_point, 3 * t_b, kStageOut},
+                       {a.prim, out_prim, n * sizeof(int), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}};
+    return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
 SPIRA_ENTRY(nearest_entry, nearest_impl)
 
 // ======================================================================= spira_scene_cast_hits_*: the first max_hits hits of every ray, in order
-// Kernels, the list and the pruning argument: spira_hits.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels whose
-// list capacity (1, 4 or 16) is the smallest that holds max_hits.  The device form touches no workspace of the context (it allocates nothing); the host
-// form stages rays and outputs.
+// Kernels, the list and the pruning argument: spira_hits.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the smallest
+// that holds max_hits.
 template <class T, int CAP>
 ListKernels<spira::HitsArgs<T>> hits_kernels() {
     return {spira::k_hits_session<T, CAP>, spira::k_hits<T, true, false, CAP>, spira::k_hits<T, false, true, CAP>, spira::k_hits<T, false, false, CAP>, true};
@@ -1663,29 +1668,18 @@ int hits_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t ma
     if (max_hits == 0) { out_prim = nullptr; out_t = nullptr; }      // (count only: the lists have no slots)
     if (int rc = spira::hits_check(rays8 != nullptr, n_rays, max_hits, flags, out_prim || out_t || out_count, &msg)) return fail(rc, msg);
     const ListKernels<A> kernels = max_hits <= 1 ? hits_kernels<T, 1>() : max_hits <= 4 ? hits_kernels<T, 4>() : hits_kernels<T, 16>();
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_rays, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n_rays = n_rays; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
-    a.max_hits = max_hits; a.count_all = (flags & SPIRA_HITS_COUNT_ALL) ? 1u : 0u;
-    const size_t n = n_rays, slots = n * max_hits, prim_b = slots * sizeof(int);
-    // [rays | t | prim | pad | count]: every block starts at a multiple of sizeof(T) or more (pad: a NULL block that rounds prim up to 8 bytes)
-    StageBlock io[] = {{(void *)rays8, 8 * n * sizeof(T), kStageIn}, {out_t, slots * sizeof(T), kStageOut}, {out_prim, prim_b, kStageOut}, {nullptr, prim_b & 4, 0},
-                       {out_count, n * sizeof(uint32_t), kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.rays = (const T *)io[0].dev; a.t = (T *)io[1].dev; a.prim = (int *)io[2].dev; a.count = (uint32_t *)io[4].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    a.n_rays = n_rays; a.max_hits = max_hits; a.count_all = (flags & SPIRA_HITS_COUNT_ALL) ? 1u : 0u;
+    const size_t n = n_rays, slots = n * max_hits;
+    StageBlock io[] = {{a.rays, rays8, 8 * n * sizeof(T), kStageIn}, {a.t, out_t, slots * sizeof(T), kStageOut}, {a.prim, out_prim, slots * sizeof(int), kStageOut},
+                       {a.count, out_count, n * sizeof(uint32_t), kStageOut}};
+    return list_query_call<T>(h, n_rays, flags, on_device, user_stream, a, io, kernels);
 }
 SPIRA_ENTRY(hits_entry, hits_impl)
 
 // ======================================================================= spira_scene_nearest_k_*: the max_near closest objects of every point, in order
-// Kernels, the list and the pruning argument: spira_knearest.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels
-// whose list capacity (1, 4 or 16) is the smallest that holds max_near.  The device form touches no workspace of the context (it allocates nothing); the
-// host form stages points and outputs.
+// Kernels, the list and the pruning argument: spira_knearest.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the
+// smallest that holds max_near.
 template <class T, int CAP>
 ListKernels<spira::KNearArgs<T>> knear_kernels() {
     return {spira::k_knear_session<T, CAP>, spira::k_knear<T, true, false, CAP>, spira::k_knear<T, false, true, CAP>, spira::k_knear<T, false, false, CAP>, false};
@@ -1698,30 +1692,17 @@ int nearest_k_impl(const spira_scene *h, const T *points4, uint32_t n_points, ui
     if (max_near == 0) { out_prim = nullptr; out_dist = nullptr; out_point = nullptr; }      // (count only: the lists have no slots)
     if (int rc = spira::nearest_k_check(points4 != nullptr, n_points, max_near, flags, out_prim || out_dist || out_point || out_count, &msg)) return fail(rc, msg);
     const ListKernels<A> kernels = max_near <= 1 ? knear_kernels<T, 1>() : max_near <= 4 ? knear_kernels<T, 4>() : knear_kernels<T, 16>();
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
-    a.max_near = max_near; a.count_all = (flags & SPIRA_NEAR_COUNT_ALL) ? 1u : 0u;
-    const size_t n = n_points, slots = n * max_near, prim_b = slots * sizeof(int);
-    // [points | dist | point | prim | pad | count | trips]: every block starts at a multiple of sizeof(T) or more (pad: a NULL block that rounds prim up to
-    // 8 bytes; count and trips hold 4-byte values)
-    StageBlock io[] = {{(void *)points4, 4 * n * sizeof(T), kStageIn}, {out_dist, slots * sizeof(T), kStageOut}, {out_point, 3 * slots * sizeof(T), kStageOut},
-                       {out_prim, prim_b, kStageOut}, {nullptr, prim_b & 4, 0}, {out_count, n * sizeof(uint32_t), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.count = (uint32_t *)io[5].dev;
-    a.trips = (uint32_t *)io[6].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    a.n_points = n_points; a.max_near = max_near; a.count_all = (flags & SPIRA_NEAR_COUNT_ALL) ? 1u : 0u;
+    const size_t n = n_points, slots = n * max_near;
+    StageBlock io[] = {{a.points, points4, 4 * n * sizeof(T), kStageIn}, {a.dist, out_dist, slots * sizeof(T), kStageOut}, {a.point, out_point, 3 * slots * sizeof(T), kStageOut},
+                       {a.prim, out_prim, slots * sizeof(int), kStageOut}, {a.count, out_count, n * sizeof(uint32_t), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}};
+    return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
 SPIRA_ENTRY(nearest_k_entry, nearest_k_impl)
 
 // ======================================================================= spira_scene_sweep_* / spira_scene_sweep_blocked_*: the first contact of a moving ball
-// Kernels, the contract and the margin argument: spira_sweep.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch.  The device form
-// touches no workspace of the context (it allocates nothing); the host form stages rays, radii and outputs.
+// Kernels, the contract and the margin argument: spira_sweep.h; the call: list_query_call.
 template <class T>
 int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_sweeps, uint32_t flags, int *out_prim, T *out_t, T *out_point, T *out_normal,
                uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
@@ -1730,29 +1711,19 @@ int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_
     const ListKernels<A> blocked = {spira::k_sweep_session<T, true>, spira::k_sweep<T, true, false, true>, spira::k_sweep<T, false, true, true>, spira::k_sweep<T, false, false, true>, false};
     const char *msg = nullptr;
     if (int rc = spira::sweep_check(rays8 != nullptr, radii != nullptr, n_sweeps, flags, any ? out_hit != nullptr : (out_prim || out_t || out_point || out_normal), &msg)) return fail(rc, msg);
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_sweeps, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n = n_sweeps; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.n = n_sweeps;
     const size_t n = n_sweeps, t_b = n * sizeof(T);
-    // [rays | radii | t | point | normal | prim | trips | hit]: every block starts at a multiple of sizeof(T) or more, the 4-byte ones of 4
-    StageBlock io[] = {{(void *)rays8, 8 * t_b, kStageIn}, {(void *)radii, t_b, kStageIn}, {out_t, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_normal, 3 * t_b, kStageOut},
-                       {out_prim, n * sizeof(int), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}, {out_hit, n, kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.rays = (const T *)io[0].dev; a.radii = (const T *)io[1].dev; a.t = (T *)io[2].dev; a.point = (T *)io[3].dev; a.normal = (T *)io[4].dev; a.prim = (int *)io[5].dev;
-    a.trips = (uint32_t *)io[6].dev; a.hit = (uint8_t *)io[7].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(any ? blocked : first, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    StageBlock io[] = {{a.rays, rays8, 8 * t_b, kStageIn}, {a.radii, radii, t_b, kStageIn}, {a.t, out_t, t_b, kStageOut}, {a.point, out_point, 3 * t_b, kStageOut},
+                       {a.normal, out_normal, 3 * t_b, kStageOut}, {a.prim, out_prim, n * sizeof(int), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut},
+                       {a.hit, out_hit, n, kStageOut}};
+    return list_query_call<T>(h, n_sweeps, flags, on_device, user_stream, a, io, any ? blocked : first);
 }
 SPIRA_ENTRY(sweep_entry, sweep_impl)
 
 // ======================================================================= spira_scene_overlap_box_* / spira_scene_overlap_any_*: what touches an oriented box
-// Kernels, the contract and the margin argument: spira_overlap.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels
-// whose list capacity (1, 4 or 16) is the smallest that holds max_list.  The device form touches no workspace of the context (it allocates nothing); the
-// host form stages boxes and outputs.
+// Kernels, the contract and the margin argument: spira_overlap.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the
+// smallest that holds max_list.
 template <class T, bool ANY, int CAP>
 ListKernels<spira::OverlapArgs<T>> overlap_kernels() {
     return {spira::k_overlap_session<T, ANY, CAP>, spira::k_overlap<T, true, false, ANY, CAP>, spira::k_overlap<T, false, true, ANY, CAP>, spira::k_overlap<T, false, false, ANY, CAP>, false};
@@ -1767,28 +1738,18 @@ int overlap_impl(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint3
     if (int rc = spira::overlap_check(boxes10 != nullptr, n_boxes, max_list, flags, any ? out_hit != nullptr : (out_prim || out_count), &msg)) return fail(rc, msg);
     const ListKernels<A> kernels = any ? overlap_kernels<T, true, 1>()
                                        : max_list <= 1 ? overlap_kernels<T, false, 1>() : max_list <= 4 ? overlap_kernels<T, false, 4>() : overlap_kernels<T, false, 16>();
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_boxes, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n = n_boxes; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free; a.max_list = max_list;
+    a.n = n_boxes; a.max_list = max_list;
     const size_t n = n_boxes, slots = n * max_list;
-    // [boxes | prim | count | trips | hit]: the boxes start at a multiple of sizeof(T) or more, the 4-byte blocks of 4
-    StageBlock io[] = {{(void *)boxes10, 10 * n * sizeof(T), kStageIn}, {out_prim, slots * sizeof(int), kStageOut}, {out_count, n * sizeof(uint32_t), kStageOut},
-                       {out_trips, n * sizeof(uint32_t), kStageOut}, {out_hit, n, kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.boxes = (const T *)io[0].dev; a.prim = (int *)io[1].dev; a.count = (uint32_t *)io[2].dev; a.trips = (uint32_t *)io[3].dev; a.hit = (uint8_t *)io[4].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    StageBlock io[] = {{a.boxes, boxes10, 10 * n * sizeof(T), kStageIn}, {a.prim, out_prim, slots * sizeof(int), kStageOut}, {a.count, out_count, n * sizeof(uint32_t), kStageOut},
+                       {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}, {a.hit, out_hit, n, kStageOut}};
+    return list_query_call<T>(h, n_boxes, flags, on_device, user_stream, a, io, kernels);
 }
 SPIRA_ENTRY(overlap_entry, overlap_impl)
 
 // ======================================================================= spira_scene_signed_distance_*: the nearest surface of every point and which side of it
-// Kernels and the contract: spira_sdf.h; launch arithmetic: make_cast_plan, with the knobs cast reads.  One launch, of the kernels with or without the nearest
-// walk (out_prim, out_dist and out_point all NULL: the sign-only query).  The device form touches no workspace of the context (it allocates nothing); the
-// host form stages points and outputs.
+// Kernels and the contract: spira_sdf.h; the call: list_query_call, with the kernels with or without the nearest walk (out_prim, out_dist and out_point
+// all NULL: the sign-only query).
 static_assert(spira::kSdfSkipped == SPIRA_SDF_SKIPPED, "spira_sdf.h and the header disagree on SPIRA_SDF_SKIPPED");
 template <class T, bool NEAR>
 ListKernels<spira::SdfArgs<T>> sdf_kernels() {
@@ -1801,22 +1762,12 @@ int signed_distance_impl(const spira_scene *h, const T *points4, uint32_t n_poin
     const char *msg = nullptr;
     if (int rc = spira::signed_distance_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point || out_inside || out_crossings, &msg)) return fail(rc, msg);
     const ListKernels<A> kernels = spira::signed_distance_wants_nearest(out_prim, out_dist, out_point) ? sdf_kernels<T, true>() : sdf_kernels<T, false>();
-    Session s;
     A a{};
-    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
-    const spira::CastPlan cp = spira::make_cast_plan(n_points, (uint32_t)s.cp->num_cus, spira::kBlock, read_cast_knobs());
-    a.n_points = n_points; a.base = cp.base; a.rem = cp.rem; a.refill_free = cp.refill_free;
+    a.n_points = n_points;
     const size_t n = n_points, t_b = n * sizeof(T);
-    // [points | dist | point | prim | crossings | trips | inside]: every block starts at a multiple of its element size or more
-    StageBlock io[] = {{(void *)points4, 4 * t_b, kStageIn}, {out_dist, t_b, kStageOut}, {out_point, 3 * t_b, kStageOut}, {out_prim, n * sizeof(int), kStageOut},
-                       {out_crossings, 3 * n * sizeof(uint32_t), kStageOut}, {out_trips, n * sizeof(uint32_t), kStageOut}, {out_inside, n, kStageOut}};
-    if (int rc = stage_in(s, io)) return rc;
-    a.points = (const T *)io[0].dev; a.dist = (T *)io[1].dev; a.point = (T *)io[2].dev; a.prim = (int *)io[3].dev; a.crossings = (uint32_t *)io[4].dev;
-    a.trips = (uint32_t *)io[5].dev; a.inside = (uint8_t *)io[6].dev;
-    const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
-    if (int rc = launch_list(kernels, cp, (flags & SPIRA_CAST_INPLACE) != 0, lds, s.st, a)) return rc;
-    if (int rc = stage_out(s, io)) return rc;
-    return s.close();
+    StageBlock io[] = {{a.points, points4, 4 * t_b, kStageIn}, {a.dist, out_dist, t_b, kStageOut}, {a.point, out_point, 3 * t_b, kStageOut}, {a.prim, out_prim, n * sizeof(int), kStageOut},
+                       {a.crossings, out_crossings, 3 * n * sizeof(uint32_t), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}, {a.inside, out_inside, n, kStageOut}};
+    return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
 SPIRA_ENTRY(signed_distance_entry, signed_distance_impl)
 
@@ -1831,9 +1782,9 @@ spira::RadianceKnobs read_radiance_knobs() {
     return k;
 }
 // What radiance_impl and gather_impl do with their Args (RadianceArgs, GatherArgs) once the list's own two fields are set: the path constants, the
-// workspace, the staged list / sums / valid bytes, the passes.  list, n: the caller's rays or points (six values each) and where Args keeps the staged pointer.
+// workspace, the staged list / sums / valid bytes, the passes.  list: the block of the caller's n rays or points (six values each).
 template <class T, class A>
-int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radiance *rp, A &a, const T *list, const T *A::*staged, uint32_t n, T *sum_rgb, uint8_t *out_valid,
+int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radiance *rp, A &a, const StageBlock &list, uint32_t n, T *sum_rgb, uint8_t *out_valid,
                    void (*const (&paths)[2][2])(A), void (*sum)(A)) {
     Ctx &c = *s.cp;
     if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
@@ -1843,10 +1794,8 @@ int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radian
     a.key0 = rp->key0;
     a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
     const size_t sum_b = 3 * (size_t)n * sizeof(T);
-    // [rays or points | sums | valid]: every block starts at a multiple of sizeof(T)
-    StageBlock io[] = {{(void *)list, 2 * sum_b, kStageIn}, {sum_rgb, sum_b, kStageIn | kStageOut}, {out_valid, n, kStageOut}};
+    StageBlock io[] = {list, {a.sum, sum_rgb, sum_b, kStageIn | kStageOut}, {a.valid, out_valid, n, kStageOut}};
     if (int rc = stage_in(s, io)) return rc;
-    a.*staged = (const T *)io[0].dev; a.sum = (T *)io[1].dev; a.valid = (uint8_t *)io[2].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
     if (int rc = run_passes(pl, rp->sample0, a.ws ? c.L.cap / sizeof(spira::Pack3<T>) : ~0ull, a, [&]() -> int {
             if (int rc2 = launch_paths(paths, dim3(pl.grid), lds, s.st, a)) return rc2;
@@ -1868,7 +1817,7 @@ int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const s
     if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
     a.n_rays = n_rays;
     const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_radiance_knobs());
-    return path_list_call<T>(s, pl, rp, a, rays6, &A::rays, n_rays, sum_rgb, out_valid, paths, spira::k_radiance_sum<T>);
+    return path_list_call<T>(s, pl, rp, a, {a.rays, rays6, 6 * (size_t)n_rays * sizeof(T), kStageIn}, n_rays, sum_rgb, out_valid, paths, spira::k_radiance_sum<T>);
 }
 SPIRA_ENTRY(radiance_entry, radiance_impl)
 
@@ -1927,7 +1876,7 @@ int gather_impl(const spira_scene *h, const T *points6, uint32_t n_points, const
     if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
     a.n_points = n_points;
     const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_gather_knobs());
-    return path_list_call<T>(s, pl, rp, a, points6, &A::points, n_points, sum_rgb, out_valid, paths, spira::k_gather_sum<T>);
+    return path_list_call<T>(s, pl, rp, a, {a.points, points6, 6 * (size_t)n_points * sizeof(T), kStageIn}, n_points, sum_rgb, out_valid, paths, spira::k_gather_sum<T>);
 }
 SPIRA_ENTRY(gather_entry, gather_impl)
 
@@ -1950,10 +1899,8 @@ int gather_visible_impl(const spira_scene *h, const T *points6, uint32_t n_point
     a.n_points = n_points; a.key0 = gv->key0;
     a.t_min = (T)gv->t_min; a.t_max = (T)gv->t_max;
     const size_t n = n_points;
-    // [points | counts | valid]: every block starts at a multiple of 4
-    StageBlock io[] = {{(void *)points6, 6 * n * sizeof(T), kStageIn}, {visible, n * sizeof(uint32_t), kStageIn | kStageOut}, {out_valid, n, kStageOut}};
+    StageBlock io[] = {{a.points, points6, 6 * n * sizeof(T), kStageIn}, {a.visible, visible, n * sizeof(uint32_t), kStageIn | kStageOut}, {a.valid, out_valid, n, kStageOut}};
     if (int rc = stage_in(s, io)) return rc;
-    a.points = (const T *)io[0].dev; a.visible = (uint32_t *)io[1].dev; a.valid = (uint8_t *)io[2].dev;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
     const bool inplace = (gv->flags & SPIRA_CAST_INPLACE) != 0;
     if (int rc = run_passes(pl, gv->sample0, ~0ull, a, [&]() -> int {

@@ -4,6 +4,7 @@
 // workspaces from Plan::ws and hands the plan to the organisation's enqueue function; verify_path_args() takes path_need() for its numbers.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/spira_hip.h"
@@ -467,6 +468,20 @@ inline CastPlan make_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t block
     p.refill_free = std::min<uint32_t>(64, std::max<uint32_t>(1, k.refill));
     p.grid_flat = features_grid(n_rays, block, num_cus);
     return p;
+}
+
+// ---- the arrays of a host-form list call (stage_in; spira_hip.hip): where each block lies in the context's staging buffer.  The blocks keep their
+// order; a present block starts at the next multiple of kStageAlign at or after the end of the present block before it — enough for every element type
+// of the entries, whatever sizes precede it — and a block that is not present (a NULL array of the caller) takes no room.  offset[k] is written for
+// every block (for one not present: where the next present one starts); returns the bytes the buffer must hold, the end of the last present block.
+constexpr size_t kStageAlign = 16;
+inline size_t stage_layout(const size_t *bytes, const bool *present, int n, size_t *offset) {
+    size_t end = 0;
+    for (int k = 0; k < n; ++k) {
+        offset[k] = (end + (kStageAlign - 1)) & ~(kStageAlign - 1);
+        if (present[k]) end = offset[k] + bytes[k];
+    }
+    return end;
 }
 
 // ---- radiance along the caller's rays (spira_scene_radiance_*) and the camera ray generator (spira_camera_rays_*); kernels in spira_radiance.h.

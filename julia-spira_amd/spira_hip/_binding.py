@@ -438,12 +438,38 @@ class Scene:
         _check(fn(self._h, cp, C.byref(params), C.c_void_p(d_albedo_ptr or None), C.c_void_p(d_normal_ptr or None), C.c_void_p(d_depth_ptr or None),
                   C.c_void_p(stream_ptr or None)))
 
+    def _fn(self, stem, device=False):
+        """The entry spira_scene_<stem>[_device]_<prec> of this handle's precision."""
+        return getattr(lib(), "spira_scene_" + stem + ("_device_" if device else "_") + self.prec)
+
+    @staticmethod
+    def _ptrs(device, arrays):
+        """The void * arguments of a call: integer device addresses (0 / None: NULL), or host arrays (numpy; None: NULL)."""
+        if device:
+            return map(C.c_void_p, arrays)
+        return [None if a is None else a.ctypes.data_as(C.c_void_p) for a in arrays]
+
+    @staticmethod
+    def _flags(inplace, count_all=0):
+        """The flag word of a query: CAST_INPLACE, and the count-all bit of the entries that have one."""
+        return C.c_uint32((CAST_INPLACE if inplace else 0) | count_all)
+
+    def _query(self, stem, device, ins, counts, word, outs):
+        """One list call: (handle, input arrays, the uint32 counts, the flag word or the parameter struct by reference, output arrays [, stream]); the
+        device form takes addresses."""
+        _check(self._fn(stem, device)(self._h, *self._ptrs(device, ins), *map(C.c_uint32, counts), word, *self._ptrs(device, outs)))
+
+    def _list(self, a, width, what):
+        a = np.ascontiguousarray(a, dtype=_dt(self.prec)[0])
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError(what)
+        return a
+
     def _rays(self, rays8):
-        npdt, _ = _dt(self.prec)
-        r = np.ascontiguousarray(rays8, dtype=npdt)
-        if r.ndim != 2 or r.shape[1] != 8:
-            raise ValueError("rays8: n_rays x [ox oy oz t_min dx dy dz t_max]")
-        return r
+        return self._list(rays8, 8, "rays8: n_rays x [ox oy oz t_min dx dy dz t_max]")
+
+    def _points4(self, points4):
+        return self._list(points4, 4, "points4: n_points x [px py pz r_max]")
 
     def cast(self, rays8, want_normal=False, inplace=False, want_prim=True, want_t=True):
         """spira_scene_cast_*: the closest hit of every ray of rays8 (n x [ox oy oz t_min dx dy dz t_max], host array; directions are normalised by the
@@ -455,30 +481,23 @@ class Scene:
         prim = np.empty(n, dtype=np.int32) if want_prim else None
         t = np.empty(n, dtype=npdt) if want_t else None
         nrm = np.empty((n, 3), dtype=npdt) if want_normal else None
-        fn = lib().spira_scene_cast_f32 if self.prec == "f32" else lib().spira_scene_cast_f64
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, nrm)]))
+        self._query("cast", False, (r,), (n,), self._flags(inplace), (prim, t, nrm))
         return prim, t, nrm
 
     def occluded(self, rays8, inplace=False):
         """spira_scene_occluded_*: uint8 [n] — 1 where the ray hits anything within [t_min, t_max], 0 where not, 255 for an invalid ray."""
         r = self._rays(rays8)
         hit = np.empty(len(r), dtype=np.uint8)
-        fn = lib().spira_scene_occluded_f32 if self.prec == "f32" else lib().spira_scene_occluded_f64
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)), C.c_uint32(CAST_INPLACE if inplace else 0), hit.ctypes.data_as(C.c_void_p)))
+        self._query("occluded", False, (r,), (len(r),), self._flags(inplace), (hit,))
         return hit
 
     def cast_device(self, d_rays_ptr, n_rays, d_prim_ptr, d_t_ptr, d_normal_ptr, stream_ptr, inplace=False):
         """spira_scene_cast_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or allocated."""
-        fn = lib().spira_scene_cast_device_f32 if self.prec == "f32" else lib().spira_scene_cast_device_f64
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
-                  C.c_void_p(d_t_ptr or None), C.c_void_p(d_normal_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("cast", True, (d_rays_ptr,), (n_rays,), self._flags(inplace), (d_prim_ptr, d_t_ptr, d_normal_ptr, stream_ptr))
 
     def occluded_device(self, d_rays_ptr, n_rays, d_hit_ptr, stream_ptr, inplace=False):
         """spira_scene_occluded_device_*: DEVICE addresses, asynchronous on the stream."""
-        fn = lib().spira_scene_occluded_device_f32 if self.prec == "f32" else lib().spira_scene_occluded_device_f64
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("occluded", True, (d_rays_ptr,), (n_rays,), self._flags(inplace), (d_hit_ptr, stream_ptr))
 
     def cast_hits(self, rays8, max_hits, inplace=False, count_all=False, want_prim=True, want_t=True, want_count=True):
         """spira_scene_cast_hits_*: the first max_hits hits of every ray of rays8 (host array, as for cast), ordered by t ascending and, among equal t, by
@@ -492,44 +511,33 @@ class Scene:
         prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
         t = np.empty((n, room), dtype=npdt) if want_t and k else None
         count = np.empty(n, dtype=np.uint32) if want_count else None
-        fn = lib().spira_scene_cast_hits_f32 if self.prec == "f32" else lib().spira_scene_cast_hits_f64
-        flags = (CAST_INPLACE if inplace else 0) | (HITS_COUNT_ALL if count_all else 0)
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(flags),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, count)]))
+        self._query("cast_hits", False, (r,), (n, k), self._flags(inplace, HITS_COUNT_ALL if count_all else 0), (prim, t, count))
         return prim, t, count
 
     def cast_hits_device(self, d_rays_ptr, n_rays, max_hits, d_prim_ptr, d_t_ptr, d_count_ptr, stream_ptr, inplace=False, count_all=False):
         """spira_scene_cast_hits_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
         allocated."""
-        fn = lib().spira_scene_cast_hits_device_f32 if self.prec == "f32" else lib().spira_scene_cast_hits_device_f64
-        flags = (CAST_INPLACE if inplace else 0) | (HITS_COUNT_ALL if count_all else 0)
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.c_uint32(max_hits), C.c_uint32(flags), C.c_void_p(d_prim_ptr or None),
-                  C.c_void_p(d_t_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("cast_hits", True, (d_rays_ptr,), (n_rays, max_hits), self._flags(inplace, HITS_COUNT_ALL if count_all else 0),
+                    (d_prim_ptr, d_t_ptr, d_count_ptr, stream_ptr))
 
     def closest_point(self, points4, inplace=False, want_prim=True, want_dist=True, want_point=True, want_trips=False):
         """spira_scene_closest_point_*: for every point of points4 (n x [px py pz r_max], host array) the nearest point of the scene's surface within r_max.
         Returns (prim int32 [n], dist [n], point [n, 3], trips uint32 [n]), None where not wanted: prim is the object index (spheres first), RAY_MISS
         (dist = the point's r_max, point 0) or RAY_INVALID (dist 0, point 0).  inplace: the comparison organisation."""
         npdt, _ = _dt(self.prec)
-        p = np.ascontiguousarray(points4, dtype=npdt)
-        if p.ndim != 2 or p.shape[1] != 4:
-            raise ValueError("points4: n_points x [px py pz r_max]")
+        p = self._points4(points4)
         n = len(p)
         prim = np.empty(n, dtype=np.int32) if want_prim else None
         dist = np.empty(n, dtype=npdt) if want_dist else None
         point = np.empty((n, 3), dtype=npdt) if want_point else None
         trips = np.empty(n, dtype=np.uint32) if want_trips else None
-        fn = lib().spira_scene_closest_point_f32 if self.prec == "f32" else lib().spira_scene_closest_point_f64
-        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, trips)]))
+        self._query("closest_point", False, (p,), (n,), self._flags(inplace), (prim, dist, point, trips))
         return prim, dist, point, trips
 
     def closest_point_device(self, d_points_ptr, n_points, d_prim_ptr, d_dist_ptr, d_point_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
         """spira_scene_closest_point_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
         allocated."""
-        fn = lib().spira_scene_closest_point_device_f32 if self.prec == "f32" else lib().spira_scene_closest_point_device_f64
-        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
-                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("closest_point", True, (d_points_ptr,), (n_points,), self._flags(inplace), (d_prim_ptr, d_dist_ptr, d_point_ptr, d_trips_ptr, stream_ptr))
 
     def nearest_k(self, points4, max_near, inplace=False, count_all=False, want_prim=True, want_dist=True, want_point=True, want_count=True, want_trips=False):
         """spira_scene_nearest_k_*: the max_near closest objects of every point of points4 (host array, as for closest_point), ordered by squared distance
@@ -538,9 +546,7 @@ class Scene:
         slot of an invalid point RAY_INVALID, 0 and 0.  count: the slots filled, or with count_all every object within r_max (the walk then prunes with
         r_max only; max_near may be 0).  inplace: the comparison organisation."""
         npdt, _ = _dt(self.prec)
-        p = np.ascontiguousarray(points4, dtype=npdt)
-        if p.ndim != 2 or p.shape[1] != 4:
-            raise ValueError("points4: n_points x [px py pz r_max]")
+        p = self._points4(points4)
         n, k = len(p), int(max_near)
         room = k if 0 < k <= MAX_NEAR else 1      # (a refused max_near: the entry says so)
         prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
@@ -548,21 +554,15 @@ class Scene:
         point = np.empty((n, room, 3), dtype=npdt) if want_point and k else None
         count = np.empty(n, dtype=np.uint32) if want_count else None
         trips = np.empty(n, dtype=np.uint32) if want_trips else None
-        fn = lib().spira_scene_nearest_k_f32 if self.prec == "f32" else lib().spira_scene_nearest_k_f64
-        flags = (CAST_INPLACE if inplace else 0) | (NEAR_COUNT_ALL if count_all else 0)
-        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(flags),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, count, trips)]))
+        self._query("nearest_k", False, (p,), (n, k), self._flags(inplace, NEAR_COUNT_ALL if count_all else 0), (prim, dist, point, count, trips))
         return prim, dist, point, count, trips
 
     def nearest_k_device(self, d_points_ptr, n_points, max_near, d_prim_ptr, d_dist_ptr, d_point_ptr, d_count_ptr, stream_ptr, inplace=False, count_all=False,
                          d_trips_ptr=0):
         """spira_scene_nearest_k_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
         allocated."""
-        fn = lib().spira_scene_nearest_k_device_f32 if self.prec == "f32" else lib().spira_scene_nearest_k_device_f64
-        flags = (CAST_INPLACE if inplace else 0) | (NEAR_COUNT_ALL if count_all else 0)
-        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(max_near), C.c_uint32(flags), C.c_void_p(d_prim_ptr or None),
-                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(d_trips_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("nearest_k", True, (d_points_ptr,), (n_points, max_near), self._flags(inplace, NEAR_COUNT_ALL if count_all else 0),
+                    (d_prim_ptr, d_dist_ptr, d_point_ptr, d_count_ptr, d_trips_ptr, stream_ptr))
 
     def _sweeps(self, rays8, radii):
         npdt, _ = _dt(self.prec)
@@ -585,39 +585,26 @@ class Scene:
         point = np.empty((n, 3), dtype=npdt) if want_point else None
         nrm = np.empty((n, 3), dtype=npdt) if want_normal else None
         trips = np.empty(n, dtype=np.uint32) if want_trips else None
-        fn = lib().spira_scene_sweep_f32 if self.prec == "f32" else lib().spira_scene_sweep_f64
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, t, point, nrm, trips)]))
+        self._query("sweep", False, (r, rad), (n,), self._flags(inplace), (prim, t, point, nrm, trips))
         return prim, t, point, nrm, trips
 
     def sweep_blocked(self, rays8, radii, inplace=False):
         """spira_scene_sweep_blocked_*: uint8 [n] — 1 where the ball touches anything within [t_min, t_max], 0 where not, 255 for an invalid sweep."""
         r, rad = self._sweeps(rays8, radii)
         hit = np.empty(len(r), dtype=np.uint8)
-        fn = lib().spira_scene_sweep_blocked_f32 if self.prec == "f32" else lib().spira_scene_sweep_blocked_f64
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), rad.ctypes.data_as(C.c_void_p), C.c_uint32(len(r)), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  hit.ctypes.data_as(C.c_void_p)))
+        self._query("sweep_blocked", False, (r, rad), (len(r),), self._flags(inplace), (hit,))
         return hit
 
     def sweep_device(self, d_rays_ptr, d_radii_ptr, n, d_prim_ptr, d_t_ptr, d_point_ptr, d_normal_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
         """spira_scene_sweep_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or allocated."""
-        fn = lib().spira_scene_sweep_device_f32 if self.prec == "f32" else lib().spira_scene_sweep_device_f64
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_void_p(d_radii_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  C.c_void_p(d_prim_ptr or None), C.c_void_p(d_t_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_normal_ptr or None),
-                  C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("sweep", True, (d_rays_ptr, d_radii_ptr), (n,), self._flags(inplace), (d_prim_ptr, d_t_ptr, d_point_ptr, d_normal_ptr, d_trips_ptr, stream_ptr))
 
     def sweep_blocked_device(self, d_rays_ptr, d_radii_ptr, n, d_hit_ptr, stream_ptr, inplace=False):
         """spira_scene_sweep_blocked_device_*: DEVICE addresses, asynchronous on the stream."""
-        fn = lib().spira_scene_sweep_blocked_device_f32 if self.prec == "f32" else lib().spira_scene_sweep_blocked_device_f64
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_void_p(d_radii_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  C.c_void_p(d_hit_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("sweep_blocked", True, (d_rays_ptr, d_radii_ptr), (n,), self._flags(inplace), (d_hit_ptr, stream_ptr))
 
     def _boxes(self, boxes10):
-        npdt, _ = _dt(self.prec)
-        b = np.ascontiguousarray(boxes10, dtype=npdt)
-        if b.ndim != 2 or b.shape[1] != 10:
-            raise ValueError("boxes10: n x [cx cy cz hx hy hz qx qy qz qw]")
-        return b
+        return self._list(boxes10, 10, "boxes10: n x [cx cy cz hx hy hz qx qy qz qw]")
 
     def overlap_box(self, boxes10, max_list, inplace=False, want_prim=True, want_count=True, want_trips=False):
         """spira_scene_overlap_box_*: the objects that touch each oriented box of boxes10 (host array, n x [cx cy cz hx hy hz qx qy qz qw]; the library
@@ -630,31 +617,24 @@ class Scene:
         prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
         count = np.empty(n, dtype=np.uint32) if want_count else None
         trips = np.empty(n, dtype=np.uint32) if want_trips else None
-        fn = lib().spira_scene_overlap_box_f32 if self.prec == "f32" else lib().spira_scene_overlap_box_f64
-        _check(fn(self._h, b.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(k), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, count, trips)]))
+        self._query("overlap_box", False, (b,), (n, k), self._flags(inplace), (prim, count, trips))
         return prim, count, trips
 
     def overlap_any(self, boxes10, inplace=False):
         """spira_scene_overlap_any_*: uint8 [n] — 1 where anything touches the box, 0 where nothing does, 255 for an invalid box."""
         b = self._boxes(boxes10)
         hit = np.empty(len(b), dtype=np.uint8)
-        fn = lib().spira_scene_overlap_any_f32 if self.prec == "f32" else lib().spira_scene_overlap_any_f64
-        _check(fn(self._h, b.ctypes.data_as(C.c_void_p), C.c_uint32(len(b)), C.c_uint32(CAST_INPLACE if inplace else 0), hit.ctypes.data_as(C.c_void_p)))
+        self._query("overlap_any", False, (b,), (len(b),), self._flags(inplace), (hit,))
         return hit
 
     def overlap_box_device(self, d_boxes_ptr, n, max_list, d_prim_ptr, d_count_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
         """spira_scene_overlap_box_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
         allocated."""
-        fn = lib().spira_scene_overlap_box_device_f32 if self.prec == "f32" else lib().spira_scene_overlap_box_device_f64
-        _check(fn(self._h, C.c_void_p(d_boxes_ptr or None), C.c_uint32(n), C.c_uint32(max_list), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  C.c_void_p(d_prim_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("overlap_box", True, (d_boxes_ptr,), (n, max_list), self._flags(inplace), (d_prim_ptr, d_count_ptr, d_trips_ptr, stream_ptr))
 
     def overlap_any_device(self, d_boxes_ptr, n, d_hit_ptr, stream_ptr, inplace=False):
         """spira_scene_overlap_any_device_*: DEVICE addresses, asynchronous on the stream."""
-        fn = lib().spira_scene_overlap_any_device_f32 if self.prec == "f32" else lib().spira_scene_overlap_any_device_f64
-        _check(fn(self._h, C.c_void_p(d_boxes_ptr or None), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_hit_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("overlap_any", True, (d_boxes_ptr,), (n,), self._flags(inplace), (d_hit_ptr, stream_ptr))
 
     def signed_distance(self, points4, inplace=False, want_point=True, want_crossings=False, want_trips=False, want_prim=True, want_dist=True, want_inside=True):
         """spira_scene_signed_distance_*: for every point of points4 (host array, as for closest_point) the nearest surface and which side of it the point is
@@ -663,9 +643,7 @@ class Scene:
         crossings the triangle candidates of the three rays (SDF_SKIPPED: ray not walked).  With prim, dist and point all unwanted the nearest walk is not
         run (the sign-only query).  inplace: the comparison organisation."""
         npdt, _ = _dt(self.prec)
-        p = np.ascontiguousarray(points4, dtype=npdt)
-        if p.ndim != 2 or p.shape[1] != 4:
-            raise ValueError("points4: n_points x [px py pz r_max]")
+        p = self._points4(points4)
         n = len(p)
         prim = np.empty(n, dtype=np.int32) if want_prim else None
         dist = np.empty(n, dtype=npdt) if want_dist else None
@@ -673,28 +651,22 @@ class Scene:
         inside = np.empty(n, dtype=np.uint8) if want_inside else None
         crossings = np.empty((n, 3), dtype=np.uint32) if want_crossings else None
         trips = np.empty(n, dtype=np.uint32) if want_trips else None
-        fn = lib().spira_scene_signed_distance_f32 if self.prec == "f32" else lib().spira_scene_signed_distance_f64
-        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(CAST_INPLACE if inplace else 0),
-                  *[o.ctypes.data_as(C.c_void_p) if o is not None else None for o in (prim, dist, point, inside, crossings, trips)]))
+        self._query("signed_distance", False, (p,), (n,), self._flags(inplace), (prim, dist, point, inside, crossings, trips))
         return prim, dist, point, inside, crossings, trips
 
     def signed_distance_device(self, d_points_ptr, n_points, d_prim_ptr, d_dist_ptr, d_point_ptr, d_inside_ptr, stream_ptr, inplace=False, d_crossings_ptr=0,
                                d_trips_ptr=0):
         """spira_scene_signed_distance_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
         allocated."""
-        fn = lib().spira_scene_signed_distance_device_f32 if self.prec == "f32" else lib().spira_scene_signed_distance_device_f64
-        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(CAST_INPLACE if inplace else 0), C.c_void_p(d_prim_ptr or None),
-                  C.c_void_p(d_dist_ptr or None), C.c_void_p(d_point_ptr or None), C.c_void_p(d_inside_ptr or None), C.c_void_p(d_crossings_ptr or None),
-                  C.c_void_p(d_trips_ptr or None), C.c_void_p(stream_ptr or None)))
+        self._query("signed_distance", True, (d_points_ptr,), (n_points,), self._flags(inplace),
+                    (d_prim_ptr, d_dist_ptr, d_point_ptr, d_inside_ptr, d_crossings_ptr, d_trips_ptr, stream_ptr))
 
     def radiance(self, rays6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_radiance_*: path-traced radiance along rays6 (n x [ox oy oz dx dy dz], host array; directions are normalised by the library).
         Ray k, sample s is the renderer's path at pixel key key0 + k.  ADDS samples sample0 .. sample0 + spp - 1, in order, to sums ([n, 3], in place; None: a
         fresh zero array).  Returns sums, or (sums, valid uint8 [n]) with want_valid."""
         npdt, _ = _dt(self.prec)
-        r = np.ascontiguousarray(rays6, dtype=npdt)
-        if r.ndim != 2 or r.shape[1] != 6:
-            raise ValueError("rays6: n_rays x [ox oy oz dx dy dz]")
+        r = self._list(rays6, 6, "rays6: n_rays x [ox oy oz dx dy dz]")
         n = len(r)
         if sums is None:
             sums = np.zeros((n, 3), dtype=npdt)
@@ -702,25 +674,17 @@ class Scene:
             raise ValueError("sums: a contiguous [n_rays, 3] array of the handle's precision")
         valid = np.empty(n, dtype=np.uint8) if want_valid else None
         rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
-        fn = lib().spira_scene_radiance_f32 if self.prec == "f32" else lib().spira_scene_radiance_f64
-        _check(fn(self._h, r.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(rp), sums.ctypes.data_as(C.c_void_p),
-                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        self._query("radiance", False, (r,), (n,), C.byref(rp), (sums, valid))
         return (sums, valid) if want_valid else sums
 
     def radiance_device(self, d_rays_ptr, n_rays, spp, max_depth, d_sums_ptr, seed=0, sample0=0, key0=0, flags=0, d_valid_ptr=0, stream_ptr=0):
         """spira_scene_radiance_device_*: DEVICE addresses (d_valid_ptr 0 / None: not wanted), asynchronous on the stream; the sums are added to in place."""
         rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
-        fn = lib().spira_scene_radiance_device_f32 if self.prec == "f32" else lib().spira_scene_radiance_device_f64
-        _check(fn(self._h, C.c_void_p(d_rays_ptr or None), C.c_uint32(n_rays), C.byref(rp), C.c_void_p(d_sums_ptr or None), C.c_void_p(d_valid_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("radiance", True, (d_rays_ptr,), (n_rays,), C.byref(rp), (d_sums_ptr, d_valid_ptr, stream_ptr))
 
 
     def _points(self, points6):
-        npdt, _ = _dt(self.prec)
-        p = np.ascontiguousarray(points6, dtype=npdt)
-        if p.ndim != 2 or p.shape[1] != 6:
-            raise ValueError("points6: n_points x [px py pz nx ny nz]")
-        return p
+        return self._list(points6, 6, "points6: n_points x [px py pz nx ny nz]")
 
     def gather(self, points6, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
         """spira_scene_gather_*: path-traced radiance over the hemisphere of every point of points6 (n x [px py pz nx ny nz], host array; the library
@@ -735,17 +699,13 @@ class Scene:
             raise ValueError("sums: a contiguous [n_points, 3] array of the handle's precision")
         valid = np.empty(n, dtype=np.uint8) if want_valid else None
         rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
-        fn = lib().spira_scene_gather_f32 if self.prec == "f32" else lib().spira_scene_gather_f64
-        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(rp), sums.ctypes.data_as(C.c_void_p),
-                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        self._query("gather", False, (p,), (n,), C.byref(rp), (sums, valid))
         return (sums, valid) if want_valid else sums
 
     def gather_device(self, d_points_ptr, n_points, spp, max_depth, d_sums_ptr, seed=0, sample0=0, key0=0, flags=0, d_valid_ptr=0, stream_ptr=0):
         """spira_scene_gather_device_*: DEVICE addresses (d_valid_ptr 0 / None: not wanted), asynchronous on the stream; the sums are added to in place."""
         rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
-        fn = lib().spira_scene_gather_device_f32 if self.prec == "f32" else lib().spira_scene_gather_device_f64
-        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.byref(rp), C.c_void_p(d_sums_ptr or None), C.c_void_p(d_valid_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("gather", True, (d_points_ptr,), (n_points,), C.byref(rp), (d_sums_ptr, d_valid_ptr, stream_ptr))
 
     def gather_visible(self, points6, spp, t_min=1e-3, t_max=float("inf"), seed=0, sample0=0, key0=0, counts=None, want_valid=False, inplace=False):
         """spira_scene_gather_visible_*: ADDS to counts (uint32 [n], in place; None: a fresh zero array) the number of samples sample0 .. sample0 + spp - 1
@@ -759,18 +719,14 @@ class Scene:
             raise ValueError("counts: a contiguous uint32 [n_points] array")
         valid = np.empty(n, dtype=np.uint8) if want_valid else None
         gv = GatherVisible(spp, sample0, seed, key0, CAST_INPLACE if inplace else 0, t_min, t_max)
-        fn = lib().spira_scene_gather_visible_f32 if self.prec == "f32" else lib().spira_scene_gather_visible_f64
-        _check(fn(self._h, p.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.byref(gv), counts.ctypes.data_as(C.c_void_p),
-                  valid.ctypes.data_as(C.c_void_p) if want_valid else None))
+        self._query("gather_visible", False, (p,), (n,), C.byref(gv), (counts, valid))
         return (counts, valid) if want_valid else counts
 
     def gather_visible_device(self, d_points_ptr, n_points, spp, d_counts_ptr, t_min=1e-3, t_max=float("inf"), seed=0, sample0=0, key0=0, d_valid_ptr=0,
                               stream_ptr=0, inplace=False):
         """spira_scene_gather_visible_device_*: DEVICE addresses, asynchronous on the stream; nothing is synchronised or allocated."""
         gv = GatherVisible(spp, sample0, seed, key0, CAST_INPLACE if inplace else 0, t_min, t_max)
-        fn = lib().spira_scene_gather_visible_device_f32 if self.prec == "f32" else lib().spira_scene_gather_visible_device_f64
-        _check(fn(self._h, C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.byref(gv), C.c_void_p(d_counts_ptr or None), C.c_void_p(d_valid_ptr or None),
-                  C.c_void_p(stream_ptr or None)))
+        self._query("gather_visible", True, (d_points_ptr,), (n_points,), C.byref(gv), (d_counts_ptr, d_valid_ptr, stream_ptr))
 
 
 def gather_rays(points6, sample=0, seed=0, key0=0, prec="f32"):

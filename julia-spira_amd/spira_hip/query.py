@@ -34,16 +34,26 @@ def normalize_rays(rays8, dtype, frame=None):
     return r, valid
 
 
+def _device_list(who, scene, x, columns, stream):
+    """The test every device front end makes of its list `x` (a contiguous tensor [n, columns] on a device, in the scene's precision).  Returns the torch
+    dtype, n and the stream to enqueue on (`stream`; None: the current one of the tensor's device)."""
+    import torch
+    want = torch.float32 if scene.prec == "f32" else torch.float64
+    if x.dtype != want or not x.is_cuda or x.dim() != 2 or x.shape[1] != columns or not x.is_contiguous():
+        raise ValueError("%s: a contiguous device tensor of n x %d %s values is needed" % (who, columns, scene.prec))
+    return want, x.shape[0], stream if stream is not None else torch.cuda.current_stream(x.device)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else 0
+
+
 def cast_rays(scene, rays, want_normal=False, occlusion=False, inplace=False, stream=None):
     """spira_scene_cast_device_* (occlusion: spira_scene_occluded_device_*) for a torch tensor of rays [n, 8] on the scene's device, in the scene's
     precision.  Enqueues on `stream` (a torch.cuda.Stream; None: the current one) and returns device tensors without synchronising:
     (prim int32 [n], t [n], normal [n, 3] or None), or hit uint8 [n] for occlusion.  `rays` must stay alive until the work has run."""
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if rays.dtype != want or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-        raise ValueError("cast_rays: a contiguous device tensor of n x 8 %s values is needed" % scene.prec)
-    n = rays.shape[0]
-    st = stream if stream is not None else torch.cuda.current_stream(rays.device)
+    want, n, st = _device_list("cast_rays", scene, rays, 8, stream)
     with torch.cuda.stream(st):
         if occlusion:
             hit = torch.empty(n, dtype=torch.uint8, device=rays.device)
@@ -52,7 +62,7 @@ def cast_rays(scene, rays, want_normal=False, occlusion=False, inplace=False, st
         prim = torch.empty(n, dtype=torch.int32, device=rays.device)
         t = torch.empty(n, dtype=want, device=rays.device)
         nrm = torch.empty((n, 3), dtype=want, device=rays.device) if want_normal else None
-        scene.cast_device(rays.data_ptr(), n, prim.data_ptr(), t.data_ptr(), nrm.data_ptr() if want_normal else 0, st.cuda_stream, inplace=inplace)
+        scene.cast_device(rays.data_ptr(), n, prim.data_ptr(), t.data_ptr(), _ptr(nrm), st.cuda_stream, inplace=inplace)
     return prim, t, nrm
 
 
@@ -65,18 +75,14 @@ def cast_all(scene, rays, max_hits, count_all=False, inplace=False, want_prim=Tr
     if isinstance(rays, np.ndarray) or not hasattr(rays, "is_cuda"):
         return scene.cast_hits(rays, max_hits, inplace=inplace, count_all=count_all, want_prim=want_prim, want_t=want_t)
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if rays.dtype != want or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-        raise ValueError("cast_all: a contiguous device tensor of n x 8 %s values is needed" % scene.prec)
-    n, k = rays.shape[0], int(max_hits)
+    want, n, st = _device_list("cast_all", scene, rays, 8, stream)
+    k = int(max_hits)
     room = k if 0 < k <= B.MAX_HITS else 1
-    st = stream if stream is not None else torch.cuda.current_stream(rays.device)
     with torch.cuda.stream(st):
         prim = torch.empty((n, room), dtype=torch.int32, device=rays.device) if want_prim and k else None
         t = torch.empty((n, room), dtype=want, device=rays.device) if want_t and k else None
         count = torch.empty(n, dtype=torch.int32, device=rays.device)
-        scene.cast_hits_device(rays.data_ptr(), n, k, prim.data_ptr() if prim is not None else 0, t.data_ptr() if t is not None else 0, count.data_ptr(),
-                               st.cuda_stream, inplace=inplace, count_all=count_all)
+        scene.cast_hits_device(rays.data_ptr(), n, k, _ptr(prim), _ptr(t), count.data_ptr(), st.cuda_stream, inplace=inplace, count_all=count_all)
     return prim, t, count
 
 
@@ -201,18 +207,13 @@ def closest_points(scene, points, inplace=False, want_point=True, want_trips=Fal
     on `stream` (a torch.cuda.Stream; None: the current one) and returns device tensors without synchronising: (prim int32 [n], dist [n], point [n, 3]
     or None, trips int32 [n] or None).  `points` must stay alive until the work has run."""
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise ValueError("closest_points: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
-    n = points.shape[0]
-    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    want, n, st = _device_list("closest_points", scene, points, 4, stream)
     with torch.cuda.stream(st):
         prim = torch.empty(n, dtype=torch.int32, device=points.device)
         dist = torch.empty(n, dtype=want, device=points.device)
         q = torch.empty((n, 3), dtype=want, device=points.device) if want_point else None
         trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
-        scene.closest_point_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), q.data_ptr() if want_point else 0, st.cuda_stream,
-                                   inplace=inplace, d_trips_ptr=trips.data_ptr() if want_trips else 0)
+        scene.closest_point_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), _ptr(q), st.cuda_stream, inplace=inplace, d_trips_ptr=_ptr(trips))
     return prim, dist, q, trips
 
 
@@ -226,21 +227,17 @@ def k_nearest(scene, points, k, count_all=False, inplace=False, want_prim=True, 
     if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
         return scene.nearest_k(points, k, inplace=inplace, count_all=count_all, want_prim=want_prim, want_dist=want_dist, want_point=want_point, want_trips=want_trips)
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise ValueError("k_nearest: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
-    n, k = points.shape[0], int(k)
+    want, n, st = _device_list("k_nearest", scene, points, 4, stream)
+    k = int(k)
     room = k if 0 < k <= B.MAX_NEAR else 1
-    st = stream if stream is not None else torch.cuda.current_stream(points.device)
     with torch.cuda.stream(st):
         prim = torch.empty((n, room), dtype=torch.int32, device=points.device) if want_prim and k else None
         dist = torch.empty((n, room), dtype=want, device=points.device) if want_dist and k else None
         q = torch.empty((n, room, 3), dtype=want, device=points.device) if want_point and k else None
         count = torch.empty(n, dtype=torch.int32, device=points.device)
         trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
-        ptr = lambda t: t.data_ptr() if t is not None else 0
-        scene.nearest_k_device(points.data_ptr(), n, k, ptr(prim), ptr(dist), ptr(q), count.data_ptr(), st.cuda_stream, inplace=inplace, count_all=count_all,
-                               d_trips_ptr=ptr(trips))
+        scene.nearest_k_device(points.data_ptr(), n, k, _ptr(prim), _ptr(dist), _ptr(q), count.data_ptr(), st.cuda_stream, inplace=inplace, count_all=count_all,
+                               d_trips_ptr=_ptr(trips))
     return prim, dist, q, count, trips
 
 
@@ -394,13 +391,9 @@ def sweep_spheres(scene, rays, radii, blocked=False, inplace=False, want_point=T
             return scene.sweep_blocked(rays, radii, inplace=inplace)
         return scene.sweep(rays, radii, inplace=inplace, want_point=want_point, want_normal=want_normal, want_trips=want_trips)
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if rays.dtype != want or not rays.is_cuda or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-        raise ValueError("sweep_spheres: a contiguous device tensor of n x 8 %s values is needed" % scene.prec)
-    n = rays.shape[0]
+    want, n, st = _device_list("sweep_spheres", scene, rays, 8, stream)
     if radii.dtype != want or not radii.is_cuda or radii.dim() != 1 or radii.shape[0] != n or not radii.is_contiguous():
         raise ValueError("sweep_spheres: radii must be a contiguous device tensor of n %s values" % scene.prec)
-    st = stream if stream is not None else torch.cuda.current_stream(rays.device)
     with torch.cuda.stream(st):
         if blocked:
             hit = torch.empty(n, dtype=torch.uint8, device=rays.device)
@@ -411,9 +404,8 @@ def sweep_spheres(scene, rays, radii, blocked=False, inplace=False, want_point=T
         point = torch.empty((n, 3), dtype=want, device=rays.device) if want_point else None
         nrm = torch.empty((n, 3), dtype=want, device=rays.device) if want_normal else None
         trips = torch.empty(n, dtype=torch.int32, device=rays.device) if want_trips else None
-        ptr = lambda x: x.data_ptr() if x is not None else 0
-        scene.sweep_device(rays.data_ptr(), radii.data_ptr(), n, prim.data_ptr(), t.data_ptr(), ptr(point), ptr(nrm), st.cuda_stream, inplace=inplace,
-                           d_trips_ptr=ptr(trips))
+        scene.sweep_device(rays.data_ptr(), radii.data_ptr(), n, prim.data_ptr(), t.data_ptr(), _ptr(point), _ptr(nrm), st.cuda_stream, inplace=inplace,
+                           d_trips_ptr=_ptr(trips))
     return prim, t, point, nrm, trips
 
 
@@ -535,12 +527,9 @@ def overlap_boxes(scene, boxes, max_list, any=False, inplace=False, want_trips=F
             return scene.overlap_any(boxes, inplace=inplace)
         return scene.overlap_box(boxes, max_list, inplace=inplace, want_trips=want_trips)
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if boxes.dtype != want or not boxes.is_cuda or boxes.dim() != 2 or boxes.shape[1] != 10 or not boxes.is_contiguous():
-        raise ValueError("overlap_boxes: a contiguous device tensor of n x 10 %s values is needed" % scene.prec)
-    n, k = boxes.shape[0], int(max_list)
+    _, n, st = _device_list("overlap_boxes", scene, boxes, 10, stream)
+    k = int(max_list)
     room = k if 0 < k <= B.MAX_OVERLAP else 1
-    st = stream if stream is not None else torch.cuda.current_stream(boxes.device)
     with torch.cuda.stream(st):
         if any:
             hit = torch.empty(n, dtype=torch.uint8, device=boxes.device)
@@ -549,8 +538,7 @@ def overlap_boxes(scene, boxes, max_list, any=False, inplace=False, want_trips=F
         prim = torch.empty((n, room), dtype=torch.int32, device=boxes.device) if k else None
         count = torch.empty(n, dtype=torch.int32, device=boxes.device)
         trips = torch.empty(n, dtype=torch.int32, device=boxes.device) if want_trips else None
-        ptr = lambda t: t.data_ptr() if t is not None else 0
-        scene.overlap_box_device(boxes.data_ptr(), n, k, ptr(prim), count.data_ptr(), st.cuda_stream, inplace=inplace, d_trips_ptr=ptr(trips))
+        scene.overlap_box_device(boxes.data_ptr(), n, k, _ptr(prim), count.data_ptr(), st.cuda_stream, inplace=inplace, d_trips_ptr=_ptr(trips))
     return prim, count, trips
 
 
@@ -664,11 +652,7 @@ def signed_distance(scene, points, inplace=False, want_point=True, want_crossing
     if isinstance(points, np.ndarray) or not hasattr(points, "is_cuda"):
         return scene.signed_distance(points, inplace=inplace, want_point=want_point, want_crossings=want_crossings, want_trips=want_trips)
     import torch
-    want = torch.float32 if scene.prec == "f32" else torch.float64
-    if points.dtype != want or not points.is_cuda or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
-        raise ValueError("signed_distance: a contiguous device tensor of n x 4 %s values is needed" % scene.prec)
-    n = points.shape[0]
-    st = stream if stream is not None else torch.cuda.current_stream(points.device)
+    want, n, st = _device_list("signed_distance", scene, points, 4, stream)
     with torch.cuda.stream(st):
         prim = torch.empty(n, dtype=torch.int32, device=points.device)
         dist = torch.empty(n, dtype=want, device=points.device)
@@ -676,9 +660,8 @@ def signed_distance(scene, points, inplace=False, want_point=True, want_crossing
         inside = torch.empty(n, dtype=torch.uint8, device=points.device)
         cr = torch.empty((n, 3), dtype=torch.int32, device=points.device) if want_crossings else None
         trips = torch.empty(n, dtype=torch.int32, device=points.device) if want_trips else None
-        ptr = lambda t: t.data_ptr() if t is not None else 0
-        scene.signed_distance_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), ptr(q), inside.data_ptr(), st.cuda_stream, inplace=inplace,
-                                     d_crossings_ptr=ptr(cr), d_trips_ptr=ptr(trips))
+        scene.signed_distance_device(points.data_ptr(), n, prim.data_ptr(), dist.data_ptr(), _ptr(q), inside.data_ptr(), st.cuda_stream, inplace=inplace,
+                                     d_crossings_ptr=_ptr(cr), d_trips_ptr=_ptr(trips))
     return prim, dist, q, inside, cr, trips
 
 
