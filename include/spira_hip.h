@@ -821,6 +821,10 @@ int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, dou
  * function k_path asks (csrc/spira_sky.h; no device needed): 1 no ray of the pixel can — it sees the sky alone —, 0 one may, or a negative SPIRA_E_*
  * code (a NULL pointer).  It errs towards 0 only. */
 int spira_sky_pixel_f64(const double camera12[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres);
+/* Which spheres can they meet?  *out_mask: bit s is clear only if no camera ray of the pixel can meet sphere s (s < 32; spheres beyond have no bit and
+ * count as reachable; every bit is set where the pixel's own guards fail).  k_path ORs the masks of a run's pixels and its camera rays test the spheres
+ * whose bit is set (SPIRA_REACH_MASKS).  0, or a negative SPIRA_E_* code (a NULL pointer).  A bit errs towards set only. */
+int spira_pixel_reach_f64(const double camera12[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres, uint32_t *out_mask);
 
 /* ---- first-hit feature buffers: per-pixel albedo, normal and depth, the guides of the denoiser below ----
  * For samples 0 .. params->spp - 1 of each pixel: the camera ray every render entry takes (RNG key: global pixel, sample, bounce 0) and its closest

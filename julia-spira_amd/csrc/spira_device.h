@@ -911,6 +911,50 @@ __device__ __forceinline__ void closest_hit_local(const SceneLds<T> &sc, Vec<T> 
     }
 }
 
+// The CAM scan of a sphere scene under a wave-uniform reach mask (PathArgs::reach_masks): spheres s < 32 are visited only where bit s of `mask` is set,
+// spheres from 32 on always, in ascending order — a sphere left out has disc < 0 for every ray of the row (spira_sky.h), so `closest`, `prim` and the
+// speculative window (root_operands) are those of the full loop.  An all-ones mask IS the full loop.  The next packet is requested ahead of the test, as there.
+template <class T, class P>
+__device__ __forceinline__ void closest_hit_cam_masked(const SceneLds<T> &sc, Vec<T> d, T t_min, T &closest, int &prim, P &pol, const Pack4<T> *cam, uint32_t mask) {
+    closest = (T)INFINITY;                                     // t_max = Inf, :335
+    prim = -1;
+    const T a = dot(d, d);                                     // :115
+    const T two_a = (T)2.0 * a;
+    const T four_a = (T)4 * a;
+    const RootDiv<T> over_2a = root_divisor<T>(two_a, pol);
+    root_t_min<T>(t_min, pol);
+    const uint32_t n = sc.n_spheres;
+    auto from = [&](uint32_t k) -> uint32_t {                  // the first sphere >= k to visit (scalar arithmetic: mask and k are wave-uniform)
+        if (k >= 32u) return k;
+        const uint32_t m = mask >> k;
+        return m ? k + (uint32_t)__builtin_ctz(m) : 32u;
+    };
+    uint32_t s = from(0u);
+    Pack4<T> c_next = cam[s < n ? s : 0u];                     // (slot 0 always exists in the LDS image)
+    while (s < n) {
+        const Pack4<T> c = c_next;
+        const uint32_t s_next = from(s + 1u);
+        c_next = cam[s_next < n ? s_next : s];
+        const Vec<T> oc = mk<T>(c.x, c.y, c.z);
+        const T cc = c.w;
+        T b = (T)2.0 * dot(oc, d);                             // :116
+        const T bb = b * b;
+        T disc = bb - four_a * cc;                             // :118
+        if (!(disc < 0)) {                                     // :120
+            root_operands<T>(bb, disc, pol);
+            T sq = root_sqrt<T>(disc, pol);                    // :125
+            T root = root_over<T>(-b - sq, over_2a, pol);          // :126
+            bool ok = !(root < t_min || root > closest);       // :130
+            if (!ok && root < t_min) {                         // (closest_hit_local has the argument)
+                root = root_over<T>(-b + sq, over_2a, pol);
+                ok = !(root < t_min || root > closest);
+            }
+            if (ok) { closest = root; prim = (int)s; }         // :137, :252
+        }
+        s = s_next;
+    }
+}
+
 // Does the ray come near the mesh at all (its LDS-resident bounding box, conservative slab test, within the closest hit so far)?
 template <class T>
 __device__ __forceinline__ bool mesh_box_hit(const SceneLds<T> &sc, Vec<T> o, Vec<T> d, T closest) {
@@ -1185,6 +1229,25 @@ __device__ __forceinline__ void camera_ray_lds(const RenderConst<T> &rc, const T
     rng3<T>(rng_key(rc.sA, rc.sB, pixel, sample, 0), 0, xu, xv, unused);
     T u = pixel_quotient<T>((T)(i - 1) + xu, pd.w1, pol);                    // :398
     T v = pixel_quotient<T>((T)(j - 1) + xv, pd.h1, pol);                    // :399
+    o = mk<T>(cam[0], cam[1], cam[2]);
+    const Vec<T> llc = mk<T>(cam[3], cam[4], cam[5]), hor = mk<T>(cam[6], cam[7], cam[8]), ver = mk<T>(cam[9], cam[10], cam[11]);
+    d = normalize(((llc + hor * u) + ver * v) - o, pol);                     // :303
+}
+
+// the same from a pixel table entry (PathArgs::pixel_table): i - 1, j - 1 and the inner hashes mix32(sA + pixel), mix32(sB ^ pixel) of rng_key, whose
+// bounce is 0 here — (sample << 8) | 0 — so the key is the same three words
+template <class T, class P>
+__device__ __forceinline__ void camera_ray_lds(const T *cam, const PixelDiv<T> &pd, uint32_t im1, uint32_t jm1, uint32_t hA, uint32_t hB, uint32_t sample,
+                                               Vec<T> &o, Vec<T> &d, P &pol) {
+    T xu, xv, unused;
+    const uint32_t sb = sample << 8;
+    RngKey k;
+    k.hA = mix32(hA ^ sb);
+    k.hB = mix32(hB + sb);
+    k.hBr = (k.hB << 16) | (k.hB >> 16);
+    rng3<T>(k, 0, xu, xv, unused);
+    T u = pixel_quotient<T>((T)im1 + xu, pd.w1, pol);                        // :398
+    T v = pixel_quotient<T>((T)jm1 + xv, pd.h1, pol);                        // :399
     o = mk<T>(cam[0], cam[1], cam[2]);
     const Vec<T> llc = mk<T>(cam[3], cam[4], cam[5]), hor = mk<T>(cam[6], cam[7], cam[8]), ver = mk<T>(cam[9], cam[10], cam[11]);
     d = normalize(((llc + hor * u) + ver * v) - o, pol);                     // :303
@@ -1598,7 +1661,16 @@ template <class T> struct PathArgs {
     // only entry of the run it touches — until the end-of-wave block moves it to accum under the conditions it already has.  No scan, and no
     // 24 bytes per sample written and read back.
     uint32_t sky_runs;
+    // Pixel table and reach masks (pixel-owning passes; 0: off, each on its own).  The lane that classifies its owned pixel ahead of the loop keeps what
+    // path_of gave it: a PixelEntry per owned pixel and one reach word per run (the OR of its pixels' pixel_reach masks, spira_sky.h) go to a region of
+    // LDS behind the camera's packets — the host adds own_lds_bytes() to these launches alone.  A camera row of the loop (RUN pixels x 64 / RUN slots)
+    // then reads pixel, i - 1, j - 1 and the two inner hashes of the RNG key from its pixel's entry instead of dividing and mixing per path
+    // (pixel_table), and its scan visits only the spheres its run can reach, in ascending order (reach_masks; a row that spans runs — k_eff no
+    // multiple of 64 / RUN — or a scene of more than 32 spheres scans all).  Same words, same `closest` / `prim`: a sphere left out has disc < 0.
+    uint32_t pixel_table, reach_masks;
 };
+struct alignas(16) PixelEntry { uint32_t hA, hB, im1, jm1, pixel, pad[3]; };      // mix32(sA + pixel), mix32(sB ^ pixel), i - 1, j - 1
+static_assert(sizeof(PixelEntry) == 32, "an entry is 32 bytes (spira_plan.h, kPixelEntryBytes)");
 
 // Pixel-owning passes: lane l of wave w owns pixel ((l / RUN) * nw + w) * RUN + l % RUN — 64 / RUN runs of RUN adjacent pixels, nw * RUN pixels
 // apart, so that a wave's cost is the mean of pixels all over the frame (contiguous blocks are all sky or all sphere: a long launch tail).
@@ -1767,21 +1839,36 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
     uint32_t sky_mask = 0;
     uint32_t *sky_word = reinterpret_cast<uint32_t *>(cam_lds + 12) + wave;
     static_assert(12 * sizeof(T) + WPB * sizeof(uint32_t) <= 128 || !kOwnT, "a word per wave behind the camera");
+    // The wave's pixel table and its runs' reach words (PathArgs::pixel_table / reach_masks): behind the camera's packets, where the host made room.
+    PixelEntry *own_tab = reinterpret_cast<PixelEntry *>(reinterpret_cast<unsigned char *>(cam_lds) + 128 + (a.cam_consts ? a.scene.n_spheres * sizeof(Pack4<T>) : 0));
+    uint32_t *reach_word = reinterpret_cast<uint32_t *>(own_tab + WPB * 64) + wave * (64 / SPIRA_RESOLVE_RUN);
+    own_tab += wave * 64;
     if constexpr (kOwnT) {
-        if (own && a.sky_runs) {
+        if (own && (a.sky_runs || a.pixel_table || a.reach_masks)) {
             constexpr uint32_t kRun = SPIRA_RESOLVE_RUN, kRuns = 64 / kRun, kRowSlots = 64 / kRun;
             static_assert(kRun == 4 && 2 * 64 * sizeof(Pack3<T>) <= SUB * sizeof(Pack4<T>), "the run mask below is written for runs of 4; a row of terms fits the work list");
             {
                 const uint32_t px = owned_pixel(wid, NW, lane);
                 bool sky = false;
+                uint32_t reach = 0xFFFFFFFFu;                        // (a pixel beyond the tile: its run is no sky run and scans everything)
+                uint32_t pi = 1, pj = 1, pixel = 0, sample;
                 if (px < rc.tile_pixels) {
-                    uint32_t pi, pj, pixel, sample;
+                    bool beyond;
                     path_of<T>(rc, px, a.pass, pi, pj, pixel, sample);
-                    sky = sky_pixel(cam_lds, rc.width, rc.height, pi, pj, a.scene.spheres5, a.scene.n_spheres);
+                    reach = pixel_reach(cam_lds, rc.width, rc.height, pi, pj, a.scene.spheres5, a.scene.n_spheres, &beyond);
+                    sky = reach == 0 && !beyond;                     // sky_pixel
+                }
+                if (a.pixel_table) {                                 // what the lane knows of its pixel: kept for the camera rows of the loop
+                    PixelEntry &e = own_tab[lane];
+                    e.hA = mix32(rc.sA + pixel); e.hB = mix32(rc.sB ^ pixel); e.im1 = pi - 1; e.jm1 = pj - 1; e.pixel = pixel;
+                }
+                if (a.reach_masks) {                                 // a run reaches what one of its pixels does
+                    reach |= (uint32_t)__shfl_xor((int)reach, 1); reach |= (uint32_t)__shfl_xor((int)reach, 2);
+                    if (lane % kRun == 0) reach_word[lane / kRun] = reach;
                 }
                 unsigned long long b = __ballot(sky);
                 b &= b >> 1; b &= b >> 2;                            // bit 4 g: all four pixels of run g (inside the tile, and sky)
-                for (uint32_t g = 0; g < kRuns; ++g) sky_mask |= (uint32_t)((b >> (kRun * g)) & 1ull) << g;
+                if (a.sky_runs) for (uint32_t g = 0; g < kRuns; ++g) sky_mask |= (uint32_t)((b >> (kRun * g)) & 1ull) << g;
             }
             // The sky pass.  Run g's paths in the loop's order — rows of RUN pixels x 64 / RUN slots, the loop's own camera ray and sky term — but the
             // terms go to the wave's work list (idle until the loop's first phase 1) and lanes 0 .. RUN-1 add them up in sample order: resolve_pixel's statements.
@@ -1880,10 +1967,12 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                 bool parked = false; T park_t = 0; int park_prim = -1;
                 uint32_t qf = idx;                                // round 0: the camera ray's path index
                 bool in = idx < limit;
+                uint32_t own_l = 0, own_slot = 0;                 // pixel-owning pass: whose pixel of the wave's 64 the path is, and which of its slots
                 if (own && first) {                               // pixel-owning pass: idx is the wave's path (PathArgs::accum)
                     const uint32_t t = idx / SPIRA_RESOLVE_RUN, run = fastdiv(t, a.fd_keff);
-                    const uint32_t px = owned_pixel(wid, NW, run * SPIRA_RESOLVE_RUN + idx % SPIRA_RESOLVE_RUN);
-                    qf = (t - run * a.k_eff) * rc.tile_pixels + px;
+                    own_l = run * SPIRA_RESOLVE_RUN + idx % SPIRA_RESOLVE_RUN; own_slot = t - run * a.k_eff;
+                    const uint32_t px = owned_pixel(wid, NW, own_l);
+                    qf = own_slot * rc.tile_pixels + px;
                     in = in && px < rc.tile_pixels;
                     if constexpr (kOwnT) in = in && !((*sky_word >> run) & 1u);       // an all-sky run was summed ahead of the loop
                 }
@@ -1893,9 +1982,27 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                         uint32_t pixel, sample, pi, pj;
                         Vec<T> d;
                         q[r] = ql;
-                        path_of<T>(rc, qf, a.pass, pi, pj, pixel, sample);
-                        if (kCarry) { ka[r] = mix32(rc.sA + pixel) ^ (sample << 8); kb[r] = mix32(rc.sB ^ pixel) + (sample << 8); }
-                        camera_ray_lds<T>(rc, cam_lds, pix_div, pi, pj, pixel, sample, o[r], d, pol);
+                        uint32_t cmask = 0xFFFFFFFFu;             // the spheres this row's camera scan visits (kOwnT; wave-uniform)
+                        if constexpr (kOwnT) {
+                            uint32_t hA, hB, im1, jm1;
+                            if (own && a.pixel_table) {           // the pixel's entry of the wave's table instead of two divisions and two mixes per path
+                                const PixelEntry e = own_tab[own_l];
+                                hA = e.hA; hB = e.hB; im1 = e.im1; jm1 = e.jm1;
+                                sample = rc.sample0 + a.pass * rc.slots + own_slot;
+                            } else {
+                                path_of<T>(rc, qf, a.pass, pi, pj, pixel, sample);
+                                hA = mix32(rc.sA + pixel); hB = mix32(rc.sB ^ pixel); im1 = pi - 1; jm1 = pj - 1;
+                            }
+                            ka[r] = hA ^ (sample << 8); kb[r] = hB + (sample << 8);
+                            camera_ray_lds<T>(cam_lds, pix_div, im1, jm1, hA, hB, sample, o[r], d, pol);
+                            // a row inside one run (k_eff a multiple of the row's slots) of a scene the mask has a bit for every sphere of
+                            if (own && a.reach_masks && a.k_eff % (64 / SPIRA_RESOLVE_RUN) == 0 && sc.n_spheres <= 32u)
+                                cmask = (uint32_t)__builtin_amdgcn_readfirstlane((int)reach_word[fastdiv((sub * SUB + r * 64) / SPIRA_RESOLVE_RUN, a.fd_keff)]);
+                        } else {
+                            path_of<T>(rc, qf, a.pass, pi, pj, pixel, sample);
+                            if (kCarry) { ka[r] = mix32(rc.sA + pixel) ^ (sample << 8); kb[r] = mix32(rc.sB ^ pixel) + (sample << 8); }
+                            camera_ray_lds<T>(rc, cam_lds, pix_div, pi, pj, pixel, sample, o[r], d, pol);
+                        }
                         if (EXT) { ex[r].flags = rc.flags; if (rc.flags & kExtSpectral) beta[r] = ext_wavelength<T>(sc, rc.sA, rc.sB, pixel, sample, ex[r]); }
                         T t; uint32_t slot = 0;
                         int prim;
@@ -1903,7 +2010,10 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
                             if (kCam && a.cam_consts) closest_hit_local<T, Pol, TRI, true>(sc, o[r], d, (T)0.001, t, prim, pol, cam_sph);
                             else closest_hit_local<T, Pol, TRI>(sc, o[r], d, (T)0.001, t, prim, pol);   // :335, spheres and LDS triangles
                             parked = mesh_box_hit<T>(sc, o[r], d, t);
-                        } else if (kCam && !BVH && a.cam_consts) { closest_hit_local<T, Pol, TRI, true>(sc, o[r], d, (T)0.001, t, prim, pol, cam_sph); }
+                        } else if (kCam && !BVH && a.cam_consts) {
+                            if constexpr (kOwnT) closest_hit_cam_masked<T, Pol>(sc, d, (T)0.001, t, prim, pol, cam_sph, cmask);      // (all ones: the full scan)
+                            else closest_hit_local<T, Pol, TRI, true>(sc, o[r], d, (T)0.001, t, prim, pol, cam_sph);
+                        }
                         else prim = closest_hit<T, BVH, Pol, TRI>(sc, o[r], d, (T)0.001, t, slot, pol);     // :335
                         ++n_seg;
                         if (parked) { park_t = t; park_prim = prim; pend[r].v = d; }          // parked below, in uniform control flow
@@ -2324,11 +2434,11 @@ __global__ __launch_bounds__(kBlock, MODE == 2 ? (sizeof(T) == 8 ? SPIRA_WAVES_B
         }
         // k_resolve's fold of the statistics rows, one wave instruction: lane i adds counter i (Stats' first four fields)
         const uint32_t seg = __shfl(n_seg, 0), rmw = __shfl(n_rmw, 0), sto = __shfl(n_store, 0);
-        if (lane < 4) {
-            unsigned long long *f = lane == 0 ? &a.stats->segments : (lane == 1 ? &a.stats->rays_enqueued : (lane == 2 ? &a.stats->radiance_rmw : &a.stats->radiance_store));
-            atomicAdd(f, (unsigned long long)(lane == 0 ? seg : (lane == 1 ? n_enq : (lane == 2 ? rmw : sto))));
+        // (lane 4, where the wave summed sky runs: their pixels, in the same instruction)
+        if (lane < 4 || (kOwnT && lane == 4 && sky_mask)) {
+            unsigned long long *f = lane == 0 ? &a.stats->segments : (lane == 1 ? &a.stats->rays_enqueued : (lane == 2 ? &a.stats->radiance_rmw : (lane == 3 ? &a.stats->radiance_store : &a.stats->sky_pixels)));
+            atomicAdd(f, (unsigned long long)(lane == 0 ? seg : (lane == 1 ? n_enq : (lane == 2 ? rmw : (lane == 3 ? sto : SPIRA_RESOLVE_RUN * (uint32_t)__popc(sky_mask))))));
         }
-        if constexpr (kOwnT) if (lane == 4 && sky_mask) atomicAdd(&a.stats->sky_pixels, (unsigned long long)(SPIRA_RESOLVE_RUN * __popc(sky_mask)));
     }
     MESH_STAT(if (lane == 0) { unsigned long long *g = g_mesh_dbg + (mesh_mode == 2u ? 16 : 0);
                                atomicAdd(&g[0], __builtin_readcyclecounter() - dbg_t0); atomicAdd(&g[1], dbg_sess); atomicAdd(&g[2], (unsigned long long)dbg_ns);

@@ -783,6 +783,7 @@ spira::Knobs read_knobs() {
     k.mesh_fat_waves_per_cu = env_u32("SPIRA_MESH_FAT_WAVES_PER_CU", 16);
     k.cam_consts = env_u32("SPIRA_CAM_CONSTS", 1);
     k.sky_runs = env_u32("SPIRA_SKY_RUNS", 1);
+    k.pixel_table = env_u32("SPIRA_PIXEL_TABLE", 1); k.reach_masks = env_u32("SPIRA_REACH_MASKS", 1);
     return k;
 }
 template <class T>
@@ -819,8 +820,9 @@ int ensure_workspaces(Ctx &c, const spira::Workspace &w) {
 // Called right before every k_path launch: each pointer of PathArgs against the capacity of the buffer it points into, for the grid about to be
 // launched (spira_plan.h, path_need); a launch that would not fit is refused (SPIRA_E_LIMIT) instead of letting a kernel write past a buffer nobody
 // sized.  (Round 3's fuzz found exactly that: a depth-1 mesh render writing parked rays' hits into queues only `max_depth > 1` used to size.)
+static_assert(sizeof(spira::PixelEntry) == spira::kPixelEntryBytes && spira::kOwnRuns * SPIRA_RESOLVE_RUN == 64, "own_lds_bytes sizes what k_path's prologue writes");
 template <class T>
-int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_launch_blocks) {
+int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_launch_blocks, size_t own_lds = 0) {
     using P4 = spira::Pack4<T>;
     using P2 = spira::Pack2<T>;
     spira::PathLaunch l;
@@ -829,6 +831,7 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
     l.mesh_mode = a.mesh_mode; l.resume_k = a.resume_k; l.resume_nw = a.resume_nw;
     l.mesh = a.scene.n_bvh_tris != 0; l.pixel_owning = a.accum != nullptr; l.l_private = a.l_private != 0;
     l.prec = sizeof(T); l.wpb = spira::kBlock / 64; l.carry_key = SPIRA_CARRY_KEY;
+    l.pixel_table = a.pixel_table != 0; l.reach_masks = a.reach_masks != 0; l.own_lds = own_lds;
     const spira::PathNeed need = spira::path_need(l);
     const uint64_t nw = need.nw, n = need.packets;
     auto covers = [](const DevBuf &b, const void *ptr, uint64_t bytes) { return ptr == b.p && b.p != nullptr && b.cap >= bytes; };
@@ -847,6 +850,7 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
     if (!bad && !covers(c.stats, a.stats, sizeof(spira::Stats))) bad = "counters";
     if (!bad && a.accum && (!covers(c.accum, a.accum, (uint64_t)a.rc.tile_pixels * sizeof(P4)) || !need.owning_ok)) bad = "pixel-owning pass";
     if (!bad && a.l_private && !need.private_ok) bad = "wave-private radiance blocks";
+    if (!bad && !need.table_ok) bad = "pixel table and reach masks in LDS";
     if (bad) return fail(SPIRA_E_LIMIT, std::string("internal: a workspace is smaller than the launch needs (") + bad + ")");
     return 0;
 }
@@ -1017,6 +1021,7 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
     // ... + one packet per sphere: what a sphere test of a CAMERA ray does not depend on the ray for (closest_hit_local, CAM) — where the block has the room
     pa.cam_consts = (kn.cam_consts && pa.scene.n_spheres && lds_a + (size_t)pa.scene.n_spheres * sizeof(P4) <= (size_t)160 * 1024) ? 1u : 0u;
     if (pa.cam_consts) lds_a += (size_t)pa.scene.n_spheres * sizeof(P4);
+    size_t own_lds = 0;
     if (plan.two_pass) {
         pa.mesh_mode = 1; pa.mesh_count = (uint32_t *)c.mesh_count.p;
         pa.resume_nw = G * plan.wpb; pa.resume_k = plan.fat_k(pa.resume_nw);
@@ -1026,8 +1031,14 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
         pa.accum_first = (pa.pass == 0 && !k.progressive) ? 1u : 0u;
         pa.l_private = plan.l_private ? 1u : 0u;
         pa.sky_runs = plan.sky_runs ? 1u : 0u;
+        // ... + the waves' pixel tables and run masks behind everything else (spira_plan.h, own_lds_bytes): these launches alone, and where the block has the room
+        if ((plan.pixel_table || plan.reach_masks) && lds_a + spira::own_lds_bytes(plan.wpb) <= (size_t)160 * 1024) {
+            own_lds = (size_t)spira::own_lds_bytes(plan.wpb);
+            lds_a += own_lds;
+            pa.pixel_table = plan.pixel_table ? 1u : 0u; pa.reach_masks = plan.reach_masks ? 1u : 0u;
+        }
     }
-    if (int rc = verify_path_args<T>(c, pa, G)) return rc;      // every pointer against the capacity of its buffer, for THIS grid
+    if (int rc = verify_path_args<T>(c, pa, G, own_lds)) return rc;     // every pointer against the capacity of its buffer, for THIS grid
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
     if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec)) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
     k.launches += k.spec ? 2 : 1;      // the speculative launch and its exact follow-up
@@ -3622,6 +3633,11 @@ int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const doubl
 int spira_sky_pixel_f64(const double cam[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres) {
     if (!cam || (n_spheres && !spheres5)) return fail(SPIRA_E_INVALID, "cam or spheres5 is NULL");
     return spira::sky_pixel(cam, width, height, i, j, spheres5, n_spheres) ? 1 : 0;
+}
+int spira_pixel_reach_f64(const double cam[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres, uint32_t *out_mask) {
+    if (!cam || !out_mask || (n_spheres && !spheres5)) return fail(SPIRA_E_INVALID, "cam, out_mask or spheres5 is NULL");
+    *out_mask = spira::pixel_reach(cam, width, height, i, j, spheres5, n_spheres);
+    return 0;
 }
 int spira_adaptive_converged_f32(const float sum3[3], float q, uint32_t n, double tolerance, double floor) {
     return adaptive_converged_host<float>(sum3, q, n, tolerance, floor);

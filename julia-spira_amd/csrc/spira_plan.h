@@ -20,6 +20,8 @@ struct Knobs {
     uint32_t spec_div = 1;                     // SPIRA_SPEC_DIV: 0 off, 1 where the scene's scale allows, 2 report every wave, 3 on whatever the scale
     uint32_t dense_pct = 70, mesh_min_batch = 128, mesh_refill = 16, mesh_fat_waves_per_cu = 16, cam_consts = 1;
     uint32_t sky_runs = 1;                     // SPIRA_SKY_RUNS: pixel-owning passes sum their all-sky runs ahead of the loop (0: every path goes through it; A/B, tests)
+    uint32_t pixel_table = 1;                  // SPIRA_PIXEL_TABLE: their camera rows read pixel, i, j and the two inner key hashes from a per-wave LDS table (0: path_of and the mixes per path)
+    uint32_t reach_masks = 1;                  // SPIRA_REACH_MASKS: their camera rows test only the spheres their pixel run can reach (0: every sphere)
 };
 
 struct PlanIn {
@@ -55,6 +57,7 @@ struct Plan {
     bool mesh_scene = false, defer_mesh = false, two_pass = false;      // a BVH scene; its traversal deferred (mesh lists); ... as a second, fat-wave launch
     bool fused = false, l_private = false;                 // pixel-owning passes (PathArgs::accum); wave-private radiance blocks (PathArgs::l_private)
     bool sky_runs = false;                                 // ... whose all-sky runs never enter the loop (PathArgs::sky_runs)
+    bool pixel_table = false, reach_masks = false;         // ... whose camera rows are fed from the wave's pixel table / scan by their run's reach mask (PathArgs, same names)
     bool spec_allowed = false;                             // the organisation has a speculative-division launch for this call
     uint32_t G_max = 0, cap_max = 0;                       // geometry of the largest pass
     uint64_t q_rays = 0;
@@ -149,6 +152,8 @@ inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
     // queue word has 31 bits for the entry of L.  SPIRA_PRIVATE_L=0: the slot-major layout (A/B).
     pl.l_private = pl.fused && in.carry_key && in.max_depth <= 128 && k.private_l != 0 && 64ull * waves * pl.slots <= 0x7FFFFFFFull;
     pl.sky_runs = pl.fused && k.sky_runs != 0;
+    pl.pixel_table = pl.fused && k.pixel_table != 0;
+    pl.reach_masks = pl.fused && k.reach_masks != 0;
     pl.q_rays = (uint64_t)g.cap * waves;
     if (pl.q_rays > 0xFFFFFFFFull) return bad("pass too large");
     // the speculative launch: fresh renders only (a progressive SPIRA_SEM_METAL call updates sums and states in place), R = 2 instantiations only
@@ -208,16 +213,22 @@ inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
 
 // ---- what a k_path launch needs of the workspaces, on counts: verify_path_args() (spira_hip.hip) compares these with the buffers behind the
 // pointers of the PathArgs about to be launched; the sanitizer harness with Plan::ws, for every pass of every plan of its sweep.
+// The LDS a launch that can run a pixel-owning pass adds for the pixel table and the reach masks (k_path's prologue writes both, the camera rows read
+// them): per wave 64 entries of kPixelEntryBytes — {mix32(sA + pixel), mix32(sB ^ pixel), i - 1, j - 1, pixel}, padded — and one mask word per run.
+constexpr uint32_t kPixelEntryBytes = 32, kOwnRuns = 16;
+inline uint64_t own_lds_bytes(uint32_t wpb) { return (uint64_t)wpb * (64 * kPixelEntryBytes + kOwnRuns * sizeof(uint32_t)); }
 struct PathLaunch {
     uint32_t blocks = 0, cap = 0, n_first = 0, k_eff = 0;      // blocks: of the pass's first launch (a fat wave of the second owns the regions of the waves it takes over)
     uint32_t tile_pixels = 0, max_depth = 0, flags = 0, n_lds_triangles = 0;
     uint32_t mesh_mode = 0, resume_k = 1, resume_nw = 0;
     bool mesh = false, pixel_owning = false, l_private = false;
+    bool pixel_table = false, reach_masks = false;             // PathArgs, same names
+    uint64_t own_lds = 0;                                      // bytes the launch's LDS block holds for the pixel table and the run masks (own_lds_bytes)
     uint32_t prec = 0, wpb = 0, carry_key = 0;
 };
 struct PathNeed {
     uint64_t nw, packets, l_entries;       // waves; entries of every per-packet array; entries of L
-    bool fits, resume_ok, owning_ok, private_ok;
+    bool fits, resume_ok, owning_ok, private_ok, table_ok;
 };
 inline PathNeed path_need(const PathLaunch &a) {
     PathNeed n{};
@@ -233,6 +244,8 @@ inline PathNeed path_need(const PathLaunch &a) {
                   (uint64_t)a.k_eff * tp == a.n_first && 64 * n.nw >= tp && a.cap >= 64ull * a.k_eff;
     // wave-private radiance blocks: pixel-owning passes whose queue word need not be the path index (the RNG key is carried: max_depth <= 128)
     n.private_ok = a.pixel_owning && a.carry_key && a.max_depth <= 128 && n.l_entries <= 0x80000000ull;
+    // pixel table / reach masks: pixel-owning passes alone, and the launch's LDS block has their region
+    n.table_ok = (!a.pixel_table && !a.reach_masks) || (a.pixel_owning && a.own_lds >= own_lds_bytes(a.wpb));
     return n;
 }
 

@@ -1,5 +1,5 @@
-// spira_sky.h — can any camera ray of one pixel reach any sphere?  One function, host and device, Float64 (pixel-owning passes are): k_path asks it
-// once per owned pixel ahead of its loop (spira_device.h, "sky pass"), spira_sky_pixel_f64 exports it, tests/native/sky_cull.cpp holds it against the
+// spira_sky.h — which spheres can the camera rays of one pixel reach, and can they reach any?  Two functions, host and device, Float64 (pixel-owning passes are): k_path asks it
+// once per owned pixel ahead of its loop (spira_device.h, "sky pass"), spira_sky_pixel_f64 / spira_pixel_reach_f64 export them, tests/native/sky_cull.cpp and reach_mask.cpp hold them against the
 // scan's own discriminant.  No HIP header, no library call: a host compiler reads it as it stands.
 //
 // The rays of pixel (i, j) (reference indices, 1-based) have the directions D = llc + hor u + ver v - origin with u in [(i-1)/(W-1), i/(W-1)),
@@ -28,8 +28,11 @@
 namespace spira {
 
 // cam: origin, lower-left corner, horizontal, vertical (3 values each, the kernel's LDS order); spheres5: {x, y, z, radius, material} per sphere.
-// true: no ray of pixel (i, j) has disc >= 0 for any sphere — the pixel sees the sky alone.
-SPIRA_HD inline bool sky_pixel(const double *cam, uint32_t W, uint32_t H, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres) {
+// Bit s of the result is clear only if no ray of pixel (i, j) can have disc >= 0 for sphere s: the inequality above, sphere by sphere, with the same
+// slack and the same guards.  Where a guard of the pixel fails (the early "may hit" exits) every bit is set; where a guard of a sphere fails, its bit.
+// Spheres with index >= 32 have no bit: a caller that wants a mask treats them as reachable (k_path scans all of them then).  `beyond` (optional)
+// receives whether one of THEM may be hit, so that sky_pixel still answers for sphere sets of any size as it always has.
+SPIRA_HD inline uint32_t pixel_reach(const double *cam, uint32_t W, uint32_t H, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres, bool *beyond = nullptr) {
     const double kSlack = 1.0 / 1048576.0, kHuge = 1.0e100, kTiny = 1.0e-100;
     const double w1 = (double)W - 1.0, h1 = (double)H - 1.0;
     const double uc = ((double)i - 0.5) / w1, vc = ((double)j - 0.5) / h1;
@@ -40,8 +43,10 @@ SPIRA_HD inline bool sky_pixel(const double *cam, uint32_t W, uint32_t H, uint32
     const double dy = ((cam[4] + cam[7] * uc) + cam[10] * vc) - cam[1];
     const double dz = ((cam[5] + cam[8] * uc) + cam[11] * vc) - cam[2];
     const double dd = (dx * dx + dy * dy) + dz * dz, dn = __builtin_sqrt(dd);
-    if (!(rho >= 0.0 && dn > rho && dn > kTiny && dn < kHuge)) return false;
+    if (!(rho >= 0.0 && dn > rho && dn > kTiny && dn < kHuge)) { if (beyond) *beyond = n_spheres > 32u; return 0xFFFFFFFFu; }
     const double q = __builtin_sqrt(dd - rho * rho);                 // |Dc| cos delta
+    uint32_t reach = 0;
+    bool far = false;
     for (uint32_t s = 0; s < n_spheres; ++s) {
         const double *sp = spheres5 + 5 * (uint64_t)s;
         const double r = sp[3];
@@ -50,10 +55,18 @@ SPIRA_HD inline bool sky_pixel(const double *cam, uint32_t W, uint32_t H, uint32
         const double xx = cy * dz - cz * dy, xy = cz * dx - cx * dz, xz = cx * dy - cy * dx;
         const double xn = __builtin_sqrt((xx * xx + xy * xy) + xz * xz);
         const double cd = __builtin_fabs((cx * dx + cy * dy) + cz * dz);
-        if (!(r > 0.0 && r < kHuge && cn > kTiny && cn < kHuge)) return false;
-        if (!(xn * q - cd * rho > (r * (1.0 + kSlack) + cn * kSlack) * dd)) return false;
+        const bool missed = (r > 0.0 && r < kHuge && cn > kTiny && cn < kHuge) && (xn * q - cd * rho > (r * (1.0 + kSlack) + cn * kSlack) * dd);
+        if (!missed) { if (s < 32u) reach |= 1u << s; else far = true; }
     }
-    return true;
+    if (beyond) *beyond = far;
+    return reach;
+}
+
+// true: no ray of pixel (i, j) has disc >= 0 for any sphere — the pixel sees the sky alone.  For up to 32 spheres this is pixel_reach() == 0; beyond
+// that the mask has run out of bits (the overflow case) and the spheres without one are asked for through `beyond`.
+SPIRA_HD inline bool sky_pixel(const double *cam, uint32_t W, uint32_t H, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres) {
+    bool beyond = false;
+    return pixel_reach(cam, W, H, i, j, spheres5, n_spheres, &beyond) == 0 && !beyond;
 }
 
 }  // namespace spira

@@ -43,7 +43,7 @@ MAX_DEPTH, MAX_SPP = 255, 1 << 24
 
 EXPORTS = [
     "spira_abi_version", "spira_build_id", "spira_last_error", "spira_device_count", "spira_set_device", "spira_get_counters",
-    "spira_get_sky_pixels", "spira_sky_pixel_f64",
+    "spira_get_sky_pixels", "spira_sky_pixel_f64", "spira_pixel_reach_f64",
     "spira_shutdown", "spira_camera_lookat_f32", "spira_camera_lookat_f64", "spira_render_f32", "spira_render_f64",
     "spira_render_device_f32", "spira_render_device_f64", "spira_trace_paths_f32", "spira_trace_paths_f64",
     "spira_tonemap_f32", "spira_stripe_rows", "spira_accumulate_f32", "spira_accumulate_f64", "spira_accumulate_device_f32",
@@ -222,6 +222,18 @@ def sky_pixel(camera12, width, height, i, j, spheres5):
     if rc < 0:
         _check(rc)
     return rc
+
+
+def pixel_reach(camera12, width, height, i, j, spheres5):
+    """spira_pixel_reach_f64: bit s clear = no camera ray of pixel (i, j) can meet sphere s (s < 32) — the library's host arithmetic."""
+    cam = np.ascontiguousarray(camera12, dtype=np.float64)
+    sp = np.ascontiguousarray(spheres5, dtype=np.float64).reshape(-1, 5)
+    assert cam.shape == (12,)
+    fn = lib().spira_pixel_reach_f64
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    mask = C.c_uint32(0)
+    _check(fn(cam.ctypes.data_as(C.c_void_p), width, height, i, j, sp.ctypes.data_as(C.c_void_p), len(sp), C.byref(mask)))
+    return mask.value
 
 
 def stripe_rows(height, stripe_h, stripe_count, stripe_rank):
