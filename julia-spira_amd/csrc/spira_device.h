@@ -581,162 +581,81 @@ __device__ __forceinline__ void bvh8_resolve_one(const SceneLds<T> &sc, Bvh8Walk
     }
 }
 
-// One trip of a lane's walk = ONE memory round trip: a lane with triangles pending tests the next one (render precision, caller's
-// coordinates: the scan's own test), any other lane visits its nearest pending child node; both kinds of lane issue their loads
-// together, through one per-lane pointer, before either computes.  (A node visit followed by a loop over its triangles made a wave
-// pay one dependent round trip per triangle of its unluckiest lane: ~10 000 cycles per wave-step on config 5.)  A group that is
-// exhausted pops the stack.  Returns false when the walk is over.  Stack levels < KL live in the wave's LDS scratch ([level][lane]).
-template <class T, int KL>
-__device__ __forceinline__ bool bvh8_step(const SceneLds<T> &sc, Bvh8Walk<T> &w, Bvh8Ray &r, Vec<T> o, Vec<T> d, T t_min, int base, T &closest, int &prim, uint32_t &slot,
-                                          uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
-    constexpr bool kWide = sizeof(T) == 8;
-    // Float32: TWO items per trip — the lane's pending triangle AND, once that was the node's last pending one, its next node visit, both fetched in the same
-    // round trip (the order of tests does not change the result: minimal t, ties to the later triangle).  Trips per ray 12.0 -> 10.4; with the 128 registers the
-    // second launch of a mesh pass has in Float32 that is config 5 3.83 -> 3.69 ms.  (It lost 5 % while that kernel was held to 96 registers and spilled 60 of
-    // them, and in Float64 — six more words to hold — it still gains nothing: 5.13 -> 5.20 ms; Float64 keeps one item per trip, below.)
-#ifdef SPIRA_BVH_DUAL_F64
-    constexpr bool kDual = true;
-#else
-    constexpr bool kDual = !kWide;
-#endif
-#ifdef SPIRA_BVH_SCREEN
-    constexpr bool kScreen = kWide;          // experiment build (see tri_screen_f32): measured 2 .. 6 % SLOWER than testing every triangle in Float64 where it is met
-#else
-    constexpr bool kScreen = false;
-#endif
-    if constexpr (kScreen) {
-        // Float64: the Float32 walk's trip (a node's last pending triangle AND the next node visit in one round trip, 5 + 3 loads), the triangle SCREENED in
-        // Float32 (tri_screen_f32): a triangle that may be hit joins the lane's candidate list; its Float64 test is run by bvh8_resolve_one(), in batches.
-        const bool do_tri = (w.tw >> 24) != 0;
-        uint32_t ti = 0;
-        const uint4 *pt = sc.bvh_tris32;
-        if (do_tri) {
-            const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);
-            ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-            w.tw &= ~(0x01000000u << s_);
-            pt = sc.bvh_tris32 + 3 * (size_t)ti;
-        }
-        bool do_node = (w.tw >> 24) == 0;
-        if (do_node && !(w.G & 0xFFu)) {
-            if (w.sp == 0) do_node = false;
-            else { --w.sp; w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL]; }
-        }
-        const uint4 *pn = sc.bvh_nodes;
-        if (do_node) {
-            const uint32_t pos = (uint32_t)__builtin_ctz(w.G);
-            const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-            w.G &= w.G - 1u;
-            if (w.G & 0xFFu) {
-                if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-                ++w.sp;
-            }
-            pn = sc.bvh_nodes + 5 * (size_t)idx;
-        }
-        const uint4 n0 = pn[0], n1 = pn[1], n2 = pn[2], n3 = pn[3], n4 = pn[4];
-        const uint4 u0 = pt[0], u1 = pt[1], u2 = pt[2];
-        asm volatile("" :: "v"(n0.x), "v"(n0.y), "v"(n0.z), "v"(n0.w), "v"(n1.x), "v"(n1.y), "v"(n1.z), "v"(n1.w), "v"(n2.x), "v"(n2.y), "v"(n2.z), "v"(n2.w) : "memory");
-        asm volatile("" :: "v"(n3.x), "v"(n3.y), "v"(n3.z), "v"(n3.w), "v"(n4.x), "v"(n4.y), "v"(n4.z), "v"(n4.w) : "memory");
-        asm volatile("" :: "v"(u0.x), "v"(u0.y), "v"(u0.z), "v"(u0.w), "v"(u1.x), "v"(u1.y), "v"(u1.z), "v"(u1.w), "v"(u2.x), "v"(u2.y), "v"(u2.z), "v"(u2.w) : "memory");
-        if (do_tri) {
-            float t_hi;
-            const int cls = tri_screen_f32(u0, u1, u2, r, (float)d.x, (float)d.y, (float)d.z, t_hi);
-            if (cls != 0) {
-                // a full list is emptied on the spot (rare: a ray grazing many triangles): this lane's candidates all go through the exact test now
-                if (__builtin_expect(w.nc == kBvhCand, 0)) { while (w.nc) bvh8_resolve_one<T>(sc, w, r, o, d, t_min, base, closest, prim, slot); }
-                w.c3 = w.c2; w.c2 = w.c1; w.c1 = w.c0; w.c0 = ti; ++w.nc;
-                if (cls == 2) r.best = __builtin_fminf(r.best, t_hi);
-            }
-        }
-        if (do_node) {
-            uint32_t ih, lh;
-            bvh8_node(n0, n1, n2, n3, n4, r, ih, lh);
-            w.G = (n1.x << 8) | ih;
-            w.tw = n1.y | (lh << 24);
-            w.rank = n1.z;
-        }
-        return (w.tw >> 24) != 0 || (w.G & 0xFFu) != 0 || w.sp > 0;
+// ------------------------------------------------------------------ one TRIP of a lane's walk through the 8-wide tree, written once
+// One trip = ONE memory round trip: a lane with triangles pending tests the next one (the LEAF arm), any other lane visits a child node (the NODE
+// arm); both kinds of lane issue their loads together, before either computes.  (A node visit followed by a loop over its triangles made a wave
+// pay one dependent round trip per triangle of its unluckiest lane: ~10 000 cycles per wave-step on config 5.)  The pieces of a trip follow, each
+// written once; every walk is built from them.  Two skeletons take the leaf arm as a callable: bvh8_trip below, the ray walks' (closest hit here,
+// multi-hit in spira_hits.h; walk_trip_two is its two-item form, which the screened Float64 walks use directly), and near_trip, the distance walks'
+// (spira_nearest.h: closest point, K nearest, signed distance).  The sweep (spira_sweep.h) and the box overlap (spira_overlap.h) have node arms and
+// walk structs of their own and are one function each on the same pieces.  The walk structs (Bvh8Walk, NearWalk, SweepWalk, OverlapWalk) carry tw,
+// rank and sp with one meaning; G is a group of siblings, a bit per child still to visit, everywhere but in NearWalk (see there).
+
+// The next pending triangle: the lowest leaf slot of tw is cleared; its record is tri_base + the rank of the slot.
+template <class W> __device__ __forceinline__ uint32_t walk_take_tri(W &w) {
+    const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);
+    const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
+    w.tw &= ~(0x01000000u << s_);
+    return ti;
+}
+// The next child of the group in G (its low byte is never empty here): bit (slot ^ oct), ascending = front to back; its bit is cleared.
+template <class W> __device__ __forceinline__ uint32_t walk_next_child(W &w, uint32_t oct) {
+    const uint32_t pos = (uint32_t)__builtin_ctz(w.G);
+    const uint32_t idx = (pos ^ oct) + (w.G >> 8);
+    w.G &= w.G - 1u;
+    return idx;
+}
+// ... and, siblings left, the group is kept on the stack, whose levels < KL live in the wave's LDS scratch ([level][lane]) and the others in the
+// lane's private array (the ray walks); or which is private altogether (the sweep and the box walk: its own overload, because `stack[sp++]` and
+// `stack[sp - 0]; ++sp` are scheduled differently and each family keeps the instruction stream it was tuned with — docs/experiments.md §42).
+template <int KL, class W> __device__ __forceinline__ uint32_t walk_take_group(W &w, uint32_t oct, uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
+    const uint32_t idx = walk_next_child(w, oct);
+    if (w.G & 0xFFu) {
+        if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
+        ++w.sp;
     }
-    if constexpr (kDual) {
-        const bool do_tri = (w.tw >> 24) != 0;
-        uint32_t ti = 0;
-        const uint4 *pt = reinterpret_cast<const uint4 *>(sc.bvh_tris);
-        if (do_tri) {
-            const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);
-            ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-            w.tw &= ~(0x01000000u << s_);
-            pt = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-        }
-        bool do_node = (w.tw >> 24) == 0;
-        if (do_node && !(w.G & 0xFFu)) {
-            if (w.sp == 0) do_node = false;
-            else { --w.sp; w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL]; }
-        }
-        const uint4 *pn = sc.bvh_nodes;
-        if (do_node) {
-            const uint32_t pos = (uint32_t)__builtin_ctz(w.G);
-            const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-            w.G &= w.G - 1u;
-            if (w.G & 0xFFu) {
-                if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-                ++w.sp;
-            }
-            pn = sc.bvh_nodes + 5 * (size_t)idx;
-        }
-        const uint4 n0 = pn[0], n1 = pn[1], n2 = pn[2], n3 = pn[3], n4 = pn[4];
-        const uint4 u0 = pt[0], u1 = pt[1], u2 = pt[2], uz = make_uint4(0, 0, 0, 0);
-        uint4 u3 = uz, u4 = uz, u5 = uz;
-        if constexpr (kWide) { u3 = pt[3]; u4 = pt[4]; u5 = pt[5]; }
-        asm volatile("" :: "v"(n0.x), "v"(n0.y), "v"(n0.z), "v"(n0.w), "v"(n1.x), "v"(n1.y), "v"(n1.z), "v"(n1.w), "v"(n2.x), "v"(n2.y), "v"(n2.z), "v"(n2.w) : "memory");
-        asm volatile("" :: "v"(n3.x), "v"(n3.y), "v"(n3.z), "v"(n3.w), "v"(n4.x), "v"(n4.y), "v"(n4.z), "v"(n4.w) : "memory");
-        asm volatile("" :: "v"(u0.x), "v"(u0.y), "v"(u0.z), "v"(u0.w), "v"(u1.x), "v"(u1.y), "v"(u1.z), "v"(u1.w), "v"(u2.x), "v"(u2.y), "v"(u2.z), "v"(u2.w) : "memory");
-        if constexpr (kWide) asm volatile("" :: "v"(u3.x), "v"(u3.y), "v"(u3.z), "v"(u3.w), "v"(u4.x), "v"(u4.y), "v"(u4.z), "v"(u4.w), "v"(u5.x), "v"(u5.y), "v"(u5.z), "v"(u5.w) : "memory");
-        if (do_tri) {
-            Pack4<T> v0, e1, e2;
-            bvh8_tri_words(u0, u1, u2, u3, u4, u5, v0, e1, e2);
-            T t;
-            if (triangle_test<T>(v0, e1, e2, o, d, t_min, closest, t)) {
-                const int p = base + (int)Bits<T>::to_u32(v0.w);
-                if (t < closest || p > prim) {
-                    closest = t; prim = p; slot = ti;
-                    r.best = bvh8_best((float)((t - w.t0) * sc.bvh_root[2].w));
-                }
-            }
-        }
-        if (do_node) {
-            uint32_t ih, lh;
-            bvh8_node(n0, n1, n2, n3, n4, r, ih, lh);
-            w.G = (n1.x << 8) | ih;
-            w.tw = n1.y | (lh << 24);
-            w.rank = n1.z;
-        }
-        return (w.tw >> 24) != 0 || (w.G & 0xFFu) != 0 || w.sp > 0;
+    return idx;
+}
+template <class W> __device__ __forceinline__ uint32_t walk_take_group(W &w, uint32_t oct, uint32_t *stack) {
+    const uint32_t idx = walk_next_child(w, oct);
+    if (w.G & 0xFFu) stack[w.sp++] = w.G;
+    return idx;
+}
+// A group that is exhausted — no triangle pending, no sibling left — gives way to the one on top of the stack.  false: there is none, the walk is over.
+template <int KL, class W> __device__ __forceinline__ bool walk_pop(W &w, uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
+    if ((w.tw >> 24) == 0 && !(w.G & 0xFFu)) {
+        if (w.sp == 0) return false;
+        --w.sp;
+        w.G = (KL > 0 && (int)w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL];
     }
-    const bool is_tri = (w.tw >> 24) != 0;
-    const uint4 *ptr;
-    uint32_t ti = 0;
-    if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next hit leaf slot; its triangle: tri_base + rank of the slot
-        ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-    } else {
-        const uint32_t pos = (uint32_t)__builtin_ctz(w.G);                 // (the low byte is never empty here)
-        const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-        w.G &= w.G - 1u;
-        if (w.G & 0xFFu) {                                                 // siblings left: keep the group
-            if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-            ++w.sp;
-        }
-        ptr = sc.bvh_nodes + 5 * (size_t)idx;
-    }
-    // Every lane loads the same number of words (a node is 5 x 16 bytes, a triangle 3 in Float32 and 6 in Float64; the arrays are padded
-    // by one record): a wave-instruction costs the memory pipeline the same whichever lanes take part, and loads under a condition
-    // would be sunk behind the other arm's arithmetic — a second round trip.  The empty asm pins all of them ahead of both arms.
-    uint4 w0, w1, w2, w3, w4, w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) {
-        // Float64: written out as the six aligned 16-byte loads they are.  Left to itself the compiler regroups the words by their later use
-        // into loads at odd offsets (dwordx4 at +4, dwordx2 at +0, dwordx3 at +68 ...): -2.5 % on config 5.  (In Float32 its grouping is the
-        // faster one by 5 %: register allocation.)
+    return true;
+}
+template <class W> __device__ __forceinline__ bool walk_pop(W &w, uint32_t *stack) { return walk_pop<0>(w, nullptr, stack, 0u); }
+// A visited node's children become the walk's state: ih = child nodes to visit, lh = leaf slots to test (words 4..6 of the record: child_base, tri_base, ranks).
+template <class W> __device__ __forceinline__ void walk_set_node(W &w, const uint4 n1, uint32_t ih, uint32_t lh) {
+    w.G = (n1.x << 8) | ih;
+    w.tw = n1.y | (lh << 24);
+    w.rank = n1.z;
+}
+
+// The loads of a trip.  Every lane loads the same number of words (a node is 5 x 16 bytes, a triangle 3 in Float32 and 6 in Float64 — NT; the
+// arrays are padded by one record): a wave-instruction costs the memory pipeline the same whichever lanes take part, and loads under a condition
+// would be sunk behind the other arm's arithmetic — a second round trip.  The empty asm pins all of them ahead of both arms.
+__device__ __forceinline__ void walk_pin(const uint4 a, const uint4 b, const uint4 c) {
+    asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(c.x), "v"(c.y), "v"(c.z), "v"(c.w) : "memory");
+}
+__device__ __forceinline__ void walk_pin(const uint4 a, const uint4 b) {
+    asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w) : "memory");
+}
+__device__ __forceinline__ void walk_pin(const uint4 a) { asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w) : "memory"); }
+template <class T> constexpr int kTriWords = sizeof(T) == 8 ? 6 : 3;      // NT of a triangle record in T
+// One record, a node's or a triangle's, through one pointer.  WRITTEN (the ray walks in Float64): as the six aligned 16-byte loads they are.  Left to
+// itself the compiler regroups the words by their later use into loads at odd offsets (dwordx4 at +4, dwordx2 at +0, dwordx3 at +68 ...): -2.5 % on
+// config 5.  (In Float32 its grouping is the faster one by 5 %: register allocation; the distance, sweep and overlap walks were tuned on it in both.)
+template <int NT, bool WRITTEN>
+__device__ __forceinline__ void walk_load_one(const uint4 *ptr, uint4 &w0, uint4 &w1, uint4 &w2, uint4 &w3, uint4 &w4, uint4 &w5) {
+    w5 = make_uint4(0, 0, 0, 0);
+    if constexpr (WRITTEN && NT == 6) {
         typedef uint32_t U4 __attribute__((ext_vector_type(4)));
         U4 q0, q1, q2, q3, q4, q5;
         asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:16\n\tglobal_load_dwordx4 %2, %6, off offset:32\n\t"
@@ -747,89 +666,149 @@ __device__ __forceinline__ bool bvh8_step(const SceneLds<T> &sc, Bvh8Walk<T> &w,
         w3 = make_uint4(q3.x, q3.y, q3.z, q3.w); w4 = make_uint4(q4.x, q4.y, q4.z, q4.w); w5 = make_uint4(q5.x, q5.y, q5.z, q5.w);
     } else {
         w0 = ptr[0]; w1 = ptr[1]; w2 = ptr[2]; w3 = ptr[3]; w4 = ptr[4];
-        asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-        asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
+        if constexpr (NT == 6) w5 = ptr[5];
+        walk_pin(w0, w1, w2);
+        walk_pin(w3, w4);
+        if constexpr (NT == 6) walk_pin(w5);
     }
-    if (is_tri) {
-        Pack4<T> v0, e1, e2;
-        bvh8_tri_words(w0, w1, w2, w3, w4, w5, v0, e1, e2);
-        T t;
-        if (triangle_test<T>(v0, e1, e2, o, d, t_min, closest, t)) {
-            const int p = base + (int)Bits<T>::to_u32(v0.w);
-            if (t < closest || p > prim) {                                // t == closest: the later object wins
-                closest = t; prim = p; slot = ti;
-                r.best = bvh8_best((float)((t - w.t0) * sc.bvh_root[2].w));
-            }
-        }
-    } else {
-        uint32_t ih, lh;
-        bvh8_node(w0, w1, w2, w3, w4, r, ih, lh);
-        w.G = (w1.x << 8) | ih;
-        w.tw = w1.y | (lh << 24);
-        w.rank = w1.z;
-    }
-    if ((w.tw >> 24) == 0 && !(w.G & 0xFFu)) {
-        if (w.sp == 0) return false;
-        --w.sp;
-        w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL];
-    }
-    return true;
+}
+// The node record and the triangle record of a trip that takes both.
+template <int NT>
+__device__ __forceinline__ void walk_load_two(const uint4 *pn, const uint4 *pt, uint4 &n0, uint4 &n1, uint4 &n2, uint4 &n3, uint4 &n4,
+                                              uint4 &u0, uint4 &u1, uint4 &u2, uint4 &u3, uint4 &u4, uint4 &u5) {
+    n0 = pn[0]; n1 = pn[1]; n2 = pn[2]; n3 = pn[3]; n4 = pn[4];
+    u0 = pt[0]; u1 = pt[1]; u2 = pt[2];
+    u3 = u4 = u5 = make_uint4(0, 0, 0, 0);
+    if constexpr (NT == 6) { u3 = pt[3]; u4 = pt[4]; u5 = pt[5]; }
+    walk_pin(n0, n1, n2);
+    walk_pin(n3, n4);
+    walk_pin(u0, u1, u2);
+    if constexpr (NT == 6) walk_pin(u3, u4, u5);
 }
 
-// The screened trip of a traversal SESSION's Float64 walk (k_path): the same trip as the kScreen branch of bvh8_step, but the lane carries nothing of its ray
-// in Float64 — direction in Float32, origin = the entry point inside Bvh8Ray — because the Float64 tests of its candidates run outside the walk's loop,
-// from the parked entry re-read there.  Returns 0: the walk is over; 1: go on; 2: the candidate list is full (nothing was done: the caller empties it).
+// TWO items per trip, the ray walks' other form: the lane's pending triangle AND, once that was the node's last pending one, its next node visit, both
+// fetched in the same round trip (the order of tests does not change the result: minimal t, ties to the later triangle).  `tris` holds records of NT
+// words and the leaf gets the raw words, `leaf(ti, u0 .. u5)`: T records for bvh8_trip, the Float32 copies (3 words) for the screened Float64 walks.
+// Returns false when the walk is over.
+template <int KL, int NT, class W, class Leaf>
+__device__ __forceinline__ bool walk_trip_two(const uint4 *nodes, const uint4 *tris, W &w, Bvh8Ray &r, uint32_t *lds_stack, uint32_t *stack, uint32_t lane, const Leaf &leaf) {
+    const bool do_tri = (w.tw >> 24) != 0;
+    uint32_t ti = 0;
+    const uint4 *pt = tris;
+    if (do_tri) {
+        ti = walk_take_tri(w);
+        pt = tris + NT * (size_t)ti;
+    }
+    const bool do_node = (w.tw >> 24) == 0 && walk_pop<KL>(w, lds_stack, stack, lane);
+    const uint4 *pn = nodes;
+    if (do_node) pn = nodes + 5 * (size_t)walk_take_group<KL>(w, r.oct, lds_stack, stack, lane);
+    uint4 n0, n1, n2, n3, n4, u0, u1, u2, u3, u4, u5;
+    walk_load_two<NT>(pn, pt, n0, n1, n2, n3, n4, u0, u1, u2, u3, u4, u5);
+    if (do_tri) leaf(ti, u0, u1, u2, u3, u4, u5);
+    if (do_node) {
+        uint32_t ih, lh;
+        bvh8_node(n0, n1, n2, n3, n4, r, ih, lh);
+        walk_set_node(w, n1, ih, lh);
+    }
+    return (w.tw >> 24) != 0 || (w.G & 0xFFu) != 0 || w.sp > 0;
+}
+
+// The ray walks' trip; the triangle test runs in render precision on the caller's coordinates (the scan's own test) inside `leaf(ti, v0, e1, e2)`.
+// Float32 takes TWO items per trip: trips per ray 12.0 -> 10.4; with the 128 registers the second launch of a mesh pass has in Float32 that is config 5
+// 3.83 -> 3.69 ms.  (It lost 5 % while that kernel was held to 96 registers and spilled 60 of them, and in Float64 — six more words to hold — it still
+// gains nothing: 5.13 -> 5.20 ms; Float64 keeps one item per trip unless built with SPIRA_BVH_DUAL_F64.)  Returns false when the walk is over.
+template <class T, int KL, class Leaf>
+__device__ __forceinline__ bool bvh8_trip(const SceneLds<T> &sc, Bvh8Walk<T> &w, Bvh8Ray &r, uint32_t *lds_stack, uint32_t *stack, uint32_t lane, const Leaf &leaf) {
+#ifdef SPIRA_BVH_DUAL_F64
+    constexpr bool kDual = true;
+#else
+    constexpr bool kDual = sizeof(T) != 8;
+#endif
+    if constexpr (kDual) {
+        return walk_trip_two<KL, kTriWords<T>>(sc.bvh_nodes, reinterpret_cast<const uint4 *>(sc.bvh_tris), w, r, lds_stack, stack, lane,
+            [&](uint32_t ti, const uint4 u0, const uint4 u1, const uint4 u2, const uint4 u3, const uint4 u4, const uint4 u5) {
+                Pack4<T> v0, e1, e2;
+                bvh8_tri_words(u0, u1, u2, u3, u4, u5, v0, e1, e2);
+                leaf(ti, v0, e1, e2);
+            });
+    } else {
+        const bool is_tri = (w.tw >> 24) != 0;
+        const uint4 *ptr;
+        uint32_t ti = 0;
+        if (is_tri) {
+            ti = walk_take_tri(w);
+            ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
+        } else ptr = sc.bvh_nodes + 5 * (size_t)walk_take_group<KL>(w, r.oct, lds_stack, stack, lane);
+        uint4 w0, w1, w2, w3, w4, w5;
+        walk_load_one<kTriWords<T>, true>(ptr, w0, w1, w2, w3, w4, w5);
+        if (is_tri) {
+            Pack4<T> v0, e1, e2;
+            bvh8_tri_words(w0, w1, w2, w3, w4, w5, v0, e1, e2);
+            leaf(ti, v0, e1, e2);
+        } else {
+            uint32_t ih, lh;
+            bvh8_node(w0, w1, w2, w3, w4, r, ih, lh);
+            walk_set_node(w, w1, ih, lh);
+        }
+        return walk_pop<KL>(w, lds_stack, stack, lane);
+    }
+}
+
+// The leaf arm of the screened Float64 trips (tri_screen_f32): a triangle that may be hit joins the lane's candidate list — `full()` first makes room in
+// a full one; its Float64 test is run by bvh8_resolve_one() or by the session, in batches.
+template <class Full>
+__device__ __forceinline__ void bvh8_screen_leaf(Bvh8Walk<double> &w, Bvh8Ray &r, uint32_t ti, const uint4 u0, const uint4 u1, const uint4 u2, float dx, float dy, float dz, const Full &full) {
+    float t_hi;
+    const int cls = tri_screen_f32(u0, u1, u2, r, dx, dy, dz, t_hi);
+    if (cls != 0) {
+        full();
+        w.c3 = w.c2; w.c2 = w.c1; w.c1 = w.c0; w.c0 = ti; ++w.nc;
+        if (cls == 2) r.best = __builtin_fminf(r.best, t_hi);
+    }
+}
+
+// One trip of the closest-hit walk.  Returns false when the walk is over.
+template <class T, int KL>
+__device__ __forceinline__ bool bvh8_step(const SceneLds<T> &sc, Bvh8Walk<T> &w, Bvh8Ray &r, Vec<T> o, Vec<T> d, T t_min, int base, T &closest, int &prim, uint32_t &slot,
+                                          uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
+#ifdef SPIRA_BVH_SCREEN
+    constexpr bool kScreen = sizeof(T) == 8;          // experiment build (see tri_screen_f32): measured 2 .. 6 % SLOWER than testing every triangle in Float64 where it is met
+#else
+    constexpr bool kScreen = false;
+#endif
+    if constexpr (kScreen) {
+        // Float64: the Float32 walk's trip (5 + 3 loads), the triangle SCREENED in Float32
+        return walk_trip_two<KL, 3>(sc.bvh_nodes, sc.bvh_tris32, w, r, lds_stack, stack, lane,
+            [&](uint32_t ti, const uint4 u0, const uint4 u1, const uint4 u2, const uint4, const uint4, const uint4) {
+                // a full list is emptied on the spot (rare: a ray grazing many triangles): this lane's candidates all go through the exact test now
+                bvh8_screen_leaf(w, r, ti, u0, u1, u2, (float)d.x, (float)d.y, (float)d.z,
+                                 [&]() { if (__builtin_expect(w.nc == kBvhCand, 0)) { while (w.nc) bvh8_resolve_one<T>(sc, w, r, o, d, t_min, base, closest, prim, slot); } });
+            });
+    } else {
+        return bvh8_trip<T, KL>(sc, w, r, lds_stack, stack, lane, [&](uint32_t ti, const Pack4<T> v0, const Pack4<T> e1, const Pack4<T> e2) {
+            T t;
+            if (triangle_test<T>(v0, e1, e2, o, d, t_min, closest, t)) {
+                const int p = base + (int)Bits<T>::to_u32(v0.w);
+                if (t < closest || p > prim) {                                // t == closest: the later object wins
+                    closest = t; prim = p; slot = ti;
+                    r.best = bvh8_best((float)((t - w.t0) * sc.bvh_root[2].w));
+                }
+            }
+        });
+    }
+}
+
+// The screened trip of a traversal SESSION's Float64 walk (k_path): the kScreen trip of bvh8_step, but the lane carries nothing of its ray in Float64 —
+// direction in Float32, origin = the entry point inside Bvh8Ray — because the Float64 tests of its candidates run outside the walk's loop, from the
+// parked entry re-read there.  Returns 0: the walk is over; 1: go on; 2: the candidate list is full (nothing was done: the caller empties it).
 enum : int { kWalkDone = 0, kWalkOn = 1, kWalkFull = 2 };
 template <int KL>
 __device__ __forceinline__ int bvh8_step_screened(const uint4 *nodes, const uint4 *tris32, Bvh8Walk<double> &w, Bvh8Ray &r, float dx, float dy, float dz,
                                                   uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
     if (__builtin_expect(w.nc == kBvhCand, 0)) return kWalkFull;
-    const bool do_tri = (w.tw >> 24) != 0;
-    uint32_t ti = 0;
-    const uint4 *pt = tris32;
-    if (do_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);
-        ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        pt = tris32 + 3 * (size_t)ti;
-    }
-    bool do_node = (w.tw >> 24) == 0;
-    if (do_node && !(w.G & 0xFFu)) {
-        if (w.sp == 0) do_node = false;
-        else { --w.sp; w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL]; }
-    }
-    const uint4 *pn = nodes;
-    if (do_node) {
-        const uint32_t pos = (uint32_t)__builtin_ctz(w.G);
-        const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-        w.G &= w.G - 1u;
-        if (w.G & 0xFFu) {
-            if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-            ++w.sp;
-        }
-        pn = nodes + 5 * (size_t)idx;
-    }
-    const uint4 n0 = pn[0], n1 = pn[1], n2 = pn[2], n3 = pn[3], n4 = pn[4];
-    const uint4 u0 = pt[0], u1 = pt[1], u2 = pt[2];
-    asm volatile("" :: "v"(n0.x), "v"(n0.y), "v"(n0.z), "v"(n0.w), "v"(n1.x), "v"(n1.y), "v"(n1.z), "v"(n1.w), "v"(n2.x), "v"(n2.y), "v"(n2.z), "v"(n2.w) : "memory");
-    asm volatile("" :: "v"(n3.x), "v"(n3.y), "v"(n3.z), "v"(n3.w), "v"(n4.x), "v"(n4.y), "v"(n4.z), "v"(n4.w) : "memory");
-    asm volatile("" :: "v"(u0.x), "v"(u0.y), "v"(u0.z), "v"(u0.w), "v"(u1.x), "v"(u1.y), "v"(u1.z), "v"(u1.w), "v"(u2.x), "v"(u2.y), "v"(u2.z), "v"(u2.w) : "memory");
-    if (do_tri) {
-        float t_hi;
-        const int cls = tri_screen_f32(u0, u1, u2, r, dx, dy, dz, t_hi);
-        if (cls != 0) {
-            w.c3 = w.c2; w.c2 = w.c1; w.c1 = w.c0; w.c0 = ti; ++w.nc;
-            if (cls == 2) r.best = __builtin_fminf(r.best, t_hi);
-        }
-    }
-    if (do_node) {
-        uint32_t ih, lh;
-        bvh8_node(n0, n1, n2, n3, n4, r, ih, lh);
-        w.G = (n1.x << 8) | ih;
-        w.tw = n1.y | (lh << 24);
-        w.rank = n1.z;
-    }
-    return ((w.tw >> 24) != 0 || (w.G & 0xFFu) != 0 || w.sp > 0) ? kWalkOn : kWalkDone;
+    const bool on = walk_trip_two<KL, 3>(nodes, tris32, w, r, lds_stack, stack, lane,
+        [&](uint32_t ti, const uint4 u0, const uint4 u1, const uint4 u2, const uint4, const uint4, const uint4) { bvh8_screen_leaf(w, r, ti, u0, u1, u2, dx, dy, dz, []() {}); });
+    return on ? kWalkOn : kWalkDone;
 }
 
 // `closest` / `prim` come in holding the best hit so far (spheres, LDS triangles) and go out updated; `slot` is the hit triangle's

@@ -216,7 +216,7 @@ __device__ __forceinline__ void hits_scan_local(const SceneLds<T> &sc, Vec<T> o,
 }
 
 // The leaf arm of a trip: the scan's own test of one tree triangle against the lane's bound; after an insertion into a full list the Float32 side's
-// bound follows the new K-th t, as bvh8_step's follows `closest`.
+// bound follows the new K-th t, as the closest-hit leaf's follows `closest`.
 template <class T, int CAP>
 __device__ __forceinline__ void hits8_leaf(const SceneLds<T> &sc, const Bvh8Walk<T> &w, Bvh8Ray &r, Vec<T> o, Vec<T> d, T t_min, int base, const Pack4<T> v0, const Pack4<T> e1,
                                            const Pack4<T> e2, HitsLane<T, CAP> &h, uint32_t K, bool count_all) {
@@ -227,116 +227,15 @@ __device__ __forceinline__ void hits8_leaf(const SceneLds<T> &sc, const Bvh8Walk
     }
 }
 
-// The multi-hit twin of bvh8_step (spira_device.h): the same trip — ONE memory round trip, every lane's loads issued through one pointer per kind and
-// pinned ahead of both arms, Float32 taking a node's last pending triangle AND the next node visit together — over the same Bvh8Walk, stack and node
-// test; only the leaf arm differs (hits8_leaf).  The Float32-screen experiment of the closest-hit walk is not carried over: Float64 tests every triangle
-// exactly where it is met.  Returns false when the walk is over.
+// One trip of the multi-hit walk: bvh8_trip (spira_device.h) over the same Bvh8Walk, stack and node test as the closest-hit walk, with hits8_leaf as its
+// leaf arm.  The Float32-screen experiment of the closest-hit walk is not carried over: Float64 tests every triangle exactly where it is met.  Returns
+// false when the walk is over.
 template <class T, int KL, int CAP>
 __device__ __forceinline__ bool hits8_step(const SceneLds<T> &sc, Bvh8Walk<T> &w, Bvh8Ray &r, Vec<T> o, Vec<T> d, T t_min, int base, HitsLane<T, CAP> &h, uint32_t K, bool count_all,
                                            uint32_t *lds_stack, uint32_t *stack, uint32_t lane) {
-    constexpr bool kWide = sizeof(T) == 8;
-#ifdef SPIRA_BVH_DUAL_F64
-    constexpr bool kDual = true;
-#else
-    constexpr bool kDual = !kWide;
-#endif
-    if constexpr (kDual) {
-        const bool do_tri = (w.tw >> 24) != 0;
-        const uint4 *pt = reinterpret_cast<const uint4 *>(sc.bvh_tris);
-        if (do_tri) {
-            const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);
-            const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-            w.tw &= ~(0x01000000u << s_);
-            pt = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-        }
-        bool do_node = (w.tw >> 24) == 0;
-        if (do_node && !(w.G & 0xFFu)) {
-            if (w.sp == 0) do_node = false;
-            else { --w.sp; w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL]; }
-        }
-        const uint4 *pn = sc.bvh_nodes;
-        if (do_node) {
-            const uint32_t pos = (uint32_t)__builtin_ctz(w.G);
-            const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-            w.G &= w.G - 1u;
-            if (w.G & 0xFFu) {
-                if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-                ++w.sp;
-            }
-            pn = sc.bvh_nodes + 5 * (size_t)idx;
-        }
-        const uint4 n0 = pn[0], n1 = pn[1], n2 = pn[2], n3 = pn[3], n4 = pn[4];
-        const uint4 u0 = pt[0], u1 = pt[1], u2 = pt[2], uz = make_uint4(0, 0, 0, 0);
-        uint4 u3 = uz, u4 = uz, u5 = uz;
-        if constexpr (kWide) { u3 = pt[3]; u4 = pt[4]; u5 = pt[5]; }
-        asm volatile("" :: "v"(n0.x), "v"(n0.y), "v"(n0.z), "v"(n0.w), "v"(n1.x), "v"(n1.y), "v"(n1.z), "v"(n1.w), "v"(n2.x), "v"(n2.y), "v"(n2.z), "v"(n2.w) : "memory");
-        asm volatile("" :: "v"(n3.x), "v"(n3.y), "v"(n3.z), "v"(n3.w), "v"(n4.x), "v"(n4.y), "v"(n4.z), "v"(n4.w) : "memory");
-        asm volatile("" :: "v"(u0.x), "v"(u0.y), "v"(u0.z), "v"(u0.w), "v"(u1.x), "v"(u1.y), "v"(u1.z), "v"(u1.w), "v"(u2.x), "v"(u2.y), "v"(u2.z), "v"(u2.w) : "memory");
-        if constexpr (kWide) asm volatile("" :: "v"(u3.x), "v"(u3.y), "v"(u3.z), "v"(u3.w), "v"(u4.x), "v"(u4.y), "v"(u4.z), "v"(u4.w), "v"(u5.x), "v"(u5.y), "v"(u5.z), "v"(u5.w) : "memory");
-        if (do_tri) {
-            Pack4<T> v0, e1, e2;
-            bvh8_tri_words(u0, u1, u2, u3, u4, u5, v0, e1, e2);
-            hits8_leaf<T, CAP>(sc, w, r, o, d, t_min, base, v0, e1, e2, h, K, count_all);
-        }
-        if (do_node) {
-            uint32_t ih, lh;
-            bvh8_node(n0, n1, n2, n3, n4, r, ih, lh);
-            w.G = (n1.x << 8) | ih;
-            w.tw = n1.y | (lh << 24);
-            w.rank = n1.z;
-        }
-        return (w.tw >> 24) != 0 || (w.G & 0xFFu) != 0 || w.sp > 0;
-    }
-    const bool is_tri = (w.tw >> 24) != 0;
-    const uint4 *ptr;
-    if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next hit leaf slot; its triangle: tri_base + rank of the slot
-        const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-    } else {
-        const uint32_t pos = (uint32_t)__builtin_ctz(w.G);                 // (the low byte is never empty here)
-        const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-        w.G &= w.G - 1u;
-        if (w.G & 0xFFu) {                                                 // siblings left: keep the group
-            if (KL > 0 && w.sp < KL) lds_stack[w.sp * 64 + lane] = w.G; else stack[w.sp - KL] = w.G;
-            ++w.sp;
-        }
-        ptr = sc.bvh_nodes + 5 * (size_t)idx;
-    }
-    // every lane loads the same number of words (both arrays are padded by one record), all of them ahead of both arms: bvh8_step's reasons
-    uint4 w0, w1, w2, w3, w4, w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) {
-        typedef uint32_t U4 __attribute__((ext_vector_type(4)));
-        U4 q0, q1, q2, q3, q4, q5;
-        asm volatile("global_load_dwordx4 %0, %6, off\n\tglobal_load_dwordx4 %1, %6, off offset:16\n\tglobal_load_dwordx4 %2, %6, off offset:32\n\t"
-                     "global_load_dwordx4 %3, %6, off offset:48\n\tglobal_load_dwordx4 %4, %6, off offset:64\n\tglobal_load_dwordx4 %5, %6, off offset:80\n\t"
-                     "s_waitcnt vmcnt(0)"
-                     : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "=&v"(q4), "=&v"(q5) : "v"(ptr) : "memory");
-        w0 = make_uint4(q0.x, q0.y, q0.z, q0.w); w1 = make_uint4(q1.x, q1.y, q1.z, q1.w); w2 = make_uint4(q2.x, q2.y, q2.z, q2.w);
-        w3 = make_uint4(q3.x, q3.y, q3.z, q3.w); w4 = make_uint4(q4.x, q4.y, q4.z, q4.w); w5 = make_uint4(q5.x, q5.y, q5.z, q5.w);
-    } else {
-        w0 = ptr[0]; w1 = ptr[1]; w2 = ptr[2]; w3 = ptr[3]; w4 = ptr[4];
-        asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-        asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
-    }
-    if (is_tri) {
-        Pack4<T> v0, e1, e2;
-        bvh8_tri_words(w0, w1, w2, w3, w4, w5, v0, e1, e2);
+    return bvh8_trip<T, KL>(sc, w, r, lds_stack, stack, lane, [&](uint32_t, const Pack4<T> v0, const Pack4<T> e1, const Pack4<T> e2) {
         hits8_leaf<T, CAP>(sc, w, r, o, d, t_min, base, v0, e1, e2, h, K, count_all);
-    } else {
-        uint32_t ih, lh;
-        bvh8_node(w0, w1, w2, w3, w4, r, ih, lh);
-        w.G = (w1.x << 8) | ih;
-        w.tw = w1.y | (lh << 24);
-        w.rank = w1.z;
-    }
-    if ((w.tw >> 24) == 0 && !(w.G & 0xFFu)) {
-        if (w.sp == 0) return false;
-        --w.sp;
-        w.G = (KL > 0 && w.sp < KL) ? lds_stack[w.sp * 64 + lane] : stack[w.sp - KL];
-    }
-    return true;
+    });
 }
 
 // One lane per ray.  Launches: <T, false, false, .> spheres alone, <T, false, true, .> with LDS triangles, <T, true, false, .> a BVH mesh (SPIRA_CAST_INPLACE).

@@ -12,7 +12,7 @@
 // candidates cannot matter: the refilled sessions and the in-place walk give the same bytes, and K = 1 gives spira_scene_closest_point_*'s answer.
 //
 // Pruning.  bound = best0 until the lane's list holds K entries, then the list's last d2 (the K-th so far); under SPIRA_NEAR_COUNT_ALL it stays best0.
-// An object met — in LDS or in a leaf — is a candidate when d2 <= bound; near_insert places it by index.  The tree step is near_step with `bound` in the
+// An object met — in LDS or in a leaf — is a candidate when d2 <= bound; near_insert places it by index.  The tree step is near_trip with `bound` in the
 // place of `best`: bestn = near_bestn(bound, scale), recomputed whenever the list is full after an insertion; near_node's strict test, the nearest
 // surviving child first and the one deferred-children entry per node are as they are, so the stack bound (one entry per level) is unchanged.  Exact:
 //   (1) the safety proof of spira_nearest.h ("Why pruning is safe") shows that every triangle of a skipped child has a scan d2 STRICTLY beyond the value
@@ -264,63 +264,13 @@ __device__ __forceinline__ void knear_scan_local(const KNearArgs<T> &a, const Sc
         }
 }
 
-// The K-nearest twin of near_step (spira_nearest.h): the same trip — ONE memory round trip, every lane's loads issued ahead of both arms — over the same
-// NearWalk, stack and node test; only the leaf arm differs: the triangle is offered to the list, and bestn follows the bound when the list is full.
-// Returns false when the walk is over.
+// One trip of the K-nearest walk: near_trip (spira_nearest.h) over the same NearWalk, stack and node test as the closest-point walk; the triangle is
+// offered to the list, and bestn follows the bound when the list is full.  Returns false when the walk is over.
 template <class T, int CAP>
 __device__ __forceinline__ bool knear_step(const SceneLds<T> &sc, NearWalk<T> &w, int base, KNearLane<T, CAP> &h, uint32_t K, bool count_all, uint32_t *stack) {
-    constexpr bool kWide = sizeof(T) == 8;
-    const bool is_tri = (w.tw >> 24) != 0;
-    const uint4 *ptr;
-    uint32_t idx = 0, allow = 0, ti = 0;
-    if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next surviving leaf slot; its triangle: tri_base + rank of the slot
-        ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-    } else {
-        idx = w.G >> 8; allow = w.G & 0xFFu;                               // (never empty here)
-        w.G = 0;
-        ptr = sc.bvh_nodes + 5 * (size_t)idx;
-    }
-    ++w.trips;
-    // every lane loads the same number of words, all of them ahead of both arms: near_step's reasons
-    const uint4 w0 = ptr[0], w1 = ptr[1], w2 = ptr[2], w3 = ptr[3], w4 = ptr[4];
-    uint4 w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) w5 = ptr[5];
-    asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-    asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
-    if constexpr (kWide) asm volatile("" :: "v"(w5.x), "v"(w5.y), "v"(w5.z), "v"(w5.w) : "memory");
-    if (is_tri) {
-        Pack4<T> a0, a1, a2;
-        bvh8_tri_words(w0, w1, w2, w3, w4, w5, a0, a1, a2);
-        const T v0[3] = {a0.x, a0.y, a0.z}, e1[3] = {a1.x, a1.y, a1.z}, e2[3] = {a2.x, a2.y, a2.z};
-        T q[3], d2;
-        closest_point_triangle<T>(v0, e1, e2, w.p, q, d2);
-        const int p = base + (int)Bits<T>::to_u32(a0.w);
+    return near_trip<T>(sc, w, base, stack, [&](uint32_t ti, const T q[3], T d2, int p) {
         if (near_offer<T, CAP>(h.l, K, count_all, d2, p, knear_pay<T, CAP>(q, ti), h.best0, w.best, h.total)) w.bestn = near_bestn<T>(w.best, sc.bvh_root[2].w);
-    } else {
-        float d2[8];
-        const uint32_t imask = w0.w >> 24;
-        const uint32_t surv = near_node(w0, w2, w3, w4, w.nx, w.ny, w.nz, w.bestn, d2) & allow;
-        const uint32_t ih = surv & imask;
-        w.tw = w1.y | ((surv & ~imask) << 24);
-        w.rank = w1.z;
-        if (ih) {
-            uint32_t j = 0; float dj = 3.0e38f;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) if (((ih >> s) & 1u) && d2[s] < dj) { dj = d2[s]; j = (uint32_t)s; }
-            if (!((ih >> j) & 1u)) j = (uint32_t)__builtin_ctz(ih);        // (near_step's: kept total)
-            const uint32_t rest = ih & ~(1u << j);
-            if (rest) stack[w.sp++] = (idx << 8) | rest;                   // ONE entry for this node: its deferred children
-            w.G = ((w1.x + j) << 8) | 0xFFu;
-        }
-    }
-    if ((w.tw >> 24) == 0 && w.G == 0) {
-        if (w.sp == 0) return false;
-        w.G = stack[--w.sp];
-    }
-    return true;
+    });
 }
 
 // One lane per point.  Launches: <T, false, false, .> spheres alone, <T, false, true, .> with LDS triangles, <T, true, false, .> a BVH mesh (SPIRA_CAST_INPLACE).

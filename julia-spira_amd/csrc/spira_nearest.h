@@ -55,7 +55,7 @@
 //                              contiguous ranges of the point list (session_range over a CastPlan), free lanes refill by ballot and popcount prefix while
 //                              the others keep walking, a finished lane stores straight to out[point].  The kernel is the two callables: start = near_load,
 //                              near_scan_local, near_enter; step = near_step.
-// The walk (near_step): ONE memory round trip per trip — a triangle record for a lane with leaf children pending (the scan's own function on the record's
+// The walk (near_trip, whose leaf near_step supplies; the pieces of a trip: spira_device.h, "one TRIP"): ONE memory round trip per trip — a triangle record for a lane with leaf children pending (the scan's own function on the record's
 // own values, in T: the tree only prunes), else a node: its eight child boxes are dequantised, each child's squared distance is computed, children
 // proven farther than best are dropped, the surviving leaves become the pending triangles and the NEAREST surviving child node is visited next.
 // The stack: the other surviving child nodes are deferred as ONE entry, (slot of THIS node) << 8 | their bit mask.  A popped entry is a trip that fetches that
@@ -250,17 +250,16 @@ __device__ __forceinline__ uint32_t near_node(const uint4 w0, const uint4 w2, co
     return surv;
 }
 
-// One trip = ONE memory round trip (header comment, "The walk").  Returns false when the walk is over.
-template <class T>
-__device__ __forceinline__ bool near_step(const SceneLds<T> &sc, NearWalk<T> &w, int base, uint32_t *stack) {
-    constexpr bool kWide = sizeof(T) == 8;
+// One trip of the distance walks = ONE memory round trip (header comment, "The walk"; the pieces and why the loads are what they are: spira_device.h,
+// "one TRIP").  The leaf arm is the scan's own function on the record; what becomes of the triangle is the caller's, `leaf(ti, q, d2, p)`.  The node arm
+// visits the nearest surviving child first and keeps ONE deferred entry per node.  Returns false when the walk is over.
+template <class T, class Leaf>
+__device__ __forceinline__ bool near_trip(const SceneLds<T> &sc, NearWalk<T> &w, int base, uint32_t *stack, const Leaf &leaf) {
     const bool is_tri = (w.tw >> 24) != 0;
     const uint4 *ptr;
-    uint32_t idx = 0, allow = 0;
+    uint32_t idx = 0, allow = 0, ti = 0;
     if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next surviving leaf slot; its triangle: tri_base + rank of the slot
-        const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
+        ti = walk_take_tri(w);
         ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
     } else {
         idx = w.G >> 8; allow = w.G & 0xFFu;                               // (never empty here)
@@ -268,25 +267,15 @@ __device__ __forceinline__ bool near_step(const SceneLds<T> &sc, NearWalk<T> &w,
         ptr = sc.bvh_nodes + 5 * (size_t)idx;
     }
     ++w.trips;
-    // Every lane loads the same number of words (a node is 5 x 16 bytes, a triangle 3 in Float32 and 6 in Float64; both arrays are padded by one record),
-    // all of them ahead of both arms, as bvh8_step does: loads under a condition would be sunk behind the other arm's arithmetic — a second round trip.
-    const uint4 w0 = ptr[0], w1 = ptr[1], w2 = ptr[2], w3 = ptr[3], w4 = ptr[4];
-    uint4 w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) w5 = ptr[5];
-    asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-    asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
-    if constexpr (kWide) asm volatile("" :: "v"(w5.x), "v"(w5.y), "v"(w5.z), "v"(w5.w) : "memory");
+    uint4 w0, w1, w2, w3, w4, w5;
+    walk_load_one<kTriWords<T>, false>(ptr, w0, w1, w2, w3, w4, w5);
     if (is_tri) {
         Pack4<T> a0, a1, a2;
         bvh8_tri_words(w0, w1, w2, w3, w4, w5, a0, a1, a2);
         const T v0[3] = {a0.x, a0.y, a0.z}, e1[3] = {a1.x, a1.y, a1.z}, e2[3] = {a2.x, a2.y, a2.z};
         T q[3], d2;
         closest_point_triangle<T>(v0, e1, e2, w.p, q, d2);
-        const int p = base + (int)Bits<T>::to_u32(a0.w);
-        if (d2 < w.best || (d2 == w.best && p > w.prim)) {                 // d2 == best: the later object wins, whatever the order of the visits
-            w.best = d2; w.prim = p; w.q[0] = q[0]; w.q[1] = q[1]; w.q[2] = q[2];
-            w.bestn = near_bestn<T>(d2, sc.bvh_root[2].w);
-        }
+        leaf(ti, q, d2, base + (int)Bits<T>::to_u32(a0.w));
     } else {
         float d2[8];
         const uint32_t imask = w0.w >> 24;
@@ -309,6 +298,17 @@ __device__ __forceinline__ bool near_step(const SceneLds<T> &sc, NearWalk<T> &w,
         w.G = stack[--w.sp];
     }
     return true;
+}
+
+// One trip of the closest-point walk: a closer triangle replaces the winner, and bestn follows it.
+template <class T>
+__device__ __forceinline__ bool near_step(const SceneLds<T> &sc, NearWalk<T> &w, int base, uint32_t *stack) {
+    return near_trip<T>(sc, w, base, stack, [&](uint32_t, const T q[3], T d2, int p) {
+        if (d2 < w.best || (d2 == w.best && p > w.prim)) {                 // d2 == best: the later object wins, whatever the order of the visits
+            w.best = d2; w.prim = p; w.q[0] = q[0]; w.q[1] = q[1]; w.q[2] = q[2];
+            w.bestn = near_bestn<T>(d2, sc.bvh_root[2].w);
+        }
+    });
 }
 
 // One lane per point.  Launches: <T, false, false> spheres alone, <T, false, true> with LDS triangles, <T, true, false> a BVH mesh (SPIRA_CAST_INPLACE).

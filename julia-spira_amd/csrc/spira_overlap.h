@@ -53,9 +53,9 @@
 // and grown outward by  g = (max_k max(|lo_k|, |hi_k|) + 1) 2^-12  (Float32): qlo = lo - g, qhi = hi + g.  A child (lo <= hi on x: present — an empty
 // child has lo 255, hi 0) survives when its dequantised box [grid + ql step, grid + qh step] (near_node's planes: the product exact, the sum rounded once)
 // meets [qlo, qhi] on all three axes: six compares.  The bound is fixed, every surviving child is visited, a node with surviving siblings left keeps ONE
-// stack entry (child_base << 8 | their mask: sweep8_step's group, with no octant order), so the stack holds at most one entry per level; ONE memory round
-// trip per trip: a triangle record for a lane with leaf children pending — the SAT above, in T, on the record's own values: the tree only prunes — else a
-// node.  The builder partitions the triangles: a walk meets each at most once, and the list needs no duplicate suppression.
+// stack entry (child_base << 8 | their mask: the ray walks' group, with no octant order), so the stack holds at most one entry per level.  overlap_step
+// is the one trip of the project's walks (spira_device.h, "one TRIP") on its pieces: the leaf arm is the SAT above, in T, on the record's own values — the
+// tree only prunes — the node arm overlap_node.  The builder partitions the triangles: a walk meets each at most once, and the list needs no duplicate suppression.
 //
 // Why the growth suffices (normalised units; M = max(|lo|, |hi|) <= 128 by the origin and the extent rule, A = amax_n, u = 2^-24, u_T that of T).  A child
 // is wrongly skipped only if a triangle the SAT accepts lies in a child box that misses [qlo, qhi].
@@ -396,32 +396,17 @@ __device__ __forceinline__ uint32_t overlap_node(const uint4 w0, const uint4 w2,
     return surv;
 }
 
-// One trip = ONE memory round trip (header comment, "The walk").  Returns false when the walk is over.
+// One trip of the box walk = ONE memory round trip (header comment, "The walk"), on the pieces of spira_device.h ("one TRIP") with the overlap's own
+// arms; no octant (the children are taken in slot order), the stack is private.  Returns false when the walk is over.
 template <class T, int CAP>
 __device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<T, CAP> &w, int base, uint32_t K, uint32_t *stack) {
-    constexpr bool kWide = sizeof(T) == 8;
     const bool is_tri = (w.tw >> 24) != 0;
     const uint4 *ptr;
-    if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next surviving leaf slot; its triangle: tri_base + rank of the slot
-        const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-    } else {
-        const uint32_t pos = (uint32_t)__builtin_ctz(w.G);                 // (the low byte is never empty here)
-        const uint32_t idx = (w.G >> 8) + pos;
-        w.G &= w.G - 1u;
-        if (w.G & 0xFFu) stack[w.sp++] = w.G;                              // siblings left: keep the group
-        ptr = sc.bvh_nodes + 5 * (size_t)idx;
-    }
+    if (is_tri) ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)walk_take_tri(w));
+    else ptr = sc.bvh_nodes + 5 * (size_t)walk_take_group(w, 0u, stack);
     ++w.trips;
-    // Every lane loads the same number of words, all of them ahead of both arms, as near_step and sweep8_step do (both arrays are padded by one record).
-    const uint4 w0 = ptr[0], w1 = ptr[1], w2 = ptr[2], w3 = ptr[3], w4 = ptr[4];
-    uint4 w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) w5 = ptr[5];
-    asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-    asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
-    if constexpr (kWide) asm volatile("" :: "v"(w5.x), "v"(w5.y), "v"(w5.z), "v"(w5.w) : "memory");
+    uint4 w0, w1, w2, w3, w4, w5;
+    walk_load_one<kTriWords<T>, false>(ptr, w0, w1, w2, w3, w4, w5);
     if (is_tri) {
         Pack4<T> a0, a1, a2;
         bvh8_tri_words(w0, w1, w2, w3, w4, w5, a0, a1, a2);
@@ -434,11 +419,7 @@ __device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<
         w.tw = w1.y | ((surv & ~imask) << 24);
         w.rank = w1.z;
     }
-    if ((w.tw >> 24) == 0 && !(w.G & 0xFFu)) {
-        if (w.sp == 0) return false;
-        w.G = stack[--w.sp];
-    }
-    return true;
+    return walk_pop(w, stack);
 }
 
 // One lane per box.  Launches: <T, false, false, ..> spheres alone, <T, false, true, ..> with LDS triangles, <T, true, false, ..> a BVH mesh (SPIRA_CAST_INPLACE).

@@ -66,8 +66,8 @@
 // near planes and ((grid - origin) +- rn) 1/d for the far ones (upper signs: d_k >= 0), so the loop over the children costs what bvh8_node's does.  The
 // radius is added BEFORE the product with the clamped reciprocal: a ray parallel to a slab and inside its grown extent sees (-huge, +huge) as in bvh8_node,
 // one outside it an empty interval.  A grown empty child (lo 255, hi 0) could pass the slab test, so children are masked by lo <= hi, as near_node does.
-// sweep8_step makes ONE memory round trip per trip: a triangle record for a lane with leaf children pending — the leaf test above, in T, on the record's own
-// values: the tree only prunes — else a node.  best is tightened on every win; the tie rule is t < closest || p > prim.
+// sweep8_step is the one trip of the project's walks (spira_device.h, "one TRIP") on its pieces: the leaf arm is the leaf test above, in T, on the record's
+// own values — the tree only prunes — the node arm sweep8_node.  best is tightened on every win; the tie rule is t < closest || p > prim.
 //
 // Why 64 holds for the radius too.  Normalised units, A = amax_n, R = rs scale <= 64, u = 2^-24; a child is wrongly skipped only if the Float32 slab
 // test misses the path although c(t_k) lies inside the child's TRUE box grown by R.  Every triangle lies inside its child box shrunk by the builder's pad,
@@ -399,32 +399,17 @@ __device__ __forceinline__ void sweep8_node(const uint4 w0, const uint4 w2, cons
     ih = ihs;
 }
 
-// One trip = ONE memory round trip (header comment, "The walk").  Returns false when the walk is over.
+// One trip of the sweep = ONE memory round trip (header comment, "The walk"), on the pieces of spira_device.h ("one TRIP": what they do and why the
+// loads are what they are) with the sweep's own arms; the stack is private.  Returns false when the walk is over.
 template <class T>
 __device__ __forceinline__ bool sweep8_step(const SceneLds<T> &sc, SweepWalk<T> &w, Sweep8Ray &r, int base, uint32_t *stack) {
-    constexpr bool kWide = sizeof(T) == 8;
     const bool is_tri = (w.tw >> 24) != 0;
     const uint4 *ptr;
-    if (is_tri) {
-        const uint32_t s_ = (uint32_t)__builtin_ctz(w.tw >> 24);           // the next hit leaf slot; its triangle: tri_base + rank of the slot
-        const uint32_t ti = (w.tw & 0x00FFFFFFu) + ((w.rank >> (4u * s_)) & 15u);
-        w.tw &= ~(0x01000000u << s_);
-        ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)ti);
-    } else {
-        const uint32_t pos = (uint32_t)__builtin_ctz(w.G);                 // (the low byte is never empty here)
-        const uint32_t idx = (w.G >> 8) + (pos ^ r.oct);
-        w.G &= w.G - 1u;
-        if (w.G & 0xFFu) stack[w.sp++] = w.G;                              // siblings left: keep the group
-        ptr = sc.bvh_nodes + 5 * (size_t)idx;
-    }
+    if (is_tri) ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)walk_take_tri(w));
+    else ptr = sc.bvh_nodes + 5 * (size_t)walk_take_group(w, r.oct, stack);
     ++w.trips;
-    // Every lane loads the same number of words, all of them ahead of both arms, as bvh8_step and near_step do (both arrays are padded by one record).
-    const uint4 w0 = ptr[0], w1 = ptr[1], w2 = ptr[2], w3 = ptr[3], w4 = ptr[4];
-    uint4 w5 = make_uint4(0, 0, 0, 0);
-    if constexpr (kWide) w5 = ptr[5];
-    asm volatile("" :: "v"(w0.x), "v"(w0.y), "v"(w0.z), "v"(w0.w), "v"(w1.x), "v"(w1.y), "v"(w1.z), "v"(w1.w), "v"(w2.x), "v"(w2.y), "v"(w2.z), "v"(w2.w) : "memory");
-    asm volatile("" :: "v"(w3.x), "v"(w3.y), "v"(w3.z), "v"(w3.w), "v"(w4.x), "v"(w4.y), "v"(w4.z), "v"(w4.w) : "memory");
-    if constexpr (kWide) asm volatile("" :: "v"(w5.x), "v"(w5.y), "v"(w5.z), "v"(w5.w) : "memory");
+    uint4 w0, w1, w2, w3, w4, w5;
+    walk_load_one<kTriWords<T>, false>(ptr, w0, w1, w2, w3, w4, w5);
     if (is_tri) {
         Pack4<T> a0, a1, a2;
         bvh8_tri_words(w0, w1, w2, w3, w4, w5, a0, a1, a2);
@@ -440,15 +425,9 @@ __device__ __forceinline__ bool sweep8_step(const SceneLds<T> &sc, SweepWalk<T> 
     } else {
         uint32_t ih, lh;
         sweep8_node(w0, w2, w3, w4, r, ih, lh);
-        w.G = (w1.x << 8) | ih;
-        w.tw = w1.y | (lh << 24);
-        w.rank = w1.z;
+        walk_set_node(w, w1, ih, lh);
     }
-    if ((w.tw >> 24) == 0 && !(w.G & 0xFFu)) {
-        if (w.sp == 0) return false;
-        w.G = stack[--w.sp];
-    }
-    return true;
+    return walk_pop(w, stack);
 }
 
 // One lane per sweep.  Launches: <T, false, false, .> spheres alone, <T, false, true, .> with LDS triangles, <T, true, false, .> a BVH mesh (SPIRA_CAST_INPLACE).
