@@ -76,11 +76,14 @@ def head_on(rng, sc, n, lo=0.01, hi=0.10, dist=1.5):
 def grazing(rng, sc, n):
     """Paths tangent to the surface: through p + s r nrm along a direction perpendicular to nrm, for a surface point p with its normal nrm (a triangle's,
     a small sphere's), s = +-(0.9 .. 1.1) — the ball passes p at about its radius (or, on the inner side of a closed mesh, runs inside it).  The path
-    starts 1.5 extents before p and is 3 extents long."""
+    starts 1.5 extents before p and is 3 extents long.  Only triangles with area are drawn: a segment or a point has no normal, and a NaN sweep would
+    quietly join the invalid ones (a mesh whose triangles all have area draws exactly what it drew before)."""
     ext = S.target_box(sc)[3]
     tri = sc.get("triangles10")
     if tri is not None and len(tri):
-        v = np.asarray(tri, dtype=np.float64)[rng.integers(0, len(tri), n), :9].reshape(-1, 3, 3)
+        v = np.asarray(tri, dtype=np.float64)[:, :9].reshape(-1, 3, 3)
+        with_area = np.flatnonzero(np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]).any(axis=1))
+        v = v[with_area[rng.integers(0, len(with_area), n)]]
         a = rng.uniform(0.05, 0.9, (n, 1)); b = rng.uniform(0.02, 0.95, (n, 1)) * (1 - a)
         p = v[:, 0] + a * (v[:, 1] - v[:, 0]) + b * (v[:, 2] - v[:, 0])
         nrm = np.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
