@@ -8,7 +8,7 @@
 // + 1 resolve kernel, fully asynchronous on one HIP stream, the live-ray counts staying on the
 // device, and a pass carries `slots` samples of every pixel of the tile at once.
 // What a call launches and how large its workspaces are is decided in spira_plan.h (make_plan: pure arithmetic, swept on the CPU under sanitizers);
-// here render_impl<T> validates, plans, sizes the workspaces from the plan and calls the organisation's enqueue_* function, and verify_path_args
+// here Impl<T>::render validates, plans, sizes the workspaces from the plan and calls the organisation's enqueue_* function, and verify_path_args
 // checks every k_path launch against the buffers actually allocated.
 // Every entry point that enqueues on a context runs inside a Session: open (context, lock, stream, ordered after the previous call's end) ... close
 // (launch errors, the end event, a host caller's wait); render and adaptive render share prepare_path_call, FrameOut and begin/end_counters.  A launch
@@ -55,15 +55,18 @@
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
 // on another (profiles/r03_compiler_flags.md):
-//   SPIRA_TU_F32      render_impl<float> / trace_impl<float> and every kernel they launch, with -fno-slp-vectorize.  The SLP vectoriser pairs Float32
+//   SPIRA_TU_F32      spira_tu::Impl<float> (every Float32 entry: below) and every kernel its members launch, with -fno-slp-vectorize.  The SLP vectoriser pairs Float32
 //                     operations into v_pk_mul/add/fma_f32 and pays for every pair with register moves: without it S1 runs 13 % and the closed box S3
 //                     20 % faster in Float32 (Float64 has no packed arithmetic to form: indifferent, the mesh scene 4 % better off WITH the pass).
 //   SPIRA_TU_F64MESH  the Float64 path kernels of mesh scenes (k_path<double, ., BVH = true, ...>), with the compiler's defaults.
 //   SPIRA_TU_MAIN     the C ABI, the host runtime and every other Float64 kernel, with -mllvm -two-entry-phi-node-folding-threshold=1: SimplifyCFG then
 //                     turns far fewer two-sided branches into selects, which is 4 % of k_path on S1 in Float64 (1 % on the closed box) — and 5.5 % the
 //                     other way on the mesh kernels, hence their own unit.  (No effect on the Float32 kernels or the secondary Float64 ones.)
-// None of the macros defined (make stats, tests): one translation unit, the compiler's defaults.  The state below is shared by all units (inline
-// variables of a named namespace: one instance in the library); the functions further down are internal to each unit.
+// None of the macros defined (make stats, tests): one translation unit, the compiler's defaults, Impl<T> instantiated where it is called.  The state below
+// is shared by all units (inline variables of a named namespace: one instance in the library); the functions further down are internal to each unit, but
+// for the members of spira_tu::Impl<T>, which is how a Float32 call that enters through the C ABI in the SPIRA_TU_MAIN unit ends up in the SPIRA_TU_F32 one:
+// `extern template struct Impl<float>` in the first, `template struct Impl<float>` at the end of the second, and C++ does the rest.  Adding an entry: its declaration in
+// Impl, its definition (out of class, NOT inline, outside the unnamed namespace its helpers live in), the C wrappers, the header, _binding.py.
 #if (defined(SPIRA_TU_MAIN) + defined(SPIRA_TU_F32) + defined(SPIRA_TU_F64MESH)) > 1
 #error "SPIRA_TU_MAIN, SPIRA_TU_F32 and SPIRA_TU_F64MESH are three different translation units"
 #endif
@@ -71,63 +74,55 @@ struct spira_scene;
 // A host-output frame rendered as `count` consecutive row slabs (render_host_slabs): slab `index` > 0 continues the call of slab 0 — same scene (already in
 // the context's store), same counters and event brackets (they add up), and the caller holds the context's lock across all of them.
 struct SlabCtl { uint32_t index, count; };
-namespace spira_tu {      // defined in the SPIRA_TU_F32 unit, called from the SPIRA_TU_MAIN one
-int render_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                    float *out_hdr, float *out_img, bool out_on_device, void *user_stream, bool progressive, uint32_t sample0, uint32_t *rng_states, const SlabCtl *slab);
-int trace_impl_f32(const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                   uint32_t n_paths, const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance);
-int render_adaptive_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                             const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream);
-int features_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                      float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream);
-int denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
-                     float *out_hdr, float *out_img, bool on_device, void *user_stream);
-int scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
-int scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream);
-int cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
-                  bool any, bool on_device, void *user_stream);
-int nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point, uint32_t *out_trips,
-                     bool on_device, void *user_stream);
-int hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count,
-                  bool on_device, void *user_stream);
-int nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
-                       uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream);
-int sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point, float *out_normal,
-                   uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
-int overlap_impl_f32(const spira_scene *h, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
-                     uint32_t *out_trips, bool any, bool on_device, void *user_stream);
-int signed_distance_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
-                             uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream);
-int radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
-int camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream);
-int gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
-int gather_visible_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
-                            bool on_device, void *user_stream);
-int gather_rays_impl_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6, bool on_device, void *user_stream);
+namespace spira_tu {
+// Every entry that a Float32 call has to reach in the SPIRA_TU_F32 unit: one static member each, defined further down where its helpers are.  The members
+// must NOT be inline (none defined in the class, none marked inline): an explicit instantiation declaration does not suppress an inline member, and the
+// Float32 kernels it launches would be compiled into the SPIRA_TU_MAIN unit as well, with that unit's flags.  (An explicit instantiation takes the members
+// in the order declared here, and the kernels of the SPIRA_TU_F32 unit come out in that order: a new member goes at the end.)
+template <class T> struct Impl {
+    static int render(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                      T *out_hdr, T *out_img, bool out_on_device, void *user_stream,
+                      bool progressive = false, uint32_t sample0 = 0, uint32_t *rng_states = nullptr, const SlabCtl *slab = nullptr);
+    static int trace(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                     uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance);
+    static int render_adaptive(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                               const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream);
+    static int features(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                        T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream);
+    static int scene_update(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream);
+    static int scene_rebuild(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream);
+    static int cast(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
+                    bool any, bool on_device, void *user_stream);
+    static int nearest(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
+                       bool on_device, void *user_stream);
+    static int hits(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, T *out_t, uint32_t *out_count,
+                    bool on_device, void *user_stream);
+    static int nearest_k(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, T *out_dist, T *out_point,
+                         uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream);
+    static int sweep(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_sweeps, uint32_t flags, int *out_prim, T *out_t, T *out_point, T *out_normal,
+                     uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
+    static int overlap(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
+                       uint32_t *out_trips, bool any, bool on_device, void *user_stream);
+    static int signed_distance(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint8_t *out_inside,
+                               uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream);
+    static int radiance(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
+    static int camera_rays(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream);
+    static int gather(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream);
+    static int gather_visible(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                              bool on_device, void *user_stream);
+    static int gather_rays(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream);
+    static int denoise(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
+                       T *out_hdr, T *out_img, bool on_device, void *user_stream);
+};
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
 int launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a);
 }
-
-// SPIRA_ENTRY(NAME, IMPL) defines NAME<T>(args...): IMPL<T> of whichever translation unit holds the kernels of T.  In the SPIRA_TU_MAIN unit a Float32 call
-// goes to spira_tu::IMPL_f32 (declared above, defined in the SPIRA_TU_F32 unit) and IMPL<float> is never instantiated there; every other build calls IMPL<T>.
-// The arguments are taken as the caller wrote them and held against the signature of the function they go to HERE, so a call that does not fit (a literal 0
-// for a pointer, a missing argument: an entry has no defaults of its own) fails at the entry, under the entry's name.
+// The unit split of the Float32 entries, which the compiler enforces: this unit calls Impl<float> and instantiates none of it (the SPIRA_TU_F32 unit does,
+// at the end of the file, after every member's definition).  Before every use.
 #ifdef SPIRA_TU_MAIN
-constexpr bool kF32InItsOwnUnit = true;
-#else
-constexpr bool kF32InItsOwnUnit = false;
+extern template struct spira_tu::Impl<float>;
 #endif
-#define SPIRA_ENTRY(NAME, IMPL)                                                                                                                          \
-    template <class T, class... Args> int NAME(Args... args) {                                                                                           \
-        if constexpr (kF32InItsOwnUnit && sizeof(T) == 4) {                                                                                              \
-            static_assert(std::is_invocable_r_v<int, decltype(&spira_tu::IMPL##_f32), Args...>, #NAME ": the arguments do not fit " #IMPL "_f32");      \
-            return spira_tu::IMPL##_f32(args...);                                                                                                        \
-        } else {                                                                                                                                         \
-            static_assert(std::is_invocable_r_v<int, decltype(&IMPL<T>), Args...>, #NAME ": the arguments do not fit " #IMPL);                           \
-            return IMPL<T>(args...);                                                                                                                     \
-        }                                                                                                                                                \
-    }
 
 namespace spira_host {
 
@@ -189,28 +184,39 @@ struct LbvhWs {
 };
 struct LbvhTopo { uint32_t n_slots = 0; int depth = 0; std::vector<uint32_t> level_first; };
 
-struct Ctx {
+// Every device buffer of a context, and nothing else: release_all walks the struct as an array of DevBuf, so a buffer declared here is released at
+// shutdown without being named there.  (What is not a DevBuf belongs in Ctx.)
+struct CtxBuffers {
+    DevBuf qA[2], qB[2], qC[2], qR[2], qK[2], qX[2], mesh_list, mesh_count, redo, L, accum, counts, blkstats, stats, out_tmp, trace, rng;
+    DevBuf hyb_state, hyb_mat, hyb_flags;          // SPIRA_SEM_HYBRID: per-pixel ray state between its launches
+    DevBuf spd32, spd64;                          // SPIRA_EXT_SPECTRAL: the SPD table, uploaded once per precision
+    DevBuf multi_tile, multi_stack, multi_full;   // spira_render_multi_*: this device's tile; device 0: the gathered tiles, the frame
+    DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
+    DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
+    DevBuf list_io;                               // the list calls (cast, closest point, radiance, the gathers): a host form's staged list and outputs.  ONE buffer for all
+                                                  // of them: a host-form call synchronises before it returns, so a later call of another kind may reuse or regrow it
+                                                  // (ensure only grows); the device forms never touch it
+    DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel
+    DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
+    void release_all();
+};
+static_assert(std::is_standard_layout_v<CtxBuffers> && sizeof(CtxBuffers) % sizeof(DevBuf) == 0, "CtxBuffers holds DevBuf members only");
+inline void CtxBuffers::release_all() {
+    DevBuf *b = reinterpret_cast<DevBuf *>(this);
+    for (size_t i = 0; i < sizeof(CtxBuffers) / sizeof(DevBuf); ++i) b[i].release();
+}
+
+struct Ctx : CtxBuffers {
     bool init = false;
     int device = -1;
     int num_cus = 256;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;        // host-output frames rendered as row slabs: a slab's copies run here, beside the next slab's kernels
     hipEvent_t ev_slab = nullptr;
-    DevBuf qA[2], qB[2], qC[2], qR[2], qK[2], qX[2], mesh_list, mesh_count, redo, L, accum, counts, blkstats, stats, out_tmp, trace, rng;
-    DevBuf hyb_state, hyb_mat, hyb_flags;          // SPIRA_SEM_HYBRID: per-pixel ray state between its launches
-    DevBuf spd32, spd64;                          // SPIRA_EXT_SPECTRAL: the SPD table, uploaded once per precision
-    DevBuf multi_tile, multi_stack, multi_full;   // spira_render_multi_*: this device's tile; device 0: the gathered tiles, the frame
-    DevBuf ad_q, ad_n, ad_list[2], ad_count;      // spira_render_adaptive_*: per-pixel Q and sample count, the two active lists, their two lengths
-    uint32_t *h_ad_count = nullptr;               // pinned: the list length the host reads once per round
-    DevBuf dn_rec[2], dn_guide, dn_io;            // spira_denoise_*: the ping-pong colour records, the guide records, the host form's staged planes
-    DevBuf list_io;                               // the list calls (cast, closest point, radiance, the gathers): a host form's staged list and outputs.  ONE buffer for all
-                                                  // of them: a host-form call synchronises before it returns, so a later call of another kind may reuse or regrow it
-                                                  // (ensure only grows); the device forms never touch it
-    DevBuf refit_status;                          // spira_scene_update_device_*: the status word of the check kernel ...
-    uint32_t *h_refit_status = nullptr;           // ... and where the host reads it (pinned)
-    DevBuf lbvh_ws, lbvh_nodes, lbvh_small;      // spira_scene_rebuild_*: keys / binary tree / level lists, the new node slots, status + bounds + counts
-    struct LbvhSmall *h_lbvh = nullptr;           // ... and where the host reads the last (pinned)
-    std::vector<void *> lbvh_retired;             // node scratch outgrown in the middle of a rebuild: freed by the next one (a free waits for the device)
+    uint32_t *h_ad_count = nullptr;           // pinned: the length of an adaptive render's active list (ad_count), read by the host once per round
+    uint32_t *h_refit_status = nullptr;       // pinned: where the host reads refit_status
+    struct LbvhSmall *h_lbvh = nullptr;       // pinned: where the host reads lbvh_small
+    std::vector<void *> lbvh_retired;         // node scratch outgrown in the middle of a rebuild: freed by the next one (a free waits for the device)
     SceneStore scene;                         // the scene of the current call (host-array entry points)
     spira::Stats *h_stats = nullptr;          // pinned
     void *h_stage = nullptr; size_t h_stage_cap = 0;   // pinned staging of a host-output frame (copy_out below)
@@ -1169,13 +1175,14 @@ int end_counters(Session &s, const spira_counters &delta, bool cont) {
     return 0;
 }
 
+}  // namespace
 // Validation -> session -> plan -> workspaces -> scene -> prologue (events, a progressive call's running sums) -> the organisation's launches -> epilogue.
 // (The kernels of a translation unit come out in the order in which their launches are first named from here, enqueue function by enqueue function:
 // keep that order, and every launch but k_load_accum's inside one of them, and the code object does not change when this function does.)
 template <class T>
-int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                T *out_hdr, T *out_img, bool out_on_device, void *user_stream,
-                bool progressive = false, uint32_t sample0 = 0, uint32_t *rng_states = nullptr, const SlabCtl *slab = nullptr) {
+int spira_tu::Impl<T>::render(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                              T *out_hdr, T *out_img, bool out_on_device, void *user_stream,
+                              bool progressive, uint32_t sample0, uint32_t *rng_states, const SlabCtl *slab) {
     // progressive: out_hdr is the caller's running SUM (in/out), samples [sample0, sample0 + spp) are added to it
     using spira::Org;
     using P4 = spira::Pack4<T>;
@@ -1258,8 +1265,7 @@ int render_impl(const spira_scene *h, const T *spheres5, const T *materials8, co
     lap("copy_out+sync");
     return rc;
 }
-
-SPIRA_ENTRY(render_entry_plain, render_impl)
+namespace {
 
 #ifdef SPIRA_TU_MAIN
 // A large frame for a host-pointer caller, rendered as row slabs: slab k's planes go device -> pinned staging on a second stream while slab k + 1
@@ -1307,7 +1313,7 @@ int render_host_slabs(const spira_scene *h, const T *spheres5, const T *material
         T *d_hdr = out_hdr ? (T *)c.out_tmp.p + (size_t)3 * W * r0 : nullptr;
         T *d_img = out_img ? (T *)((char *)c.out_tmp.p + plane3) + (size_t)3 * W * r0 : nullptr;
         const SlabCtl ctl{s, S};
-        rc_all = render_entry_plain<T>(h, spheres5, materials8, triangles10, camera12, &ps, d_hdr, d_img, true, (void *)c.stream, false, 0, nullptr, &ctl);
+        rc_all = spira_tu::Impl<T>::render(h, spheres5, materials8, triangles10, camera12, &ps, d_hdr, d_img, true, (void *)c.stream, false, 0, nullptr, &ctl);
         if (rc_all) break;
         hipError_t e = hipEventRecord(c.ev_slab, c.stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c.copy_stream, c.ev_slab, 0);
@@ -1343,7 +1349,7 @@ int render_entry(const spira_scene *h, const T *spheres5, const T *materials8, c
         if (done || rc) return rc;
     }
 #endif
-    return render_entry_plain<T>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, nullptr);
+    return spira_tu::Impl<T>::render(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, nullptr);
 }
 
 // ---- adaptive sampling (spira_render_adaptive_*; spira_adaptive.h).  Round 0 is a plain render of min_spp samples on the slot-major plan (PlanIn::adaptive)
@@ -1358,9 +1364,10 @@ int enqueue_refine(hipStream_t st, const spira::AdaptiveRound &g, size_t lds, co
     return launch_lds(spira::k_refine<T, BVH>, dim3(g.grid), dim3(spira::kBlock), lds, st, ra);
 }
 
+}  // namespace
 template <class T>
-int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                         const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream) {
+int spira_tu::Impl<T>::render_adaptive(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                                       const spira_adaptive *ad, T *out_hdr, T *out_img, uint32_t *out_spp, T *out_q, bool out_on_device, void *user_stream) {
     using spira::Org;
     using P4 = spira::Pack4<T>;
     uint32_t rows = 0;
@@ -1463,8 +1470,7 @@ int render_adaptive_impl(const spira_scene *h, const T *spheres5, const T *mater
     }
     return s.close();
 }
-
-SPIRA_ENTRY(render_adaptive_entry, render_adaptive_impl)
+namespace {
 
 // The rule as host arithmetic: 1 converged, 0 not, or a negative code
 template <class T>
@@ -1475,11 +1481,12 @@ int adaptive_converged_host(const T *sum3, T q, uint32_t n, double tolerance, do
     return spira::adaptive_converged<T>(sum3[0], sum3[1], sum3[2], q, n, (T)tolerance, (T)floor) ? 1 : 0;
 }
 
+}  // namespace
 // ---- first-hit feature buffers (spira_render_features_*; spira_denoise.h, k_features): one launch over the tile, one lane per pixel walking its samples.
 // Asynchronous in the device-output form like every device entry; the counters of the last render are left as they are.
 template <class T>
-int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-                  T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
+int spira_tu::Impl<T>::features(const spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                                T *out_albedo, T *out_normal, T *out_depth, bool out_on_device, void *user_stream) {
     uint32_t rows = 0;
     const T *some_out = out_albedo ? out_albedo : out_normal ? out_normal : out_depth;
     if (int rc = validate_call<T>(h, spheres5, materials8, triangles10, camera12, p, some_out, (const T *)nullptr, false, 0, nullptr, &rows)) return rc;
@@ -1517,8 +1524,7 @@ int features_impl(const spira_scene *h, const T *spheres5, const T *materials8, 
     }
     return s.close();
 }
-
-SPIRA_ENTRY(features_entry, features_impl)
+namespace {
 
 // ======================================================================= the list calls on a scene handle: what the queries, radiance and the gathers share
 // Each answers a caller's list (rays, points, sweeps or boxes) entry by entry.  Written once for all of them: the opening, the staging of a host caller's
@@ -1627,11 +1633,12 @@ int launch_paths(void (*const (&k)[2][2])(A), dim3 grid, size_t lds, hipStream_t
     return launch_lds(k[a.scene.n_bvh_tris ? 1 : 0][ext ? 1 : 0], grid, dim3(spira::kBlock), lds, st, a);
 }
 
+}  // namespace
 // ======================================================================= spira_scene_cast_* / spira_scene_occluded_*: the caller's rays against a handle
 // Kernels and the ray preparation: spira_query.h; the call: list_query_call.
 template <class T>
-int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
-              bool any, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::cast(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, T *out_t, T *out_normal, uint8_t *out_hit,
+                            bool any, bool on_device, void *user_stream) {
     using A = spira::CastArgs<T>;
     const ListKernels<A> closest = {spira::k_cast_session<T, false>, spira::k_cast<T, true, false, false>, spira::k_cast<T, false, true, false>, spira::k_cast<T, false, false, false>, true};
     const ListKernels<A> occluded = {spira::k_cast_session<T, true>, spira::k_cast<T, true, false, true>, spira::k_cast<T, false, true, true>, spira::k_cast<T, false, false, true>, true};
@@ -1644,13 +1651,12 @@ int cast_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t fl
                        {a.hit, out_hit, n, kStageOut}};
     return list_query_call<T>(h, n_rays, flags, on_device, user_stream, a, io, any ? occluded : closest);
 }
-SPIRA_ENTRY(cast_entry, cast_impl)
 
 // ======================================================================= spira_scene_closest_point_*: the nearest surface point for the caller's points
 // Kernels, the point preparation and the two closest-point functions: spira_nearest.h; the call: list_query_call.
 template <class T>
-int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
-                 bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::nearest(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint32_t *out_trips,
+                               bool on_device, void *user_stream) {
     using A = spira::NearestArgs<T>;
     const ListKernels<A> kernels = {spira::k_nearest_session<T>, spira::k_nearest<T, true, false>, spira::k_nearest<T, false, true>, spira::k_nearest<T, false, false>, false};
     const char *msg = nullptr;
@@ -1662,7 +1668,7 @@ int nearest_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint
                        {a.prim, out_prim, n * sizeof(int), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}};
     return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
-SPIRA_ENTRY(nearest_entry, nearest_impl)
+namespace {
 
 // ======================================================================= spira_scene_cast_hits_*: the first max_hits hits of every ray, in order
 // Kernels, the list and the pruning argument: spira_hits.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the smallest
@@ -1671,9 +1677,10 @@ template <class T, int CAP>
 ListKernels<spira::HitsArgs<T>> hits_kernels() {
     return {spira::k_hits_session<T, CAP>, spira::k_hits<T, true, false, CAP>, spira::k_hits<T, false, true, CAP>, spira::k_hits<T, false, false, CAP>, true};
 }
+}  // namespace
 template <class T>
-int hits_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, T *out_t, uint32_t *out_count,
-              bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::hits(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, T *out_t, uint32_t *out_count,
+                            bool on_device, void *user_stream) {
     using A = spira::HitsArgs<T>;
     const char *msg = nullptr;
     if (max_hits == 0) { out_prim = nullptr; out_t = nullptr; }      // (count only: the lists have no slots)
@@ -1686,7 +1693,7 @@ int hits_impl(const spira_scene *h, const T *rays8, uint32_t n_rays, uint32_t ma
                        {a.count, out_count, n * sizeof(uint32_t), kStageOut}};
     return list_query_call<T>(h, n_rays, flags, on_device, user_stream, a, io, kernels);
 }
-SPIRA_ENTRY(hits_entry, hits_impl)
+namespace {
 
 // ======================================================================= spira_scene_nearest_k_*: the max_near closest objects of every point, in order
 // Kernels, the list and the pruning argument: spira_knearest.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the
@@ -1695,9 +1702,10 @@ template <class T, int CAP>
 ListKernels<spira::KNearArgs<T>> knear_kernels() {
     return {spira::k_knear_session<T, CAP>, spira::k_knear<T, true, false, CAP>, spira::k_knear<T, false, true, CAP>, spira::k_knear<T, false, false, CAP>, false};
 }
+}  // namespace
 template <class T>
-int nearest_k_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, T *out_dist, T *out_point,
-                   uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::nearest_k(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, T *out_dist, T *out_point,
+                                 uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
     using A = spira::KNearArgs<T>;
     const char *msg = nullptr;
     if (max_near == 0) { out_prim = nullptr; out_dist = nullptr; out_point = nullptr; }      // (count only: the lists have no slots)
@@ -1710,13 +1718,12 @@ int nearest_k_impl(const spira_scene *h, const T *points4, uint32_t n_points, ui
                        {a.prim, out_prim, slots * sizeof(int), kStageOut}, {a.count, out_count, n * sizeof(uint32_t), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}};
     return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
-SPIRA_ENTRY(nearest_k_entry, nearest_k_impl)
 
 // ======================================================================= spira_scene_sweep_* / spira_scene_sweep_blocked_*: the first contact of a moving ball
 // Kernels, the contract and the margin argument: spira_sweep.h; the call: list_query_call.
 template <class T>
-int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_sweeps, uint32_t flags, int *out_prim, T *out_t, T *out_point, T *out_normal,
-               uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::sweep(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_sweeps, uint32_t flags, int *out_prim, T *out_t, T *out_point, T *out_normal,
+                             uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
     using A = spira::SweepArgs<T>;
     const ListKernels<A> first = {spira::k_sweep_session<T, false>, spira::k_sweep<T, true, false, false>, spira::k_sweep<T, false, true, false>, spira::k_sweep<T, false, false, false>, false};
     const ListKernels<A> blocked = {spira::k_sweep_session<T, true>, spira::k_sweep<T, true, false, true>, spira::k_sweep<T, false, true, true>, spira::k_sweep<T, false, false, true>, false};
@@ -1730,7 +1737,7 @@ int sweep_impl(const spira_scene *h, const T *rays8, const T *radii, uint32_t n_
                        {a.hit, out_hit, n, kStageOut}};
     return list_query_call<T>(h, n_sweeps, flags, on_device, user_stream, a, io, any ? blocked : first);
 }
-SPIRA_ENTRY(sweep_entry, sweep_impl)
+namespace {
 
 // ======================================================================= spira_scene_overlap_box_* / spira_scene_overlap_any_*: what touches an oriented box
 // Kernels, the contract and the margin argument: spira_overlap.h; the call: list_query_call, with the kernels whose list capacity (1, 4 or 16) is the
@@ -1739,9 +1746,10 @@ template <class T, bool ANY, int CAP>
 ListKernels<spira::OverlapArgs<T>> overlap_kernels() {
     return {spira::k_overlap_session<T, ANY, CAP>, spira::k_overlap<T, true, false, ANY, CAP>, spira::k_overlap<T, false, true, ANY, CAP>, spira::k_overlap<T, false, false, ANY, CAP>, false};
 }
+}  // namespace
 template <class T>
-int overlap_impl(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
-                 uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::overlap(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
+                               uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
     using A = spira::OverlapArgs<T>;
     const char *msg = nullptr;
     if (any) max_list = 0;
@@ -1756,7 +1764,7 @@ int overlap_impl(const spira_scene *h, const T *boxes10, uint32_t n_boxes, uint3
                        {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}, {a.hit, out_hit, n, kStageOut}};
     return list_query_call<T>(h, n_boxes, flags, on_device, user_stream, a, io, kernels);
 }
-SPIRA_ENTRY(overlap_entry, overlap_impl)
+namespace {
 
 // ======================================================================= spira_scene_signed_distance_*: the nearest surface of every point and which side of it
 // Kernels and the contract: spira_sdf.h; the call: list_query_call, with the kernels with or without the nearest walk (out_prim, out_dist and out_point
@@ -1766,9 +1774,10 @@ template <class T, bool NEAR>
 ListKernels<spira::SdfArgs<T>> sdf_kernels() {
     return {spira::k_sdf_session<T, NEAR>, spira::k_sdf<T, true, false, NEAR>, spira::k_sdf<T, false, true, NEAR>, spira::k_sdf<T, false, false, NEAR>, false};
 }
+}  // namespace
 template <class T>
-int signed_distance_impl(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint8_t *out_inside,
-                         uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::signed_distance(const spira_scene *h, const T *points4, uint32_t n_points, uint32_t flags, int *out_prim, T *out_dist, T *out_point, uint8_t *out_inside,
+                                       uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream) {
     using A = spira::SdfArgs<T>;
     const char *msg = nullptr;
     if (int rc = spira::signed_distance_check(points4 != nullptr, n_points, flags, out_prim || out_dist || out_point || out_inside || out_crossings, &msg)) return fail(rc, msg);
@@ -1780,7 +1789,7 @@ int signed_distance_impl(const spira_scene *h, const T *points4, uint32_t n_poin
                        {a.crossings, out_crossings, 3 * n * sizeof(uint32_t), kStageOut}, {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}, {a.inside, out_inside, n, kStageOut}};
     return list_query_call<T>(h, n_points, flags, on_device, user_stream, a, io, kernels);
 }
-SPIRA_ENTRY(signed_distance_entry, signed_distance_impl)
+namespace {
 
 // ======================================================================= spira_scene_radiance_*: path-traced radiance along the caller's rays; spira_camera_rays_*
 // Kernels, the ray preparation and the generator: spira_radiance.h; launch arithmetic: spira_plan.h (make_radiance_plan).  One k_radiance launch per pass
@@ -1792,7 +1801,7 @@ spira::RadianceKnobs read_radiance_knobs() {
     k.max_items = env_u32("SPIRA_RADIANCE_MAX_ITEMS", SPIRA_RADIANCE_MAX_ITEMS);
     return k;
 }
-// What radiance_impl and gather_impl do with their Args (RadianceArgs, GatherArgs) once the list's own two fields are set: the path constants, the
+// What Impl<T>::radiance and Impl<T>::gather do with their Args (RadianceArgs, GatherArgs) once the list's own two fields are set: the path constants, the
 // workspace, the staged list / sums / valid bytes, the passes.  list: the block of the caller's n rays or points (six values each).
 template <class T, class A>
 int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radiance *rp, A &a, const StageBlock &list, uint32_t n, T *sum_rgb, uint8_t *out_valid,
@@ -1816,8 +1825,9 @@ int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radian
     if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
+}  // namespace
 template <class T>
-int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::radiance(const spira_scene *h, const T *rays6, uint32_t n_rays, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     using A = spira::RadianceArgs<T>;
     void (*const paths[2][2])(A) = {{spira::k_radiance<T, false, false>, spira::k_radiance<T, false, true>}, {spira::k_radiance<T, true, false>, spira::k_radiance<T, true, true>}};
     const char *msg = nullptr;
@@ -1830,11 +1840,10 @@ int radiance_impl(const spira_scene *h, const T *rays6, uint32_t n_rays, const s
     const spira::RadiancePlan pl = spira::make_radiance_plan(n_rays, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_radiance_knobs());
     return path_list_call<T>(s, pl, rp, a, {a.rays, rays6, 6 * (size_t)n_rays * sizeof(T), kStageIn}, n_rays, sum_rgb, out_valid, paths, spira::k_radiance_sum<T>);
 }
-SPIRA_ENTRY(radiance_entry, radiance_impl)
 
 // The generator: the host form runs camera_ray_generate<T> here, the device form launches k_camera_rays<T> over the same function.
 template <class T>
-int camera_rays_impl(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::camera_rays(const T *camera12, const spira_lens *lens, T *rays6, bool on_device, void *user_stream) {
     if (!camera12) return fail(SPIRA_E_INVALID, "camera12 is NULL");
     if (!lens) return fail(SPIRA_E_INVALID, "the spira_lens struct is NULL");
     if (!rays6) return fail(SPIRA_E_INVALID, "the ray array is NULL");
@@ -1862,10 +1871,10 @@ int camera_rays_impl(const T *camera12, const spira_lens *lens, T *rays6, bool o
     hipLaunchKernelGGL(spira::k_camera_rays<T>, dim3((n + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
     return s.close();
 }
-SPIRA_ENTRY(camera_rays_entry, camera_rays_impl)
+namespace {
 
 // ======================================================================= spira_scene_gather_* / spira_scene_gather_visible_* / spira_gather_rays_*: hemisphere gather at surface points
-// Kernels and the sampling rule: spira_gather.h; launch arithmetic: spira_plan.h (make_gather_plan).  The radiance gather is radiance_impl's call over
+// Kernels and the sampling rule: spira_gather.h; launch arithmetic: spira_plan.h (make_gather_plan).  The radiance gather is Impl<T>::radiance's call over
 // points (path_list_call): one k_gather launch per pass (+ k_gather_sum where a pass holds more than one sample per point), the workspace of such a pass the
 // context's L.  The visibility gather runs the same passes with one launch each and no workspace: its device form allocates nothing.  The host forms stage
 // points, sums or counts and valid bytes.
@@ -1875,8 +1884,9 @@ spira::GatherKnobs read_gather_knobs() {
     k.max_items = env_u32("SPIRA_GATHER_MAX_ITEMS", SPIRA_GATHER_MAX_ITEMS);
     return k;
 }
+}  // namespace
 template <class T>
-int gather_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::gather(const spira_scene *h, const T *points6, uint32_t n_points, const spira_radiance *rp, T *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
     using A = spira::GatherArgs<T>;
     void (*const paths[2][2])(A) = {{spira::k_gather<T, false, false>, spira::k_gather<T, false, true>}, {spira::k_gather<T, true, false>, spira::k_gather<T, true, true>}};
     const char *msg = nullptr;
@@ -1889,11 +1899,10 @@ int gather_impl(const spira_scene *h, const T *points6, uint32_t n_points, const
     const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_gather_knobs());
     return path_list_call<T>(s, pl, rp, a, {a.points, points6, 6 * (size_t)n_points * sizeof(T), kStageIn}, n_points, sum_rgb, out_valid, paths, spira::k_gather_sum<T>);
 }
-SPIRA_ENTRY(gather_entry, gather_impl)
 
 template <class T>
-int gather_visible_impl(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
-                        bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::gather_visible(const spira_scene *h, const T *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
+                                      bool on_device, void *user_stream) {
     using A = spira::GatherVisibleArgs<T>;
     const ListKernels<A> kernels = {spira::k_gather_visible_session<T>, spira::k_gather_visible<T, true, false>, spira::k_gather_visible<T, false, true>,
                                            spira::k_gather_visible<T, false, false>, true};
@@ -1922,11 +1931,10 @@ int gather_visible_impl(const spira_scene *h, const T *points6, uint32_t n_point
     if (int rc = stage_out(s, io)) return rc;
     return s.close();
 }
-SPIRA_ENTRY(gather_visible_entry, gather_visible_impl)
 
 // The generator: the host form runs gather_ray_generate<T> here, the device form launches k_gather_rays<T> over the same function.
 template <class T>
-int gather_rays_impl(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::gather_rays(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
     const char *msg = nullptr;
     if (int rc = spira::gather_rays_check(points6 != nullptr, rays6 != nullptr, n_points, sample, key0, &msg)) return fail(rc, msg);
     uint32_t sA, sB;
@@ -1942,7 +1950,7 @@ int gather_rays_impl(const T *points6, uint32_t n_points, uint32_t sample, uint6
     hipLaunchKernelGGL(spira::k_gather_rays<T>, dim3((n_points + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
     return s.close();
 }
-SPIRA_ENTRY(gather_rays_entry, gather_rays_impl)
+namespace {
 
 // ======================================================================= spira_scene_update_*: new contents for a live handle, the tree refitted on the device
 // The arithmetic is spira_refit.h's (one header, host and device); here are its three kernels and the entry that orders them.  Nothing of k_path, the
@@ -2007,11 +2015,12 @@ __global__ __launch_bounds__(kRefitLevelBlock) void k_refit_level(uint4 *nodes, 
     }
 }
 
+}  // namespace
 // Host form (device_form false): any of the three host arrays, NULL = unchanged; validated in full before the device is touched; returns when the scene
 // is ready.  Device form: d_triangles10 in the caller's layout, checked by k_refit_check (ONE synchronisation of the stream, to read the status word), then
 // the refit is enqueued and the call returns.  Either way a refused update leaves the handle as it was.
 template <class T>
-int scene_update_impl(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+int spira_tu::Impl<T>::scene_update(spira_scene *h, const T *spheres5, const T *materials8, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
     if (int rc = check_handle<T>(h)) return rc;
     if (h->multi) return fail(SPIRA_E_UNSUPPORTED, "spira_scene_update_* does not take a handle made by spira_scene_create_multi_*");
     SceneStore &s = h->store;
@@ -2097,8 +2106,7 @@ int scene_update_impl(spira_scene *h, const T *spheres5, const T *materials8, co
     s.moderate_s = mod_s; s.moderate_t = mod_t; s.moderate = mod_s && mod_t;
     return sess.close();
 }
-
-SPIRA_ENTRY(scene_update_entry, scene_update_impl)
+namespace {
 
 // ======================================================================= spira_scene_rebuild_*: a new triangle array for a live handle, the tree built anew on the device
 // The arithmetic is spira_lbvh.h's (frame, Morton keys, radix tree, collapse) and spira_refit.h's (records and boxes).  A rebuild produces a frame and a
@@ -2319,12 +2327,13 @@ __global__ __launch_bounds__(kRefitLevelBlock) void k_lbvh_write(const spira::Lb
 }
 #endif
 
+}  // namespace
 // Host form: triangles10 validated in full on the host before the device is touched, staged, then the same pipeline; returns when the scene is ready.
 // Device form: d_triangles10 on the caller's stream.  The stream is synchronised once for the check kernel's status and bounds and once per level of the new
 // tree (the level's counts); after the last of these the remaining work is enqueued and the call returns.  Whatever refuses, refuses before the handle's
 // node array, records, frame packets or level fields are touched.
 template <class T>
-int scene_rebuild_impl(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
+int spira_tu::Impl<T>::scene_rebuild(spira_scene *h, const T *triangles10, const T *d_triangles10, bool device_form, void *user_stream) {
     if (int rc = check_handle<T>(h)) return rc;
     if (h->multi) return fail(SPIRA_E_UNSUPPORTED, "spira_scene_rebuild_* does not take a handle made by spira_scene_create_multi_*");
     SceneStore &s = h->store;
@@ -2425,13 +2434,11 @@ int scene_rebuild_impl(spira_scene *h, const T *triangles10, const T *d_triangle
     return sess.close();
 }
 
-SPIRA_ENTRY(scene_rebuild_entry, scene_rebuild_impl)
-
 // ---- the a-trous denoiser (spira_denoise_*; spira_denoise.h): prepare, then one launch per iteration between the context's two record buffers, the last
 // one writing the outputs.  The device form enqueues and returns; it allocates only when a workspace has to grow (a first call at a size).
 template <class T>
-int denoise_impl(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
-                 T *out_hdr, T *out_img, bool on_device, void *user_stream) {
+int spira_tu::Impl<T>::denoise(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
+                               T *out_hdr, T *out_img, bool on_device, void *user_stream) {
     using P4 = spira::Pack4<T>;
     if (!dn) return fail(SPIRA_E_INVALID, "dn is NULL");
     if (!color) return fail(SPIRA_E_INVALID, "color is NULL");
@@ -2490,11 +2497,9 @@ int denoise_impl(const T *color, const T *variance, const T *albedo, const T *no
     return s.close();
 }
 
-SPIRA_ENTRY(denoise_entry, denoise_impl)
-
 template <class T>
-int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
-               uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance) {
+int spira_tu::Impl<T>::trace(const T *spheres5, const T *materials8, const T *triangles10, const T *camera12, const spira_params *p,
+                             uint32_t n_paths, const uint32_t *ijs, int *prims, T *ts, T *dirs, T *radiance) {
     uint32_t rows = 0;
     if (!p) return fail(SPIRA_E_INVALID, "params is NULL");
     if (int rc = validate_scene<T>(spheres5, materials8, triangles10, p->n_spheres, p->n_materials, triangles10 ? p->n_triangles : 0)) return rc;
@@ -2544,6 +2549,7 @@ int trace_impl(const T *spheres5, const T *materials8, const T *triangles10, con
     HIP_TRY(hipMemcpyAsync(radiance, d_ra, (size_t)n_paths * 3 * sizeof(T), hipMemcpyDeviceToHost, st));
     return s.close();
 }
+namespace {
 
 // Camera constructor arithmetic, host side.  Statement order of
 // examples/julia-raytracer.jl:280-291 == src/spira-metal-optimized.jl:332-345 (focus_dist = 1).
@@ -2784,7 +2790,7 @@ int render_multi_impl(const spira_scene *mh, const T *spheres5, const T *materia
             tp.row0 = 0; tp.stripe_h = kMultiStripeH; tp.stripe_count = n; tp.stripe_rank = r;
             if (n == 1) { tp.rows = 0; tp.stripe_h = 0; tp.stripe_count = 0; tp.stripe_rank = 0; }
             T *d_hdr = (T *)c.multi_tile.p, *d_img = d_hdr + (size_t)3 * max_rows * W;
-            // render_impl writes each output as [3][rows][W] contiguously; the gather wants every tile at the pitch of the largest one
+            // Impl<T>::render writes each output as [3][rows][W] contiguously; the gather wants every tile at the pitch of the largest one
             // ([6][max_rows][W]).  A tile with fewer rows (ragged last stripes) is rendered into the second half of the buffer and its
             // six planes are re-pitched with one strided device copy.
             const spira_scene *hr = !mh ? nullptr : ((rehearse || r == 0) ? mh : mh->replica[r]);
@@ -2939,76 +2945,7 @@ int spira_tu::launch_path_resume_f64(int R, dim3 grid, size_t lds, hipStream_t s
     return launch_path_resume<double>(R, grid, lds, st, a);
 }
 #elif defined(SPIRA_TU_F32)
-int spira_tu::render_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                              float *out_hdr, float *out_img, bool out_on_device, void *user_stream, bool progressive, uint32_t sample0, uint32_t *rng_states, const SlabCtl *slab) {
-    return render_impl<float>(h, spheres5, materials8, triangles10, camera12, p, out_hdr, out_img, out_on_device, user_stream, progressive, sample0, rng_states, slab);
-}
-int spira_tu::trace_impl_f32(const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                             uint32_t n_paths, const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance) {
-    return trace_impl<float>(spheres5, materials8, triangles10, camera12, p, n_paths, ijs, prims, ts, dirs, radiance);
-}
-int spira_tu::render_adaptive_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                                       const spira_adaptive *ad, float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q, bool out_on_device, void *user_stream) {
-    return render_adaptive_impl<float>(h, spheres5, materials8, triangles10, camera12, p, ad, out_hdr, out_img, out_spp, out_q, out_on_device, user_stream);
-}
-int spira_tu::features_impl_f32(const spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *camera12, const spira_params *p,
-                                float *out_albedo, float *out_normal, float *out_depth, bool out_on_device, void *user_stream) {
-    return features_impl<float>(h, spheres5, materials8, triangles10, camera12, p, out_albedo, out_normal, out_depth, out_on_device, user_stream);
-}
-int spira_tu::scene_update_impl_f32(spira_scene *h, const float *spheres5, const float *materials8, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
-    return scene_update_impl<float>(h, spheres5, materials8, triangles10, d_triangles10, device_form, user_stream);
-}
-int spira_tu::scene_rebuild_impl_f32(spira_scene *h, const float *triangles10, const float *d_triangles10, bool device_form, void *user_stream) {
-    return scene_rebuild_impl<float>(h, triangles10, d_triangles10, device_form, user_stream);
-}
-int spira_tu::cast_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal, uint8_t *out_hit,
-                            bool any, bool on_device, void *user_stream) {
-    return cast_impl<float>(h, rays8, n_rays, flags, out_prim, out_t, out_normal, out_hit, any, on_device, user_stream);
-}
-int spira_tu::nearest_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
-                               uint32_t *out_trips, bool on_device, void *user_stream) {
-    return nearest_impl<float>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, on_device, user_stream);
-}
-int spira_tu::hits_impl_f32(const spira_scene *h, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count,
-                            bool on_device, void *user_stream) {
-    return hits_impl<float>(h, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, on_device, user_stream);
-}
-int spira_tu::nearest_k_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist,
-                                 float *out_point, uint32_t *out_count, uint32_t *out_trips, bool on_device, void *user_stream) {
-    return nearest_k_impl<float>(h, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, on_device, user_stream);
-}
-int spira_tu::sweep_impl_f32(const spira_scene *h, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point,
-                             float *out_normal, uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
-    return sweep_impl<float>(h, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, out_hit, out_trips, any, on_device, user_stream);
-}
-int spira_tu::overlap_impl_f32(const spira_scene *h, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count, uint8_t *out_hit,
-                               uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
-    return overlap_impl<float>(h, boxes10, n, max_list, flags, out_prim, out_count, out_hit, out_trips, any, on_device, user_stream);
-}
-int spira_tu::signed_distance_impl_f32(const spira_scene *h, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
-                                       uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips, bool on_device, void *user_stream) {
-    return signed_distance_impl<float>(h, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, on_device, user_stream);
-}
-int spira_tu::radiance_impl_f32(const spira_scene *h, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
-    return radiance_impl<float>(h, rays6, n_rays, rp, sum_rgb, out_valid, on_device, user_stream);
-}
-int spira_tu::camera_rays_impl_f32(const float *camera12, const spira_lens *lens, float *rays6, bool on_device, void *user_stream) {
-    return camera_rays_impl<float>(camera12, lens, rays6, on_device, user_stream);
-}
-int spira_tu::gather_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid, bool on_device, void *user_stream) {
-    return gather_impl<float>(h, points6, n_points, rp, sum_rgb, out_valid, on_device, user_stream);
-}
-int spira_tu::gather_visible_impl_f32(const spira_scene *h, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible, uint8_t *out_valid,
-                                      bool on_device, void *user_stream) {
-    return gather_visible_impl<float>(h, points6, n_points, gv, visible, out_valid, on_device, user_stream);
-}
-int spira_tu::gather_rays_impl_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6, bool on_device, void *user_stream) {
-    return gather_rays_impl<float>(points6, n_points, sample, seed, key0, rays6, on_device, user_stream);
-}
-int spira_tu::denoise_impl_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
-                               float *out_hdr, float *out_img, bool on_device, void *user_stream) {
-    return denoise_impl<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, on_device, user_stream);
-}
+template struct spira_tu::Impl<float>;      // every member, and with them every Float32 kernel, is compiled in this unit
 #else
 // ======================================================================= C ABI (SPIRA_TU_MAIN, or the single translation unit)
 extern "C" {
@@ -3046,43 +2983,43 @@ extern "C" int spira_debug_mesh_stats(unsigned long long *out32, int reset) {
 
 // ---- ray queries on a scene handle (spira_query.h)
 int spira_scene_cast_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, float *out_t, float *out_normal) {
-    return cast_entry<float>(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
+    return spira_tu::Impl<float>::cast(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
 }
 int spira_scene_cast_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags, int *out_prim, double *out_t, double *out_normal) {
-    return cast_entry<double>(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
+    return spira_tu::Impl<double>::cast(scene, rays8, n_rays, flags, out_prim, out_t, out_normal, nullptr, false, false, nullptr);
 }
 int spira_scene_cast_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags, int *d_out_prim, float *d_out_t, float *d_out_normal, void *stream) {
-    return cast_entry<float>(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
+    return spira_tu::Impl<float>::cast(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
 }
 int spira_scene_cast_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags, int *d_out_prim, double *d_out_t, double *d_out_normal, void *stream) {
-    return cast_entry<double>(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
+    return spira_tu::Impl<double>::cast(scene, d_rays8, n_rays, flags, d_out_prim, d_out_t, d_out_normal, nullptr, false, true, stream);
 }
 int spira_scene_occluded_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit) {
-    return cast_entry<float>(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
+    return spira_tu::Impl<float>::cast(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
 }
 int spira_scene_occluded_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t flags, uint8_t *out_hit) {
-    return cast_entry<double>(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
+    return spira_tu::Impl<double>::cast(scene, rays8, n_rays, flags, nullptr, nullptr, nullptr, out_hit, true, false, nullptr);
 }
 int spira_scene_occluded_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return cast_entry<float>(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
+    return spira_tu::Impl<float>::cast(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
 }
 int spira_scene_occluded_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return cast_entry<double>(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
+    return spira_tu::Impl<double>::cast(scene, d_rays8, n_rays, flags, nullptr, nullptr, nullptr, d_out_hit, true, true, stream);
 }
 // ---- multi-hit ray queries (spira_hits.h)
 int spira_scene_cast_hits_f32(const spira_scene *scene, const float *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, float *out_t, uint32_t *out_count) {
-    return hits_entry<float>(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
+    return spira_tu::Impl<float>::hits(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
 }
 int spira_scene_cast_hits_f64(const spira_scene *scene, const double *rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *out_prim, double *out_t, uint32_t *out_count) {
-    return hits_entry<double>(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
+    return spira_tu::Impl<double>::hits(scene, rays8, n_rays, max_hits, flags, out_prim, out_t, out_count, false, nullptr);
 }
 int spira_scene_cast_hits_device_f32(const spira_scene *scene, const float *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *d_out_prim, float *d_out_t,
                                      uint32_t *d_out_count, void *stream) {
-    return hits_entry<float>(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
+    return spira_tu::Impl<float>::hits(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
 }
 int spira_scene_cast_hits_device_f64(const spira_scene *scene, const double *d_rays8, uint32_t n_rays, uint32_t max_hits, uint32_t flags, int *d_out_prim, double *d_out_t,
                                      uint32_t *d_out_count, void *stream) {
-    return hits_entry<double>(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
+    return spira_tu::Impl<double>::hits(scene, d_rays8, n_rays, max_hits, flags, d_out_prim, d_out_t, d_out_count, true, stream);
 }
 // Test support, outside the ABI like spira_debug_scene_tree: the launch plan a cast of n_rays would get on a device of num_cus CUs, with the knobs of the
 // environment as the entries read them.  out8: grid, wpb, waves, base, rem, refill_free, grid_flat, kCastMinRaysPerWave.  No device needed.
@@ -3097,36 +3034,36 @@ int spira_debug_cast_plan(uint32_t n_rays, uint32_t num_cus, uint32_t *out8) {
 // ---- closest-point queries on a scene handle (spira_nearest.h)
 int spira_scene_closest_point_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
                                   uint32_t *out_trips) {
-    return nearest_entry<float>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
+    return spira_tu::Impl<float>::nearest(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
 }
 int spira_scene_closest_point_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags, int *out_prim, double *out_dist, double *out_point,
                                   uint32_t *out_trips) {
-    return nearest_entry<double>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
+    return spira_tu::Impl<double>::nearest(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_trips, false, nullptr);
 }
 int spira_scene_closest_point_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, float *d_out_dist,
                                          float *d_out_point, uint32_t *d_out_trips, void *stream) {
-    return nearest_entry<float>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
+    return spira_tu::Impl<float>::nearest(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
 }
 int spira_scene_closest_point_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, double *d_out_dist,
                                          double *d_out_point, uint32_t *d_out_trips, void *stream) {
-    return nearest_entry<double>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
+    return spira_tu::Impl<double>::nearest(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_trips, true, stream);
 }
 // ---- K-nearest point queries (spira_knearest.h)
 int spira_scene_nearest_k_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, float *out_dist,
                               float *out_point, uint32_t *out_count, uint32_t *out_trips) {
-    return nearest_k_entry<float>(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
+    return spira_tu::Impl<float>::nearest_k(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
 }
 int spira_scene_nearest_k_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *out_prim, double *out_dist,
                               double *out_point, uint32_t *out_count, uint32_t *out_trips) {
-    return nearest_k_entry<double>(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
+    return spira_tu::Impl<double>::nearest_k(scene, points4, n_points, max_near, flags, out_prim, out_dist, out_point, out_count, out_trips, false, nullptr);
 }
 int spira_scene_nearest_k_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *d_out_prim,
                                      float *d_out_dist, float *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
-    return nearest_k_entry<float>(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
+    return spira_tu::Impl<float>::nearest_k(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
 }
 int spira_scene_nearest_k_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t max_near, uint32_t flags, int *d_out_prim,
                                      double *d_out_dist, double *d_out_point, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
-    return nearest_k_entry<double>(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
+    return spira_tu::Impl<double>::nearest_k(scene, d_points4, n_points, max_near, flags, d_out_prim, d_out_dist, d_out_point, d_out_count, d_out_trips, true, stream);
 }
 // host arithmetic, no device: the triangle function the kernels and the scan call
 void spira_closest_point_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float p[3], float out_q[3], float *out_d2) {
@@ -3145,17 +3082,17 @@ void spira_closest_point_triangle_f64(const double v0[3], const double e1[3], co
 // ---- sphere sweeps on a scene handle (spira_sweep.h)
 int spira_scene_sweep_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags, int *out_prim, float *out_t, float *out_point,
                           float *out_normal, uint32_t *out_trips) {
-    return sweep_entry<float>(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
+    return spira_tu::Impl<float>::sweep(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
 }
 int spira_scene_sweep_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags, int *d_out_prim, float *d_out_t,
                                  float *d_out_point, float *d_out_normal, uint32_t *d_out_trips, void *stream) {
-    return sweep_entry<float>(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
+    return spira_tu::Impl<float>::sweep(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
 }
 int spira_scene_sweep_blocked_f32(const spira_scene *scene, const float *rays8, const float *radii, uint32_t n, uint32_t flags, uint8_t *out_hit) {
-    return sweep_entry<float>(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+    return spira_tu::Impl<float>::sweep(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
 }
 int spira_scene_sweep_blocked_device_f32(const spira_scene *scene, const float *d_rays8, const float *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return sweep_entry<float>(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+    return spira_tu::Impl<float>::sweep(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
 }
 // host arithmetic, no device: the leaf function the kernels and the scan call, with bound = t_max.  A miss: t = t_max copied, q 0.
 void spira_sweep_sphere_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float o[3], const float d_unit[3], float r, float t_min, float t_max,
@@ -3168,17 +3105,17 @@ void spira_sweep_sphere_triangle_f32(const float v0[3], const float e1[3], const
 }
 int spira_scene_sweep_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags, int *out_prim, double *out_t, double *out_point,
                           double *out_normal, uint32_t *out_trips) {
-    return sweep_entry<double>(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
+    return spira_tu::Impl<double>::sweep(scene, rays8, radii, n, flags, out_prim, out_t, out_point, out_normal, nullptr, out_trips, false, false, nullptr);
 }
 int spira_scene_sweep_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags, int *d_out_prim, double *d_out_t,
                                  double *d_out_point, double *d_out_normal, uint32_t *d_out_trips, void *stream) {
-    return sweep_entry<double>(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
+    return spira_tu::Impl<double>::sweep(scene, d_rays8, d_radii, n, flags, d_out_prim, d_out_t, d_out_point, d_out_normal, nullptr, d_out_trips, false, true, stream);
 }
 int spira_scene_sweep_blocked_f64(const spira_scene *scene, const double *rays8, const double *radii, uint32_t n, uint32_t flags, uint8_t *out_hit) {
-    return sweep_entry<double>(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+    return spira_tu::Impl<double>::sweep(scene, rays8, radii, n, flags, nullptr, nullptr, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
 }
 int spira_scene_sweep_blocked_device_f64(const spira_scene *scene, const double *d_rays8, const double *d_radii, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return sweep_entry<double>(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+    return spira_tu::Impl<double>::sweep(scene, d_rays8, d_radii, n, flags, nullptr, nullptr, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
 }
 // host arithmetic, no device: the leaf function the kernels and the scan call, with bound = t_max.  A miss: t = t_max copied, q 0.
 void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double o[3], const double d_unit[3], double r, double t_min, double t_max,
@@ -3193,31 +3130,31 @@ void spira_sweep_sphere_triangle_f64(const double v0[3], const double e1[3], con
 // ---- box overlap queries on a scene handle (spira_overlap.h)
 int spira_scene_overlap_box_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
                                 uint32_t *out_trips) {
-    return overlap_entry<float>(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+    return spira_tu::Impl<float>::overlap(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
 }
 int spira_scene_overlap_box_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim, uint32_t *d_out_count,
                                        uint32_t *d_out_trips, void *stream) {
-    return overlap_entry<float>(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+    return spira_tu::Impl<float>::overlap(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
 }
 int spira_scene_overlap_any_f32(const spira_scene *scene, const float *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
-    return overlap_entry<float>(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+    return spira_tu::Impl<float>::overlap(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
 }
 int spira_scene_overlap_any_device_f32(const spira_scene *scene, const float *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return overlap_entry<float>(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+    return spira_tu::Impl<float>::overlap(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
 }
 int spira_scene_overlap_box_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
                                 uint32_t *out_trips) {
-    return overlap_entry<double>(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+    return spira_tu::Impl<double>::overlap(scene, boxes10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
 }
 int spira_scene_overlap_box_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim, uint32_t *d_out_count,
                                        uint32_t *d_out_trips, void *stream) {
-    return overlap_entry<double>(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+    return spira_tu::Impl<double>::overlap(scene, d_boxes10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
 }
 int spira_scene_overlap_any_f64(const spira_scene *scene, const double *boxes10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
-    return overlap_entry<double>(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+    return spira_tu::Impl<double>::overlap(scene, boxes10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
 }
 int spira_scene_overlap_any_device_f64(const spira_scene *scene, const double *d_boxes10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
-    return overlap_entry<double>(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+    return spira_tu::Impl<double>::overlap(scene, d_boxes10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
 }
 // host arithmetic, no device: the leaf functions the kernels and the scan call, on a box prepared without a frame.  SPIRA_RAY_INVALID: the box is invalid.
 int spira_overlap_box_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float box10[10]) {
@@ -3244,38 +3181,38 @@ int spira_overlap_box_sphere_f64(const double centre[3], double radius, const do
 // ---- signed distance queries on a scene handle (spira_sdf.h)
 int spira_scene_signed_distance_f32(const spira_scene *scene, const float *points4, uint32_t n_points, uint32_t flags, int *out_prim, float *out_dist, float *out_point,
                                     uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips) {
-    return signed_distance_entry<float>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
+    return spira_tu::Impl<float>::signed_distance(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
 }
 int spira_scene_signed_distance_device_f32(const spira_scene *scene, const float *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, float *d_out_dist,
                                            float *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings, uint32_t *d_out_trips, void *stream) {
-    return signed_distance_entry<float>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
+    return spira_tu::Impl<float>::signed_distance(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
 }
 int spira_scene_signed_distance_f64(const spira_scene *scene, const double *points4, uint32_t n_points, uint32_t flags, int *out_prim, double *out_dist, double *out_point,
                                     uint8_t *out_inside, uint32_t *out_crossings, uint32_t *out_trips) {
-    return signed_distance_entry<double>(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
+    return spira_tu::Impl<double>::signed_distance(scene, points4, n_points, flags, out_prim, out_dist, out_point, out_inside, out_crossings, out_trips, false, nullptr);
 }
 int spira_scene_signed_distance_device_f64(const spira_scene *scene, const double *d_points4, uint32_t n_points, uint32_t flags, int *d_out_prim, double *d_out_dist,
                                            double *d_out_point, uint8_t *d_out_inside, uint32_t *d_out_crossings, uint32_t *d_out_trips, void *stream) {
-    return signed_distance_entry<double>(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
+    return spira_tu::Impl<double>::signed_distance(scene, d_points4, n_points, flags, d_out_prim, d_out_dist, d_out_point, d_out_inside, d_out_crossings, d_out_trips, true, stream);
 }
 
 // ---- radiance along the caller's rays, and the camera ray generator (spira_radiance.h)
 int spira_scene_radiance_f32(const spira_scene *scene, const float *rays6, uint32_t n_rays, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid) {
-    return radiance_entry<float>(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
+    return spira_tu::Impl<float>::radiance(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
 }
 int spira_scene_radiance_f64(const spira_scene *scene, const double *rays6, uint32_t n_rays, const spira_radiance *rp, double *sum_rgb, uint8_t *out_valid) {
-    return radiance_entry<double>(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
+    return spira_tu::Impl<double>::radiance(scene, rays6, n_rays, rp, sum_rgb, out_valid, false, nullptr);
 }
 int spira_scene_radiance_device_f32(const spira_scene *scene, const float *d_rays6, uint32_t n_rays, const spira_radiance *rp, float *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
-    return radiance_entry<float>(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
+    return spira_tu::Impl<float>::radiance(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
 }
 int spira_scene_radiance_device_f64(const spira_scene *scene, const double *d_rays6, uint32_t n_rays, const spira_radiance *rp, double *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
-    return radiance_entry<double>(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
+    return spira_tu::Impl<double>::radiance(scene, d_rays6, n_rays, rp, d_sum_rgb, d_out_valid, true, stream);
 }
-int spira_camera_rays_f32(const float camera12[12], const spira_lens *lens, float *rays6) { return camera_rays_entry<float>(camera12, lens, rays6, false, nullptr); }
-int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, double *rays6) { return camera_rays_entry<double>(camera12, lens, rays6, false, nullptr); }
-int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream) { return camera_rays_entry<float>(camera12, lens, d_rays6, true, stream); }
-int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream) { return camera_rays_entry<double>(camera12, lens, d_rays6, true, stream); }
+int spira_camera_rays_f32(const float camera12[12], const spira_lens *lens, float *rays6) { return spira_tu::Impl<float>::camera_rays(camera12, lens, rays6, false, nullptr); }
+int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, double *rays6) { return spira_tu::Impl<double>::camera_rays(camera12, lens, rays6, false, nullptr); }
+int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream) { return spira_tu::Impl<float>::camera_rays(camera12, lens, d_rays6, true, stream); }
+int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream) { return spira_tu::Impl<double>::camera_rays(camera12, lens, d_rays6, true, stream); }
 // Test support, outside the ABI like spira_debug_cast_plan: the plan a radiance call of n_rays x spp gets on a device of num_cus CUs, with the knobs of the
 // environment as the entries read them.  out8: grid, wpb, spp_pass, n_pass, direct, workspace entries (low, high word), the item cap.  No device needed.
 int spira_debug_radiance_plan(uint32_t n_rays, uint32_t spp, uint32_t num_cus, uint32_t *out8) {
@@ -3289,42 +3226,42 @@ int spira_debug_radiance_plan(uint32_t n_rays, uint32_t spp, uint32_t num_cus, u
 
 // ---- hemisphere gather at surface points (spira_gather.h)
 int spira_gather_rays_f32(const float *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6) {
-    return gather_rays_entry<float>(points6, n_points, sample, seed, key0, rays6, false, nullptr);
+    return spira_tu::Impl<float>::gather_rays(points6, n_points, sample, seed, key0, rays6, false, nullptr);
 }
 int spira_gather_rays_f64(const double *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *rays6) {
-    return gather_rays_entry<double>(points6, n_points, sample, seed, key0, rays6, false, nullptr);
+    return spira_tu::Impl<double>::gather_rays(points6, n_points, sample, seed, key0, rays6, false, nullptr);
 }
 int spira_gather_rays_device_f32(const float *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *d_rays6, void *stream) {
-    return gather_rays_entry<float>(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
+    return spira_tu::Impl<float>::gather_rays(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
 }
 int spira_gather_rays_device_f64(const double *d_points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *d_rays6, void *stream) {
-    return gather_rays_entry<double>(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
+    return spira_tu::Impl<double>::gather_rays(d_points6, n_points, sample, seed, key0, d_rays6, true, stream);
 }
 int spira_scene_gather_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_radiance *rp, float *sum_rgb, uint8_t *out_valid) {
-    return gather_entry<float>(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
+    return spira_tu::Impl<float>::gather(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
 }
 int spira_scene_gather_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_radiance *rp, double *sum_rgb, uint8_t *out_valid) {
-    return gather_entry<double>(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
+    return spira_tu::Impl<double>::gather(scene, points6, n_points, rp, sum_rgb, out_valid, false, nullptr);
 }
 int spira_scene_gather_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_radiance *rp, float *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
-    return gather_entry<float>(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
+    return spira_tu::Impl<float>::gather(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
 }
 int spira_scene_gather_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_radiance *rp, double *d_sum_rgb, uint8_t *d_out_valid, void *stream) {
-    return gather_entry<double>(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
+    return spira_tu::Impl<double>::gather(scene, d_points6, n_points, rp, d_sum_rgb, d_out_valid, true, stream);
 }
 int spira_scene_gather_visible_f32(const spira_scene *scene, const float *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible_u32, uint8_t *out_valid) {
-    return gather_visible_entry<float>(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
+    return spira_tu::Impl<float>::gather_visible(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
 }
 int spira_scene_gather_visible_f64(const spira_scene *scene, const double *points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *visible_u32, uint8_t *out_valid) {
-    return gather_visible_entry<double>(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
+    return spira_tu::Impl<double>::gather_visible(scene, points6, n_points, gv, visible_u32, out_valid, false, nullptr);
 }
 int spira_scene_gather_visible_device_f32(const spira_scene *scene, const float *d_points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *d_visible_u32,
                                           uint8_t *d_out_valid, void *stream) {
-    return gather_visible_entry<float>(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
+    return spira_tu::Impl<float>::gather_visible(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
 }
 int spira_scene_gather_visible_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_gather_visible *gv, uint32_t *d_visible_u32,
                                           uint8_t *d_out_valid, void *stream) {
-    return gather_visible_entry<double>(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
+    return spira_tu::Impl<double>::gather_visible(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
 }
 // Test support, outside the ABI like spira_debug_radiance_plan: the plan a gather of n_points x spp gets on a device of num_cus CUs, with the knobs of the
 // environment as the entries read them.  out8: grid, wpb, spp_pass, n_pass, direct, workspace entries (low, high word), the item cap.  No device needed.
@@ -3447,15 +3384,9 @@ void spira_shutdown(void) {
         if (!c.init) continue;
         (void)hipSetDevice(d);
         (void)hipDeviceSynchronize();
-        for (int i = 0; i < 2; ++i) { c.qA[i].release(); c.qB[i].release(); c.qC[i].release(); c.qR[i].release(); c.qK[i].release(); c.qX[i].release(); }
-        c.mesh_list.release(); c.mesh_count.release();
-        c.redo.release(); c.L.release(); c.accum.release(); c.counts.release(); c.blkstats.release(); c.stats.release(); c.scene.release(); c.out_tmp.release(); c.trace.release(); c.rng.release(); c.multi_tile.release(); c.multi_stack.release(); c.multi_full.release(); c.spd32.release(); c.spd64.release(); c.hyb_state.release(); c.hyb_mat.release(); c.hyb_flags.release();
-        c.ad_q.release(); c.ad_n.release(); c.ad_list[0].release(); c.ad_list[1].release(); c.ad_count.release();
+        c.release_all(); c.scene.release();
         if (c.h_ad_count) { (void)hipHostFree(c.h_ad_count); c.h_ad_count = nullptr; }
-        c.dn_rec[0].release(); c.dn_rec[1].release(); c.dn_guide.release(); c.dn_io.release();
-        c.refit_status.release(); c.list_io.release();
         if (c.h_refit_status) { (void)hipHostFree(c.h_refit_status); c.h_refit_status = nullptr; }
-        c.lbvh_ws.release(); c.lbvh_nodes.release(); c.lbvh_small.release();
         for (void *q : c.lbvh_retired) (void)hipFree(q);
         c.lbvh_retired.clear();
         if (c.h_lbvh) { (void)hipHostFree(c.h_lbvh); c.h_lbvh = nullptr; }
@@ -3568,22 +3499,22 @@ int spira_scene_destroy(spira_scene *scene) {
 }
 // ---- new contents for a live handle (host arrays, NULL = unchanged; a device triangle array on the caller's stream): the tree is refitted, not rebuilt
 int spira_scene_update_f32(spira_scene *scene, const float *spheres5, const float *materials8, const float *triangles10) {
-    return scene_update_entry<float>(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
+    return spira_tu::Impl<float>::scene_update(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
 }
 int spira_scene_update_f64(spira_scene *scene, const double *spheres5, const double *materials8, const double *triangles10) {
-    return scene_update_entry<double>(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
+    return spira_tu::Impl<double>::scene_update(scene, spheres5, materials8, triangles10, nullptr, false, nullptr);
 }
 int spira_scene_update_device_f32(spira_scene *scene, const float *d_triangles10, void *stream) {
-    return scene_update_entry<float>(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
+    return spira_tu::Impl<float>::scene_update(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
 }
 int spira_scene_update_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) {
-    return scene_update_entry<double>(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
+    return spira_tu::Impl<double>::scene_update(scene, nullptr, nullptr, nullptr, d_triangles10, true, stream);
 }
 // ---- a new triangle array for a live handle, the tree built anew on the device: a new frame, a new topology, no frame rule
-int spira_scene_rebuild_f32(spira_scene *scene, const float *triangles10) { return scene_rebuild_entry<float>(scene, triangles10, nullptr, false, nullptr); }
-int spira_scene_rebuild_f64(spira_scene *scene, const double *triangles10) { return scene_rebuild_entry<double>(scene, triangles10, nullptr, false, nullptr); }
-int spira_scene_rebuild_device_f32(spira_scene *scene, const float *d_triangles10, void *stream) { return scene_rebuild_entry<float>(scene, nullptr, d_triangles10, true, stream); }
-int spira_scene_rebuild_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) { return scene_rebuild_entry<double>(scene, nullptr, d_triangles10, true, stream); }
+int spira_scene_rebuild_f32(spira_scene *scene, const float *triangles10) { return spira_tu::Impl<float>::scene_rebuild(scene, triangles10, nullptr, false, nullptr); }
+int spira_scene_rebuild_f64(spira_scene *scene, const double *triangles10) { return spira_tu::Impl<double>::scene_rebuild(scene, triangles10, nullptr, false, nullptr); }
+int spira_scene_rebuild_device_f32(spira_scene *scene, const float *d_triangles10, void *stream) { return spira_tu::Impl<float>::scene_rebuild(scene, nullptr, d_triangles10, true, stream); }
+int spira_scene_rebuild_device_f64(spira_scene *scene, const double *d_triangles10, void *stream) { return spira_tu::Impl<double>::scene_rebuild(scene, nullptr, d_triangles10, true, stream); }
 int spira_render_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, float *out_hdr, float *out_img) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
     return render_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, out_hdr, out_img, false, nullptr);
@@ -3604,31 +3535,31 @@ int spira_render_scene_device_f64(const spira_scene *scene, const double cam[12]
 // ---- adaptive sampling: render to a noise target (host arrays; a handle; a handle and device outputs on the caller's stream)
 int spira_render_adaptive_f32(const float *s, const float *m, const float *t, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
                               float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q) {
-    return render_adaptive_entry<float>(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+    return spira_tu::Impl<float>::render_adaptive(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
 }
 int spira_render_adaptive_f64(const double *s, const double *m, const double *t, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
                               double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q) {
-    return render_adaptive_entry<double>(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+    return spira_tu::Impl<double>::render_adaptive(nullptr, s, m, t, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
 }
 int spira_render_adaptive_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
                                     float *out_hdr, float *out_img, uint32_t *out_spp, float *out_q) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return render_adaptive_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+    return spira_tu::Impl<float>::render_adaptive(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
 }
 int spira_render_adaptive_scene_f64(const spira_scene *scene, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
                                     double *out_hdr, double *out_img, uint32_t *out_spp, double *out_q) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return render_adaptive_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
+    return spira_tu::Impl<double>::render_adaptive(scene, nullptr, nullptr, nullptr, cam, p, adaptive, out_hdr, out_img, out_spp, out_q, false, nullptr);
 }
 int spira_render_adaptive_scene_device_f32(const spira_scene *scene, const float cam[12], const spira_params *p, const spira_adaptive *adaptive,
                                            float *d_hdr, float *d_img, uint32_t *d_spp, float *d_q, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return render_adaptive_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
+    return spira_tu::Impl<float>::render_adaptive(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
 }
 int spira_render_adaptive_scene_device_f64(const spira_scene *scene, const double cam[12], const spira_params *p, const spira_adaptive *adaptive,
                                            double *d_hdr, double *d_img, uint32_t *d_spp, double *d_q, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return render_adaptive_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
+    return spira_tu::Impl<double>::render_adaptive(scene, nullptr, nullptr, nullptr, cam, p, adaptive, d_hdr, d_img, d_spp, d_q, true, stream);
 }
 int spira_sky_pixel_f64(const double cam[12], uint32_t width, uint32_t height, uint32_t i, uint32_t j, const double *spheres5, uint32_t n_spheres) {
     if (!cam || (n_spheres && !spheres5)) return fail(SPIRA_E_INVALID, "cam or spheres5 is NULL");
@@ -3649,47 +3580,47 @@ int spira_adaptive_converged_f64(const double sum3[3], double q, uint32_t n, dou
 // ---- first-hit feature buffers (host arrays; a handle; a handle and device outputs on the caller's stream)
 int spira_render_features_f32(const float *s, const float *m, const float *t, const float cam[12], const spira_params *p,
                               float *out_albedo, float *out_normal, float *out_depth) {
-    return features_entry<float>(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+    return spira_tu::Impl<float>::features(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
 }
 int spira_render_features_f64(const double *s, const double *m, const double *t, const double cam[12], const spira_params *p,
                               double *out_albedo, double *out_normal, double *out_depth) {
-    return features_entry<double>(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+    return spira_tu::Impl<double>::features(nullptr, s, m, t, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
 }
 int spira_render_features_scene_f32(const spira_scene *scene, const float cam[12], const spira_params *p, float *out_albedo, float *out_normal, float *out_depth) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return features_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+    return spira_tu::Impl<float>::features(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
 }
 int spira_render_features_scene_f64(const spira_scene *scene, const double cam[12], const spira_params *p, double *out_albedo, double *out_normal, double *out_depth) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return features_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
+    return spira_tu::Impl<double>::features(scene, nullptr, nullptr, nullptr, cam, p, out_albedo, out_normal, out_depth, false, nullptr);
 }
 int spira_render_features_scene_device_f32(const spira_scene *scene, const float cam[12], const spira_params *p,
                                            float *d_albedo, float *d_normal, float *d_depth, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return features_entry<float>(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
+    return spira_tu::Impl<float>::features(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
 }
 int spira_render_features_scene_device_f64(const spira_scene *scene, const double cam[12], const spira_params *p,
                                            double *d_albedo, double *d_normal, double *d_depth, void *stream) {
     if (!scene) return fail(SPIRA_E_INVALID, "scene handle is NULL or was destroyed");
-    return features_entry<double>(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
+    return spira_tu::Impl<double>::features(scene, nullptr, nullptr, nullptr, cam, p, d_albedo, d_normal, d_depth, true, stream);
 }
 
 // ---- the a-trous denoiser (host planes; device planes on the caller's stream)
 int spira_denoise_f32(const float *color, const float *variance, const float *albedo, const float *normal, const float *depth, const spira_denoise *dn,
                       float *out_hdr, float *out_img) {
-    return denoise_entry<float>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
+    return spira_tu::Impl<float>::denoise(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
 }
 int spira_denoise_f64(const double *color, const double *variance, const double *albedo, const double *normal, const double *depth, const spira_denoise *dn,
                       double *out_hdr, double *out_img) {
-    return denoise_entry<double>(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
+    return spira_tu::Impl<double>::denoise(color, variance, albedo, normal, depth, dn, out_hdr, out_img, false, nullptr);
 }
 int spira_denoise_device_f32(const float *d_color, const float *d_variance, const float *d_albedo, const float *d_normal, const float *d_depth, const spira_denoise *dn,
                              float *d_out_hdr, float *d_out_img, void *stream) {
-    return denoise_entry<float>(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
+    return spira_tu::Impl<float>::denoise(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
 }
 int spira_denoise_device_f64(const double *d_color, const double *d_variance, const double *d_albedo, const double *d_normal, const double *d_depth, const spira_denoise *dn,
                              double *d_out_hdr, double *d_out_img, void *stream) {
-    return denoise_entry<double>(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
+    return spira_tu::Impl<double>::denoise(d_color, d_variance, d_albedo, d_normal, d_depth, dn, d_out_hdr, d_out_img, true, stream);
 }
 
 // ---- multi-device render on one node: interleaved 8-row stripes, one host thread + stream per device, one RCCL gather
@@ -3704,15 +3635,11 @@ int spira_render_multi_f64(const double *s, const double *m, const double *t, co
 
 int spira_trace_paths_f32(const float *s, const float *m, const float *t, const float cam[12], const spira_params *p, uint32_t n_paths,
                           const uint32_t *ijs, int *prims, float *ts, float *dirs, float *radiance) {
-#ifdef SPIRA_TU_MAIN
-    return spira_tu::trace_impl_f32(s, m, t, cam, p, n_paths, ijs, prims, ts, dirs, radiance);
-#else
-    return trace_impl<float>(s, m, t, cam, p, n_paths, ijs, prims, ts, dirs, radiance);
-#endif
+    return spira_tu::Impl<float>::trace(s, m, t, cam, p, n_paths, ijs, prims, ts, dirs, radiance);
 }
 int spira_trace_paths_f64(const double *s, const double *m, const double *t, const double cam[12], const spira_params *p, uint32_t n_paths,
                           const uint32_t *ijs, int *prims, double *ts, double *dirs, double *radiance) {
-    return trace_impl<double>(s, m, t, cam, p, n_paths, ijs, prims, ts, dirs, radiance);
+    return spira_tu::Impl<double>::trace(s, m, t, cam, p, n_paths, ijs, prims, ts, dirs, radiance);
 }
 
 int spira_tonemap_f32(float *values, uint64_t n, uint32_t post) {

@@ -71,10 +71,25 @@ def test_library_is_gfx950_only():
         assert b"gfx950" in blob and b"gfx942" not in blob and b"gfx90a" not in blob
 
 
+# The entries that a Float32 call has to reach in the SPIRA_TU_F32 unit: the members of spira_tu::Impl<T> (csrc/spira_hip.hip, top)
+IMPL_MEMBERS = ("render", "trace", "render_adaptive", "features", "denoise", "scene_update", "scene_rebuild", "cast", "nearest", "hits", "nearest_k", "sweep",
+                "overlap", "signed_distance", "radiance", "camera_rays", "gather", "gather_visible", "gather_rays")
+# Kernels that no flag was chosen for, held to the unit the build has always put them in: those without a precision argument, and k_assemble<T>, whose T is
+# only the element it copies (spira_render_multi_*: launched from the main unit for both precisions).
+UNIT_OF_THE_OTHER_KERNELS = {
+    "main": {"k_lbvh_sort_tile", "k_lbvh_sort_wide", "k_lbvh_radix", "k_lbvh_boxes", "k_lbvh_make", "k_lbvh_scan", "k_lbvh_write", "k_fold_stats", "k_hybrid_init",
+             "k_assemble"},
+    "f32": {"k_fold_stats", "k_hybrid_init"},
+    "f64mesh": set(),
+}
+COPIES_ONLY = {"k_assemble"}
+
+
 def test_the_translation_units_hold_the_kernels_they_are_built_for():
     """csrc/Makefile builds spira_hip.hip three times: SPIRA_TU_F32 (-fno-slp-vectorize) must hold every Float32 kernel and no Float64 one,
     SPIRA_TU_F64MESH (compiler defaults) the Float64 path kernels of mesh scenes and nothing else, SPIRA_TU_MAIN (fewer branches folded into selects) every
-    other Float64 kernel — a kernel instantiated in the wrong unit would silently run the slower code (profiles/r03_compiler_flags.md)."""
+    other Float64 kernel — a kernel instantiated in the wrong unit would silently run the slower code (profiles/r03_compiler_flags.md).
+    The rule is held against every kernel host stub the three objects contain, not against a list of names: symbols only, no assembly."""
     import subprocess
     csrc = os.path.join(ROOT, "julia-spira_amd", "csrc")
     objs = {n: os.path.join(csrc, "spira_tu_%s.o" % n) for n in ("main", "f32", "f64mesh")}
@@ -90,8 +105,35 @@ def test_the_translation_units_hold_the_kernels_they_are_built_for():
     assert count(syms["f32"], "6k_pathIf") > 0 and count(syms["f32"], "6k_pathId") == 0
     assert count(syms["main"], "6k_pathIf") == 0 and count(syms["main"], "6k_pathIdLi[12]ELb0E") > 0 and count(syms["main"], "6k_pathIdLi[12]ELb1E") == 0
     assert count(syms["f64mesh"], "6k_pathIf") == 0 and count(syms["f64mesh"], "6k_pathIdLi[12]ELb1E") > 0 and count(syms["f64mesh"], "6k_pathIdLi[12]ELb0E") == 0
-    for fn, unit in (("render_impl_f32", "f32"), ("trace_impl_f32", "f32"), ("launch_path_mesh_f64", "f64mesh"), ("launch_path_resume_f64", "f64mesh")):
-        assert re.search(r" T .*%s" % fn, syms[unit]) and re.search(r" U .*%s" % fn, syms["main"]), fn
+    # every stub there is: <length>__device_stub__<kernel> and then I<first template argument>... of a template, E of a plain function
+    others = {n: set() for n in objs}
+    seen = {n: 0 for n in objs}
+    for unit, text in syms.items():
+        for stub, kern, targs in re.findall(r"(\d+__device_stub__(k_[a-z0-9_]+)(I\S*|E))", text):
+            prec = targs[1] if targs[0] == "I" and targs[1] in "fd" and kern not in COPIES_ONLY else None
+            if prec is None:
+                others[unit].add(kern)
+            elif prec == "f":
+                assert unit == "f32", (unit, stub)
+            else:
+                mesh_path = kern == "k_path" and re.match(r"IdLi[12]ELb1E", targs) is not None
+                assert unit == ("f64mesh" if mesh_path else "main"), (unit, stub)
+            seen[unit] += 1
+    assert all(seen.values()), seen
+    assert others == UNIT_OF_THE_OTHER_KERNELS
+    # the entries: every member of Impl<float> defined (weak: an explicit instantiation) in the Float32 unit and only named by the main one, all 19
+    # of them and whatever joins them; nothing of Impl<float>, a lambda of a member included, is defined in the main unit; Impl<double> the other way round
+    member = r"^[0-9a-f ]+ (\w) _ZN8spira_tu4ImplI%sE\d+([a-z0-9_]+)E"
+    f32_members = dict((m, k) for k, m in re.findall(member % "f", syms["f32"], flags=re.M))
+    assert set(IMPL_MEMBERS) <= set(f32_members) and len(IMPL_MEMBERS) == 19
+    main_names = dict((m, k) for k, m in re.findall(member % "f", syms["main"], flags=re.M))
+    for m, kind in f32_members.items():
+        assert kind == "W" and main_names.get(m) == "U", (m, kind, main_names.get(m))
+    assert not re.search(r" [A-TV-Za-tv-z] \S*8spira_tu4ImplIfE", syms["main"])
+    assert not re.search(r"8spira_tu4ImplIdE", syms["f32"]) and not re.search(r"8spira_tu4ImplI[fd]E", syms["f64mesh"])
+    assert set(IMPL_MEMBERS) <= set(m for k, m in re.findall(member % "d", syms["main"], flags=re.M) if k == "W")
+    for fn in ("launch_path_mesh_f64", "launch_path_resume_f64"):
+        assert re.search(r" T .*%s" % fn, syms["f64mesh"]) and re.search(r" U .*%s" % fn, syms["main"]), fn
     assert not re.search(r" T spira_render_f32", syms["f32"]) and not re.search(r" T spira_render_f64", syms["f64mesh"])
     mk = open(os.path.join(csrc, "Makefile")).read()
     for flag in ("-DSPIRA_TU_F32", "-fno-slp-vectorize", "-DSPIRA_TU_MAIN", "-DSPIRA_TU_F64MESH", "-two-entry-phi-node-folding-threshold=1"):

@@ -44,7 +44,7 @@ def test_adaptive_kernels_live_in_the_unit_of_their_precision_and_beside_k_path(
             for line in text.splitlines():
                 if kern in line:
                     assert "6k_pathI" not in line
-    assert re.search(r" T .*render_adaptive_impl_f32", syms["f32"]) and re.search(r" U .*render_adaptive_impl_f32", syms["main"])
+    assert re.search(r" W _ZN8spira_tu4ImplIfE15render_adaptiveE", syms["f32"]) and re.search(r" U _ZN8spira_tu4ImplIfE15render_adaptiveE", syms["main"])
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "spira_adaptive.h" in mk.split("DEPS", 1)[1].split("\n", 1)[0]      # hashed into spira_build_id
 

@@ -45,8 +45,8 @@ def test_kernels_live_in_the_unit_of_their_precision():
         assert len(re.findall(kern + "I[fd]", syms["f64mesh"])) == 0, kern
     # three feature launches per precision: spheres alone, LDS triangles, a BVH mesh
     assert len(set(re.findall(r"10k_featuresIfLb[01]ELb[01]E", syms["f32"]))) == 3
-    for fn in ("features_impl_f32", "denoise_impl_f32"):
-        assert re.search(r" T .*%s" % fn, syms["f32"]) and re.search(r" U .*%s" % fn, syms["main"]), fn
+    for fn in ("_ZN8spira_tu4ImplIfE8featuresE", "_ZN8spira_tu4ImplIfE7denoiseE"):
+        assert re.search(r" W %s" % fn, syms["f32"]) and re.search(r" U %s" % fn, syms["main"]), fn
 
 
 # ---- the numpy restatement against known answers (exact: every weight is a dyadic rational)

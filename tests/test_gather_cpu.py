@@ -78,8 +78,8 @@ def test_the_kernels_sit_in_the_unit_of_their_precision():
     for unit, t in (("main", "d"), ("f32", "f")):
         assert len(set(re.findall(r"_ZN5spira8k_gatherI%sLb[01]ELb[01]EEEvNS_10GatherArgsIT_EE" % t, syms[unit]))) == 4      # BVH x EXT
         assert len(set(re.findall(r"_ZN5spira16k_gather_visibleI%sLb[01]ELb[01]EEEvNS_17GatherVisibleArgsIT_EE" % t, syms[unit]))) == 3
-    for fn in ("gather_impl_f32", "gather_visible_impl_f32", "gather_rays_impl_f32"):
-        assert re.search(r" T .*%s" % fn, syms["f32"]) and re.search(r" U .*%s" % fn, syms["main"]), fn
+    for fn in ("_ZN8spira_tu4ImplIfE6gatherE", "_ZN8spira_tu4ImplIfE14gather_visibleE", "_ZN8spira_tu4ImplIfE11gather_raysE"):
+        assert re.search(r" W %s" % fn, syms["f32"]) and re.search(r" U %s" % fn, syms["main"]), fn
 
 
 @pytest.mark.parametrize("prec", ["f32", "f64"])

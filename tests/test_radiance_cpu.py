@@ -67,8 +67,8 @@ def test_the_kernels_sit_in_the_unit_of_their_precision():
     # four instantiations of k_radiance per precision: BVH x EXT
     for unit, t in (("main", "d"), ("f32", "f")):
         assert len(set(re.findall(r"_ZN5spira10k_radianceI%sLb[01]ELb[01]EEEvNS_12RadianceArgsIT_EE" % t, syms[unit]))) == 4
-    for fn in ("radiance_impl_f32", "camera_rays_impl_f32"):
-        assert re.search(r" T .*%s" % fn, syms["f32"]) and re.search(r" U .*%s" % fn, syms["main"]), fn
+    for fn in ("_ZN8spira_tu4ImplIfE8radianceE", "_ZN8spira_tu4ImplIfE11camera_raysE"):
+        assert re.search(r" W %s" % fn, syms["f32"]) and re.search(r" U %s" % fn, syms["main"]), fn
 
 
 def test_return_codes_without_a_device(binding):

@@ -59,7 +59,7 @@ def test_rebuild_kernels_live_in_the_unit_of_their_precision():
         assert len(re.findall(kern + "I[fd]", syms["f64mesh"])) == 0, kern
     for kern in ("k_lbvh_radix", "k_lbvh_boxes", "k_lbvh_make", "k_lbvh_scan", "k_lbvh_write"):      # nothing of these reads T: compiled once
         assert kern in syms["main"] and kern not in syms["f32"] and kern not in syms["f64mesh"], kern
-    assert re.search(r" T .*scene_rebuild_impl_f32", syms["f32"]) and re.search(r" U .*scene_rebuild_impl_f32", syms["main"])
+    assert re.search(r" W _ZN8spira_tu4ImplIfE13scene_rebuildE", syms["f32"]) and re.search(r" U _ZN8spira_tu4ImplIfE13scene_rebuildE", syms["main"])
     assert re.search(r" T .*lbvh_topology", syms["main"]) and re.search(r" U .*lbvh_topology", syms["f32"]) and "lbvh_topology" not in syms["f64mesh"]
 
 

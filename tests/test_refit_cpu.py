@@ -47,7 +47,7 @@ def test_refit_kernels_live_in_the_unit_of_their_precision():
         assert len(re.findall(kern + "If", syms["f32"])) > 0 and len(re.findall(kern + "Id", syms["f32"])) == 0, kern
         assert len(re.findall(kern + "Id", syms["main"])) > 0 and len(re.findall(kern + "If", syms["main"])) == 0, kern
         assert len(re.findall(kern + "I[fd]", syms["f64mesh"])) == 0, kern
-    assert re.search(r" T .*scene_update_impl_f32", syms["f32"]) and re.search(r" U .*scene_update_impl_f32", syms["main"])
+    assert re.search(r" W _ZN8spira_tu4ImplIfE12scene_updateE", syms["f32"]) and re.search(r" U _ZN8spira_tu4ImplIfE12scene_updateE", syms["main"])
     mk = open(os.path.join(csrc, "Makefile")).read()
     assert "spira_refit.h" in mk.split("DEPS", 1)[1].split("\n", 1)[0]      # hashed into spira_build_id
 
