@@ -177,6 +177,7 @@ int         spira_device_count(void);
 int         spira_set_device(int device);      /* device used by subsequent calls on this thread */
 int         spira_get_counters(spira_counters *out);
 int         spira_get_sky_pixels(uint64_t *out);   /* of the same render: pixels of all-sky runs that k_path summed ahead of its loop (SPIRA_SKY_RUNS; 0 wherever no pixel-owning pass ran).  Beside spira_counters, whose layout stays */
+int         spira_get_own_passes(uint64_t *out);   /* of the same render: passes that k_path_own rendered — full pixel-owning passes of 64 slots of a Float64 sphere scene (SPIRA_OWN_KERNEL; 0 wherever every pass ran k_path) */
 void        spira_shutdown(void);              /* frees cached device workspaces */
 
 /* ---- camera (host arithmetic only; no device needed) ---- */

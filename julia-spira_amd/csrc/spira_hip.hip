@@ -230,6 +230,8 @@ struct Ctx : CtxBuffers {
     std::vector<size_t> ev_mid_end;           // ... and the ev_pool index of the event that closes that pass's bracket
     size_t ev_mid_used = 0;
     spira_counters last{};
+    uint64_t own_passes = 0;                  // passes of the call being enqueued that run k_path_own (counted as they are enqueued; slabs add up) ...
+    uint64_t last_own_passes = 0;             // ... and spira_get_own_passes: that count as end_counters latched it, of the render spira_get_counters describes
     uint64_t last_sky_pixels = 0;             // spira_get_sky_pixels: Stats::sky_pixels of the same render (spira_counters keeps its layout)
     bool last_valid = false, last_pending = false;
     hipStream_t last_stream = nullptr;
@@ -533,11 +535,26 @@ int launch_bounce(int R, dim3 grid, size_t lds, hipStream_t st, const spira::Bou
 // spec == 2 (SPIRA_SPEC_DIV=2, tests): every wave is reported, i.e. the whole pass is rendered twice.
 // MODE: PathArgs::mesh_mode as a template argument (mesh scenes: 0 one launch, 1 the parking launch of two; 2 is launch_path_resume below).
 // TRI = false: the scene holds no LDS-resident triangles (spheres only, or spheres + a BVH mesh): instantiations without the triangle scan
+// own_kernel (spira_plan.h, own_kernel_ok; verify_path_args has checked it against `a`): k_path_own instead of k_path, the same two launches.
 template <class T, bool BVH, int MODE>
-int launch_path_mode(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathArgs<T> a, int spec) {
+int launch_path_mode(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathArgs<T> a, int spec, bool own_kernel = false) {
     const bool ext = (a.rc.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) != 0;
     const bool tri = a.scene.n_triangles != 0;
     const dim3 blk(spira::kBlock);
+    if (own_kernel) {
+#if defined(SPIRA_TU_MAIN) || !(defined(SPIRA_TU_F32) || defined(SPIRA_TU_F64MESH))
+        if constexpr (sizeof(T) == 8 && !BVH && MODE == 0) {
+            if (spec) {
+                a.redo_only = spec == 2 ? 2 : 0;
+                if (int rc = launch_lds(spira::k_path_own<T, true>, grid, blk, lds, st, a)) return rc;
+                if (spec == 2) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)a.redo, 1, (size_t)grid.x * (spira::kBlock / 64), st));
+                a.redo_only = 1;
+            } else { a.redo = nullptr; a.redo_only = 0; }
+            return launch_lds(spira::k_path_own<T, false>, grid, blk, lds, st, a);
+        }
+#endif
+        return fail(SPIRA_E_LIMIT, "internal: k_path_own exists for Float64 sphere passes only");      // a missing kernel is an error, never another kernel
+    }
     if (ext) {           // extension instantiations (R = 2 only); like the default kernels, without the LDS triangle scan where the scene has none
         if (spec) {
             a.redo_only = spec == 2 ? 2 : 0;          // (2: every wave will be rendered again, whatever it reports)
@@ -563,8 +580,9 @@ int launch_path_mode(int R, dim3 grid, size_t lds, hipStream_t st, spira::PathAr
     return launch_lds(spira::k_path<T, 1, BVH, false, false, MODE>, grid, blk, lds, st, a);
 }
 template <class T>
-int launch_path(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<T> &a, int spec) {
-    if (!a.scene.n_bvh_tris) return launch_path_mode<T, false, 0>(R, grid, lds, st, a, spec);
+int launch_path(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<T> &a, int spec, bool own_kernel) {
+    if (!a.scene.n_bvh_tris) return launch_path_mode<T, false, 0>(R, grid, lds, st, a, spec, own_kernel);
+    if (own_kernel) return fail(SPIRA_E_LIMIT, "internal: k_path_own exists for Float64 sphere passes only");
 #ifdef SPIRA_TU_MAIN
     if constexpr (sizeof(T) == 8) return spira_tu::launch_path_mesh_f64(R, grid, lds, st, a, spec);
     else
@@ -790,6 +808,7 @@ spira::Knobs read_knobs() {
     k.cam_consts = env_u32("SPIRA_CAM_CONSTS", 1);
     k.sky_runs = env_u32("SPIRA_SKY_RUNS", 1);
     k.pixel_table = env_u32("SPIRA_PIXEL_TABLE", 1); k.reach_masks = env_u32("SPIRA_REACH_MASKS", 1);
+    k.own_kernel = env_u32("SPIRA_OWN_KERNEL", 1);
     return k;
 }
 template <class T>
@@ -827,10 +846,9 @@ int ensure_workspaces(Ctx &c, const spira::Workspace &w) {
 // launched (spira_plan.h, path_need); a launch that would not fit is refused (SPIRA_E_LIMIT) instead of letting a kernel write past a buffer nobody
 // sized.  (Round 3's fuzz found exactly that: a depth-1 mesh render writing parked rays' hits into queues only `max_depth > 1` used to size.)
 static_assert(sizeof(spira::PixelEntry) == spira::kPixelEntryBytes && spira::kOwnRuns * SPIRA_RESOLVE_RUN == 64, "own_lds_bytes sizes what k_path's prologue writes");
+// (R, own_knob: Plan::R and Plan::own_kernel, which own_kernel_ok reads beside the arguments)
 template <class T>
-int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_launch_blocks, size_t own_lds = 0) {
-    using P4 = spira::Pack4<T>;
-    using P2 = spira::Pack2<T>;
+spira::PathLaunch path_launch_of(const spira::PathArgs<T> &a, uint32_t first_launch_blocks, size_t own_lds, uint32_t R, bool own_knob) {
     spira::PathLaunch l;
     l.blocks = first_launch_blocks; l.cap = a.cap; l.n_first = a.n_first; l.k_eff = a.k_eff;
     l.tile_pixels = a.rc.tile_pixels; l.max_depth = a.rc.max_depth; l.flags = a.rc.flags; l.n_lds_triangles = a.scene.n_triangles;
@@ -838,6 +856,15 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
     l.mesh = a.scene.n_bvh_tris != 0; l.pixel_owning = a.accum != nullptr; l.l_private = a.l_private != 0;
     l.prec = sizeof(T); l.wpb = spira::kBlock / 64; l.carry_key = SPIRA_CARRY_KEY;
     l.pixel_table = a.pixel_table != 0; l.reach_masks = a.reach_masks != 0; l.own_lds = own_lds;
+    l.R = R; l.n_spheres = a.scene.n_spheres; l.sky_runs = a.sky_runs != 0; l.cam_consts = a.cam_consts != 0; l.own_kernel = own_knob;
+    return l;
+}
+// own_kernel: the launch is k_path_own's — refused unless that is exactly what own_kernel_ok says of these arguments
+template <class T>
+int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_launch_blocks, size_t own_lds = 0, uint32_t R = 0, bool own_knob = false, bool own_kernel = false) {
+    using P4 = spira::Pack4<T>;
+    using P2 = spira::Pack2<T>;
+    const spira::PathLaunch l = path_launch_of<T>(a, first_launch_blocks, own_lds, R, own_knob);
     const spira::PathNeed need = spira::path_need(l);
     const uint64_t nw = need.nw, n = need.packets;
     auto covers = [](const DevBuf &b, const void *ptr, uint64_t bytes) { return ptr == b.p && b.p != nullptr && b.cap >= bytes; };
@@ -857,6 +884,8 @@ int verify_path_args(const Ctx &c, const spira::PathArgs<T> &a, uint32_t first_l
     if (!bad && a.accum && (!covers(c.accum, a.accum, (uint64_t)a.rc.tile_pixels * sizeof(P4)) || !need.owning_ok)) bad = "pixel-owning pass";
     if (!bad && a.l_private && !need.private_ok) bad = "wave-private radiance blocks";
     if (!bad && !need.table_ok) bad = "pixel table and reach masks in LDS";
+    // k_path_own holds as constants what these arguments say: it runs exactly where they say all of it (and the knob is on)
+    if (!bad && own_kernel != spira::own_kernel_ok(l)) bad = "the kernel of a full pixel-owning pass";
     if (bad) return fail(SPIRA_E_LIMIT, std::string("internal: a workspace is smaller than the launch needs (") + bad + ")");
     return 0;
 }
@@ -1044,9 +1073,12 @@ int enqueue_path_pass(Call<T> &k, uint32_t *stat_rows) {
             pa.pixel_table = plan.pixel_table ? 1u : 0u; pa.reach_masks = plan.reach_masks ? 1u : 0u;
         }
     }
-    if (int rc = verify_path_args<T>(c, pa, G, own_lds)) return rc;     // every pointer against the capacity of its buffer, for THIS grid
+    // a full pass of 64 slots with everything above granted runs k_path_own (spira_plan.h, own_kernel_ok): pass by pass, from the arguments as they stand
+    const bool own_kernel = spira::own_kernel_ok(path_launch_of<T>(pa, G, own_lds, plan.R, plan.own_kernel));
+    if (int rc = verify_path_args<T>(c, pa, G, own_lds, plan.R, plan.own_kernel, own_kernel)) return rc;     // every pointer against the capacity of its buffer, for THIS grid
     HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used++], k.st));
-    if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec)) return rc;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
+    if (int rc = launch_path<T>((int)plan.R, dim3(G), lds_a, k.st, pa, k.spec, own_kernel)) return rc;
+    if (own_kernel) ++c.own_passes;      // (a kernel that was refused its LDS did not run: nothing that consumes its output is enqueued)
     k.launches += k.spec ? 2 : 1;      // the speculative launch and its exact follow-up
     if (pa.mesh_mode == 1) {           // second launch: nw / k fat waves
         if (c.ev_mid.size() <= c.ev_mid_used) {
@@ -1155,6 +1187,7 @@ int begin_counters(Session &s, bool cont) {
     if (cont) return 0;
     c.ev_used = 0;
     c.ev_mid_used = 0;
+    c.own_passes = 0;
     HIP_TRY(hipMemsetAsync(c.stats.p, 0, sizeof(spira::Stats), s.st));
     HIP_TRY(hipEventRecord(c.ev_start, s.st));
     return 0;
@@ -1169,6 +1202,7 @@ int end_counters(Session &s, const spira_counters &delta, bool cont) {
     c.last.passes += delta.passes;
     c.last.launches += delta.launches;
     c.last.bounce_launches += delta.bounce_launches;
+    c.last_own_passes = c.own_passes;
     c.last_valid = true;
     c.last_pending = true;
     c.last_stream = s.st;
@@ -3373,6 +3407,16 @@ int spira_get_sky_pixels(uint64_t *out) {
     if (int rc = get_ctx(&cp)) return rc;
     std::lock_guard<std::recursive_mutex> lock(cp->mu);
     *out = cp->last_sky_pixels;
+    return 0;
+}
+
+int spira_get_own_passes(uint64_t *out) {
+    if (!out) return fail(SPIRA_E_INVALID, "out is NULL");
+    Ctx *cp = nullptr;
+    if (int rc = get_ctx(&cp)) return rc;
+    std::lock_guard<std::recursive_mutex> lock(cp->mu);
+    if (!cp->last_valid) return fail(SPIRA_E_INVALID, "no render has run on this device");
+    *out = cp->last_own_passes;
     return 0;
 }
 

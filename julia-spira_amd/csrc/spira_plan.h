@@ -22,6 +22,7 @@ struct Knobs {
     uint32_t sky_runs = 1;                     // SPIRA_SKY_RUNS: pixel-owning passes sum their all-sky runs ahead of the loop (0: every path goes through it; A/B, tests)
     uint32_t pixel_table = 1;                  // SPIRA_PIXEL_TABLE: their camera rows read pixel, i, j and the two inner key hashes from a per-wave LDS table (0: path_of and the mixes per path)
     uint32_t reach_masks = 1;                  // SPIRA_REACH_MASKS: their camera rows test only the spheres their pixel run can reach (0: every sphere)
+    uint32_t own_kernel = 1;                   // SPIRA_OWN_KERNEL: their full passes of 64 slots run k_path_own where own_kernel_ok() holds (0: k_path everywhere; A/B, tests)
 };
 
 struct PlanIn {
@@ -58,6 +59,7 @@ struct Plan {
     bool fused = false, l_private = false;                 // pixel-owning passes (PathArgs::accum); wave-private radiance blocks (PathArgs::l_private)
     bool sky_runs = false;                                 // ... whose all-sky runs never enter the loop (PathArgs::sky_runs)
     bool pixel_table = false, reach_masks = false;         // ... whose camera rows are fed from the wave's pixel table / scan by their run's reach mask (PathArgs, same names)
+    bool own_kernel = false;                               // ... whose passes may run k_path_own (decided pass by pass: own_kernel_ok)
     bool spec_allowed = false;                             // the organisation has a speculative-division launch for this call
     uint32_t G_max = 0, cap_max = 0;                       // geometry of the largest pass
     uint64_t q_rays = 0;
@@ -154,6 +156,7 @@ inline int make_plan(const PlanIn &in, Plan &pl, const char **msg) {
     pl.sky_runs = pl.fused && k.sky_runs != 0;
     pl.pixel_table = pl.fused && k.pixel_table != 0;
     pl.reach_masks = pl.fused && k.reach_masks != 0;
+    pl.own_kernel = pl.fused && k.own_kernel != 0;
     pl.q_rays = (uint64_t)g.cap * waves;
     if (pl.q_rays > 0xFFFFFFFFull) return bad("pass too large");
     // the speculative launch: fresh renders only (a progressive SPIRA_SEM_METAL call updates sums and states in place), R = 2 instantiations only
@@ -225,6 +228,9 @@ struct PathLaunch {
     bool pixel_table = false, reach_masks = false;             // PathArgs, same names
     uint64_t own_lds = 0;                                      // bytes the launch's LDS block holds for the pixel table and the run masks (own_lds_bytes)
     uint32_t prec = 0, wpb = 0, carry_key = 0;
+    // what own_kernel_ok() reads on top: rays per lane, spheres of the scene, PathArgs::sky_runs / cam_consts, Plan::own_kernel
+    uint32_t R = 0, n_spheres = 0;
+    bool sky_runs = false, cam_consts = false, own_kernel = false;
 };
 struct PathNeed {
     uint64_t nw, packets, l_entries;       // waves; entries of every per-packet array; entries of L
@@ -247,6 +253,18 @@ inline PathNeed path_need(const PathLaunch &a) {
     // pixel table / reach masks: pixel-owning passes alone, and the launch's LDS block has their region
     n.table_ok = (!a.pixel_table && !a.reach_masks) || (a.pixel_owning && a.own_lds >= own_lds_bytes(a.wpb));
     return n;
+}
+
+// k_path_own (spira_device.h; its statements: spira_path_body.h with FIXED) renders this pass instead of k_path: exactly the passes whose facts that kernel holds as constants.
+// A full pixel-owning pass of 64 slots of a Float64 sphere scene (R = 2, no triangles of either kind, no extension, one launch), its radiance in
+// wave-private blocks (so the RNG key is carried: max_depth <= 128), all-sky runs, pixel table, reach masks (their LDS region granted) and the camera's
+// packets on, and a scene the reach mask has a bit for every sphere of.  Anything else — shorter passes above all (k_eff 1, 3, 6, a tail of 63) — is k_path's.
+inline bool own_kernel_ok(const PathLaunch &a) {
+    const PathNeed n = path_need(a);
+    return a.own_kernel && a.prec == 8 && a.R == 2 && !a.mesh && !a.n_lds_triangles && !(a.flags & (SPIRA_EXT_DIELECTRIC | SPIRA_EXT_SPECTRAL)) && a.mesh_mode == 0 &&
+           a.pixel_owning && n.owning_ok && a.l_private && n.private_ok &&
+           a.sky_runs && a.pixel_table && a.reach_masks && a.own_lds >= own_lds_bytes(a.wpb) && a.cam_consts &&
+           a.k_eff == 64 && a.n_spheres >= 1 && a.n_spheres <= 32 && a.max_depth <= 128 && a.carry_key != 0;
 }
 
 // ---- adaptive sampling (spira_render_adaptive_*; kernels in spira_adaptive.h): the sample schedule of a call and what its rounds need, as arithmetic.

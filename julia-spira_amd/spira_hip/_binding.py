@@ -43,7 +43,7 @@ MAX_DEPTH, MAX_SPP = 255, 1 << 24
 
 EXPORTS = [
     "spira_abi_version", "spira_build_id", "spira_last_error", "spira_device_count", "spira_set_device", "spira_get_counters",
-    "spira_get_sky_pixels", "spira_sky_pixel_f64", "spira_pixel_reach_f64",
+    "spira_get_sky_pixels", "spira_get_own_passes", "spira_sky_pixel_f64", "spira_pixel_reach_f64",
     "spira_shutdown", "spira_camera_lookat_f32", "spira_camera_lookat_f64", "spira_render_f32", "spira_render_f64",
     "spira_render_device_f32", "spira_render_device_f64", "spira_trace_paths_f32", "spira_trace_paths_f64",
     "spira_tonemap_f32", "spira_stripe_rows", "spira_accumulate_f32", "spira_accumulate_f64", "spira_accumulate_device_f32",
@@ -209,6 +209,13 @@ def counters():
     _check(lib().spira_get_sky_pixels(C.byref(sky)))
     d["sky_pixels"] = sky.value
     return d
+
+
+def own_passes():
+    """spira_get_own_passes: passes of the last render that k_path_own rendered (0 with SPIRA_OWN_KERNEL=0 and wherever every pass ran k_path)."""
+    n = C.c_uint64(0)
+    _check(lib().spira_get_own_passes(C.byref(n)))
+    return n.value
 
 
 def sky_pixel(camera12, width, height, i, j, spheres5):

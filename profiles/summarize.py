@@ -36,6 +36,9 @@ def short(name):
 def is_spec(name):
     """k_path<T, R, BVH, EXT, SPEC, MODE, TRI>: is this the speculative-division instantiation (the first launch of a pass)?"""
     n = short(name)
+    if n.startswith("k_path_own<"):      # k_path_own<T, SPEC>: the full pixel-owning pass in its own kernel, part of the dominant kernel like k_path
+        args = [a.strip() for a in n[n.index("<") + 1:n.rindex(">")].split(",")]
+        return len(args) >= 2 and args[1] == "true"
     if not n.startswith("k_path<"):
         return False
     args = [a.strip() for a in n[n.index("<") + 1:n.rindex(">")].split(",")]
