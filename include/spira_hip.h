@@ -681,7 +681,7 @@ int spira_camera_rays_f64(const double camera12[12], const spira_lens *lens, dou
 int spira_camera_rays_device_f32(const float camera12[12], const spira_lens *lens, float *d_rays6, void *stream);
 int spira_camera_rays_device_f64(const double camera12[12], const spira_lens *lens, double *d_rays6, void *stream);
 
-/* ---- hemisphere gather at surface points: irradiance sums and visibility counts for light probes, irradiance points and lightmap texels ----
+/* ---- hemisphere gather at surface points: irradiance sums and visibility counts for irradiance points and lightmap texels (light probes: below) ----
  * The reference has no baker; what these entries integrate is ray_color (examples/julia-raytracer.jl:328-367) and the hit scan (:242-258), over directions
  * drawn by the reference's own rejection idiom (random_in_unit_sphere, :309-316).  The caller gives POINTS; the library draws the hemisphere directions with
  * its own RNG inside the kernel, so a lightmap of n points at spp samples is one call on n x 6 values, not n * spp rays.
@@ -748,6 +748,56 @@ int spira_scene_gather_visible_device_f32(const spira_scene *scene, const float 
                                           uint32_t *d_visible_u32, uint8_t *d_out_valid, void *stream);
 int spira_scene_gather_visible_device_f64(const spira_scene *scene, const double *d_points6, uint32_t n_points, const spira_gather_visible *gv,
                                           uint32_t *d_visible_u32, uint8_t *d_out_valid, void *stream);
+
+/* ---- light probes: the radiance arriving at free points from the whole sphere, projected onto the nine real spherical harmonics of bands 0 .. 2 ----
+ * A probe is a point in free space with no normal; its answer must serve every normal a moving object later shows it.  That answer is 9 x 3 numbers:
+ * the projection of the incoming radiance onto Y_0 .. Y_8.  csrc/spira_probe.h is the authority for what follows.  All arithmetic in the call's
+ * precision T, in the written order, nothing fused.
+ * points3: n_points x [px py pz].  A point is INVALID when any of the three values is NaN or infinite.  There is no origin rule, as in the radiance entry.
+ *   q          for point k and sample s, the gather's draw, exactly: the rejection idiom under the key rng_key(sA, sB, key0 + k, s, 255), tries
+ *              t = 1 .. 64, scale 2^-20, a = (u0 - 1, u1 - 1, u2 - 1), accepted when (a.x a.x + a.y a.y) + a.z a.z < 1.
+ *   direction  qq = q.q, qh = q / sqrt(qq); where qq is below the smallest normal number of T (no try accepted), qh = (0, 0, 1).  A uniform point in the
+ *              ball, normalised, is uniform on the sphere: every valid point has a valid ray for every sample.
+ *   ray        [p, qh], qh NOT normalised again by the generator; the path's unit direction d is what the radiance entry's preparation gives for those six
+ *              values (s = (dx dx + dy dy) + dz dz, d = (dx, dy, dz) / sqrt(s)).
+ *   invalid    the generator writes six zeros.
+ *   basis      x y z = d; c0 = 0.28209479177387814, c1 = 0.4886025119029199, c2 = 1.0925484305920792, c3 = 0.31539156525252005, c4 = 0.5462742152960396,
+ *              double literals each rounded to T once:
+ *              Y0 = c0, Y1 = c1 y, Y2 = c1 z, Y3 = c1 x, Y4 = c2 (x y), Y5 = c2 (y z), Y6 = c3 (3 (z z) - 1), Y7 = c2 (x z), Y8 = c4 (x x - y y).
+ *              No Condon-Shortley sign: the ordering most graphics code uses.
+ *
+ * spira_sh9_basis_*: out9 = Y_0 .. Y_8 at the unit direction d_unit.  Host arithmetic.
+ *
+ * spira_probe_rays_*: rays6 = the ray list (n_points x 6) of ONE sample of every point.  The host form is host arithmetic (the same inline function the
+ * kernels call; no device needed).  The *_device_* form takes DEVICE pointers, is asynchronous on `stream`, synchronises and allocates nothing.
+ * Limits: NULL pointers, n_points == 0: SPIRA_E_INVALID; n_points > SPIRA_MAX_RAYS, key0 + n_points > 2^32, sample >= SPIRA_MAX_SPP: SPIRA_E_LIMIT.
+ *
+ * spira_scene_probe_sh_*: sum_sh is n_points x 9 x 3, INTERLEAVED ([k][j][channel]), caller-owned.  The entry ADDS: for every valid point k, for
+ * s = sample0 .. sample0 + spp - 1 ascending, L_s is the radiance spira_scene_radiance_* gives for the ray [p, qh(k, s)] at pixel key key0 + k, sample s,
+ * and sum[k][j][c] = sum[k][j][c] + Y_j(d_s) * L_s[c]: one product, then one addition.  So k calls of n samples leave bit for bit the sums of one call of
+ * k*n samples, a point list in chunks (key0 advanced by the points before the chunk) leaves bit for bit the sums of the whole list, and any pass split
+ * leaves the same bytes.  The SH coefficients of the radiance are (4 pi / spp) * sum: that scaling is the caller's, as pi / spp is for the gather.
+ * out_valid[k] = 0 and nothing added for an invalid point, 1 otherwise; out_valid may be NULL, sum_sh may not.  The struct is spira_radiance, unchanged;
+ * flags: 0, SPIRA_EXT_DIELECTRIC, SPIRA_EXT_SPECTRAL, any other bit SPIRA_E_UNSUPPORTED.  Errors, limits (n_points <= SPIRA_MAX_RAYS, key0 + n_points <= 2^32,
+ * sample0 + spp <= SPIRA_MAX_SPP), stream ordering, multi-device handles and the workspace are spira_scene_gather_*'s: every check before any device is
+ * touched; a call enqueued after a device-form update or rebuild on another stream sees the new tree; a handle made by spira_scene_create_multi_* is
+ * served by device 0's copy; the device form allocates only on its first call at a size (a call of one sample per point needs no workspace), and the
+ * workspace — the gather's, under the gather's knobs — stays in the device context until spira_shutdown.  n_points * spp may exceed 2^32: the call is
+ * split into passes by samples.  spira_get_counters is not affected by any of these entries. */
+void spira_sh9_basis_f32(const float d_unit[3], float out9[9]);
+void spira_sh9_basis_f64(const double d_unit[3], double out9[9]);
+int spira_probe_rays_f32(const float *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6);
+int spira_probe_rays_f64(const double *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *rays6);
+int spira_probe_rays_device_f32(const float *d_points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *d_rays6, void *stream);
+int spira_probe_rays_device_f64(const double *d_points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *d_rays6, void *stream);
+int spira_scene_probe_sh_f32(const spira_scene *scene, const float *points3, uint32_t n_points, const spira_radiance *rp,
+                             float *sum_sh, uint8_t *out_valid);
+int spira_scene_probe_sh_f64(const spira_scene *scene, const double *points3, uint32_t n_points, const spira_radiance *rp,
+                             double *sum_sh, uint8_t *out_valid);
+int spira_scene_probe_sh_device_f32(const spira_scene *scene, const float *d_points3, uint32_t n_points, const spira_radiance *rp,
+                                    float *d_sum_sh, uint8_t *d_out_valid, void *stream);
+int spira_scene_probe_sh_device_f64(const spira_scene *scene, const double *d_points3, uint32_t n_points, const spira_radiance *rp,
+                                    double *d_sum_sh, uint8_t *d_out_valid, void *stream);
 
 /* ---- progressive accumulation (checkpoint / resume / adaptive sampling) ----
  * The contract the reference's kernel was designed for and no host code uses: `current_sample_index`,

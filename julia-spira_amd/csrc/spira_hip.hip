@@ -46,6 +46,7 @@
 #include "spira_query.h"
 #include "spira_radiance.h"
 #include "spira_gather.h"
+#include "spira_probe.h"
 #include "spira_nearest.h"
 #include "spira_hits.h"
 #include "spira_knearest.h"
@@ -113,6 +114,8 @@ template <class T> struct Impl {
     static int gather_rays(const T *points6, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream);
     static int denoise(const T *color, const T *variance, const T *albedo, const T *normal, const T *depth, const spira_denoise *dn,
                        T *out_hdr, T *out_img, bool on_device, void *user_stream);
+    static int probe_sh(const spira_scene *h, const T *points3, uint32_t n_points, const spira_radiance *rp, T *sum_sh, uint8_t *out_valid, bool on_device, void *user_stream);
+    static int probe_rays(const T *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream);
 };
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
@@ -1835,11 +1838,12 @@ spira::RadianceKnobs read_radiance_knobs() {
     k.max_items = env_u32("SPIRA_RADIANCE_MAX_ITEMS", SPIRA_RADIANCE_MAX_ITEMS);
     return k;
 }
-// What Impl<T>::radiance and Impl<T>::gather do with their Args (RadianceArgs, GatherArgs) once the list's own two fields are set: the path constants, the
-// workspace, the staged list / sums / valid bytes, the passes.  list: the block of the caller's n rays or points (six values each).
+// What Impl<T>::radiance, Impl<T>::gather and Impl<T>::probe_sh do with their Args (RadianceArgs, GatherArgs, ProbeArgs) once the list's own two fields are
+// set: the path constants, the workspace, the staged list / sums / valid bytes, the passes.  list: the block of the caller's n rays or points;
+// sum_width: the values of one entry's sums (3; the probe's 9 x 3).
 template <class T, class A>
 int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radiance *rp, A &a, const StageBlock &list, uint32_t n, T *sum_rgb, uint8_t *out_valid,
-                   void (*const (&paths)[2][2])(A), void (*sum)(A)) {
+                   void (*const (&paths)[2][2])(A), void (*sum)(A), size_t sum_width = 3) {
     Ctx &c = *s.cp;
     if (int rc = c.L.ensure(pl.ws_entries * sizeof(spira::Pack3<T>))) return rc;
     if (int rc = attach_spd<T>(c, s.st, rp->flags, a.scene)) return rc;
@@ -1847,7 +1851,7 @@ int path_list_call(Session &s, const spira::RadiancePlan &pl, const spira_radian
     a.rc.flags = rp->flags; a.rc.max_depth = rp->max_depth; a.rc.spp = rp->spp;
     a.key0 = rp->key0;
     a.ws = pl.direct ? nullptr : (spira::Pack3<T> *)c.L.p;
-    const size_t sum_b = 3 * (size_t)n * sizeof(T);
+    const size_t sum_b = sum_width * (size_t)n * sizeof(T);
     StageBlock io[] = {list, {a.sum, sum_rgb, sum_b, kStageIn | kStageOut}, {a.valid, out_valid, n, kStageOut}};
     if (int rc = stage_in(s, io)) return rc;
     const size_t lds = spira::scene_lds_bytes<T>(a.scene.n_spheres, a.scene.n_materials, a.scene.n_triangles);
@@ -1982,6 +1986,43 @@ int spira_tu::Impl<T>::gather_rays(const T *points6, uint32_t n_points, uint32_t
     spira::GatherRaysArgs<T> a{};
     a.points = points6; a.rays = rays6; a.n = n_points; a.sample = sample; a.sA = sA; a.sB = sB; a.key0 = key0;
     hipLaunchKernelGGL(spira::k_gather_rays<T>, dim3((n_points + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
+    return s.close();
+}
+
+// ======================================================================= spira_scene_probe_sh_* / spira_probe_rays_*: light probes, nine SH terms of the incoming radiance
+// Kernels, the sampling rule and the basis: spira_probe.h.  The call is the gather's (path_list_call under make_gather_plan and the gather's knobs): one
+// k_probe launch per pass (+ k_probe_sum where a pass holds more than one sample per point), the workspace the context's L, a row of sums 27 values.
+template <class T>
+int spira_tu::Impl<T>::probe_sh(const spira_scene *h, const T *points3, uint32_t n_points, const spira_radiance *rp, T *sum_sh, uint8_t *out_valid, bool on_device, void *user_stream) {
+    using A = spira::ProbeArgs<T>;
+    void (*const paths[2][2])(A) = {{spira::k_probe<T, false, false>, spira::k_probe<T, false, true>}, {spira::k_probe<T, true, false>, spira::k_probe<T, true, true>}};
+    const char *msg = nullptr;
+    if (int rc = spira::probe_check(points3 != nullptr, rp != nullptr, sum_sh != nullptr, n_points, rp ? rp->spp : 1, rp ? rp->max_depth : 1, rp ? rp->flags : 0,
+                                    rp ? rp->sample0 : 0, rp ? rp->key0 : 0, rp ? rp->reserved : 0, &msg)) return fail(rc, msg);
+    Session s;
+    A a{};
+    if (int rc = open_list_call<T>(s, h, on_device, user_stream, a.scene)) return rc;
+    a.n_points = n_points;
+    const spira::GatherPlan pl = spira::make_gather_plan(n_points, rp->spp, (uint32_t)s.cp->num_cus, spira::kBlock, read_gather_knobs());
+    return path_list_call<T>(s, pl, rp, a, {a.points, points3, 3 * (size_t)n_points * sizeof(T), kStageIn}, n_points, sum_sh, out_valid, paths, spira::k_probe_sum<T>, 27);
+}
+
+// The generator: the host form runs probe_ray_generate<T> here, the device form launches k_probe_rays<T> over the same function.
+template <class T>
+int spira_tu::Impl<T>::probe_rays(const T *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream) {
+    const char *msg = nullptr;
+    if (int rc = spira::gather_rays_check(points3 != nullptr, rays6 != nullptr, n_points, sample, key0, &msg)) return fail(rc, msg);
+    uint32_t sA, sB;
+    spira::seed_halves(seed, sA, sB);
+    if (!on_device) {
+        for (uint32_t k = 0; k < n_points; ++k) spira::probe_ray_generate<T>(points3 + 3 * (size_t)k, sA, sB, key0 + k, sample, rays6 + 6 * (size_t)k);
+        return 0;
+    }
+    Session s;
+    if (int rc = Session::open(s, true, user_stream)) return rc;
+    spira::ProbeRaysArgs<T> a{};
+    a.points = points3; a.rays = rays6; a.n = n_points; a.sample = sample; a.sA = sA; a.sB = sB; a.key0 = key0;
+    hipLaunchKernelGGL(spira::k_probe_rays<T>, dim3((n_points + spira::kBlock - 1) / spira::kBlock), dim3(spira::kBlock), 0, s.st, a);
     return s.close();
 }
 namespace {
@@ -3297,6 +3338,33 @@ int spira_scene_gather_visible_device_f64(const spira_scene *scene, const double
                                           uint8_t *d_out_valid, void *stream) {
     return spira_tu::Impl<double>::gather_visible(scene, d_points6, n_points, gv, d_visible_u32, d_out_valid, true, stream);
 }
+// ---- light probes (spira_probe.h)
+int spira_probe_rays_f32(const float *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *rays6) {
+    return spira_tu::Impl<float>::probe_rays(points3, n_points, sample, seed, key0, rays6, false, nullptr);
+}
+int spira_probe_rays_f64(const double *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *rays6) {
+    return spira_tu::Impl<double>::probe_rays(points3, n_points, sample, seed, key0, rays6, false, nullptr);
+}
+int spira_probe_rays_device_f32(const float *d_points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, float *d_rays6, void *stream) {
+    return spira_tu::Impl<float>::probe_rays(d_points3, n_points, sample, seed, key0, d_rays6, true, stream);
+}
+int spira_probe_rays_device_f64(const double *d_points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, double *d_rays6, void *stream) {
+    return spira_tu::Impl<double>::probe_rays(d_points3, n_points, sample, seed, key0, d_rays6, true, stream);
+}
+int spira_scene_probe_sh_f32(const spira_scene *scene, const float *points3, uint32_t n_points, const spira_radiance *rp, float *sum_sh, uint8_t *out_valid) {
+    return spira_tu::Impl<float>::probe_sh(scene, points3, n_points, rp, sum_sh, out_valid, false, nullptr);
+}
+int spira_scene_probe_sh_f64(const spira_scene *scene, const double *points3, uint32_t n_points, const spira_radiance *rp, double *sum_sh, uint8_t *out_valid) {
+    return spira_tu::Impl<double>::probe_sh(scene, points3, n_points, rp, sum_sh, out_valid, false, nullptr);
+}
+int spira_scene_probe_sh_device_f32(const spira_scene *scene, const float *d_points3, uint32_t n_points, const spira_radiance *rp, float *d_sum_sh, uint8_t *d_out_valid, void *stream) {
+    return spira_tu::Impl<float>::probe_sh(scene, d_points3, n_points, rp, d_sum_sh, d_out_valid, true, stream);
+}
+int spira_scene_probe_sh_device_f64(const spira_scene *scene, const double *d_points3, uint32_t n_points, const spira_radiance *rp, double *d_sum_sh, uint8_t *d_out_valid, void *stream) {
+    return spira_tu::Impl<double>::probe_sh(scene, d_points3, n_points, rp, d_sum_sh, d_out_valid, true, stream);
+}
+void spira_sh9_basis_f32(const float d_unit[3], float out9[9]) { spira::sh9_basis<float>(d_unit, out9); }
+void spira_sh9_basis_f64(const double d_unit[3], double out9[9]) { spira::sh9_basis<double>(d_unit, out9); }
 // Test support, outside the ABI like spira_debug_radiance_plan: the plan a gather of n_points x spp gets on a device of num_cus CUs, with the knobs of the
 // environment as the entries read them.  out8: grid, wpb, spp_pass, n_pass, direct, workspace entries (low, high word), the item cap.  No device needed.
 int spira_debug_gather_plan(uint32_t n_points, uint32_t spp, uint32_t num_cus, uint32_t *out8) {

@@ -633,6 +633,14 @@ inline int gather_check(bool points, bool params, bool sums, uint32_t n_points, 
     if ((uint64_t)sample0 + spp > SPIRA_MAX_SPP) { *msg = "sample0 + spp exceeds 2^24"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_probe_sh_*: gather_check's rules and order, on a list of points without normals (the codes are the gather's; two messages name the probe)
+inline int probe_check(bool points, bool params, bool sums, uint32_t n_points, uint32_t spp, uint32_t max_depth, uint32_t flags, uint32_t sample0, uint32_t key0,
+                       uint32_t reserved, const char **msg) {
+    if (points && params && !sums) { *msg = "sum_sh is NULL"; return SPIRA_E_INVALID; }
+    const int rc = gather_check(points, params, true, n_points, spp, max_depth, flags, sample0, key0, reserved, msg);
+    if (rc == SPIRA_E_UNSUPPORTED) *msg = "flags: 0, SPIRA_EXT_DIELECTRIC and SPIRA_EXT_SPECTRAL are all the probe entries take";
+    return rc;
+}
 // spira_scene_gather_visible_*
 inline int gather_visible_check(bool points, bool params, bool counts, uint32_t n_points, uint32_t spp, uint32_t sample0, uint32_t key0, uint32_t flags,
                                 double t_min, double t_max, const char **msg) {

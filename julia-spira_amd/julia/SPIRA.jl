@@ -19,7 +19,7 @@ using Colors
 
 export Scene, Camera, Ray, Sphere, Material, Point3, Vec3, Color,
        render_hybrid_gpu, render_with_cpu, render, render_multi, create_scene, prepare_scene_data,
-       SceneHandle, destroy!, update!, rebuild!, gather_rays, gather_rays!, save_png, save_exr
+       SceneHandle, destroy!, update!, rebuild!, gather_rays, gather_rays!, probe_rays, probe_rays!, save_png, save_exr
 
 const libspira = get(ENV, "SPIRA_HIP_LIB", joinpath(@__DIR__, "..", "csrc", "libspira_hip.so"))
 
@@ -253,6 +253,37 @@ end
 function gather_rays!(d_rays::Ptr{Float64}, d_points6::Ptr{Float64}, n::Integer; sample::Integer=0, seed::Integer=0, key0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
     rc = ccall((:spira_gather_rays_device_f64, libspira), Cint, (Ptr{Float64}, UInt32, UInt32, UInt64, UInt32, Ptr{Float64}, Ptr{Cvoid}),
                d_points6, n, sample, seed, key0, d_rays, stream)
+    rc == 0 || spira_error(rc)
+    return d_rays
+end
+
+# The sphere rays of one sample of every light probe (spira_probe_rays_*): points3 = 3 n values [px py pz] per point (a probe has no normal), the result
+# 6 n values [p, qh] per point, qh uniform on the unit sphere (six zeros for an invalid point); point k draws under pixel key key0 + k.  Host arithmetic:
+# no device needed.  The list is what spira_scene_radiance_* takes; spira_scene_probe_sh_* draws these directions inside its kernels.
+function probe_rays(points3::Vector{Float32}; sample::Integer=0, seed::Integer=0, key0::Integer=0)
+    rays = Vector{Float32}(undef, 2 * length(points3))
+    rc = ccall((:spira_probe_rays_f32, libspira), Cint, (Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{Float32}),
+               points3, length(points3) ÷ 3, sample, seed, key0, rays)
+    rc == 0 || spira_error(rc)
+    return rays
+end
+function probe_rays(points3::Vector{Float64}; sample::Integer=0, seed::Integer=0, key0::Integer=0)
+    rays = Vector{Float64}(undef, 2 * length(points3))
+    rc = ccall((:spira_probe_rays_f64, libspira), Cint, (Ptr{Float64}, UInt32, UInt32, UInt64, UInt32, Ptr{Float64}),
+               points3, length(points3) ÷ 3, sample, seed, key0, rays)
+    rc == 0 || spira_error(rc)
+    return rays
+end
+# The device forms: n points in DEVICE memory to n rays in DEVICE memory, asynchronous on `stream`.
+function probe_rays!(d_rays::Ptr{Float32}, d_points3::Ptr{Float32}, n::Integer; sample::Integer=0, seed::Integer=0, key0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_probe_rays_device_f32, libspira), Cint, (Ptr{Float32}, UInt32, UInt32, UInt64, UInt32, Ptr{Float32}, Ptr{Cvoid}),
+               d_points3, n, sample, seed, key0, d_rays, stream)
+    rc == 0 || spira_error(rc)
+    return d_rays
+end
+function probe_rays!(d_rays::Ptr{Float64}, d_points3::Ptr{Float64}, n::Integer; sample::Integer=0, seed::Integer=0, key0::Integer=0, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:spira_probe_rays_device_f64, libspira), Cint, (Ptr{Float64}, UInt32, UInt32, UInt64, UInt32, Ptr{Float64}, Ptr{Cvoid}),
+               d_points3, n, sample, seed, key0, d_rays, stream)
     rc == 0 || spira_error(rc)
     return d_rays
 end

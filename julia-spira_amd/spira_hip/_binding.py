@@ -65,6 +65,8 @@ EXPORTS = [
     "spira_gather_rays_f32", "spira_gather_rays_f64", "spira_gather_rays_device_f32", "spira_gather_rays_device_f64",
     "spira_scene_gather_f32", "spira_scene_gather_f64", "spira_scene_gather_device_f32", "spira_scene_gather_device_f64",
     "spira_scene_gather_visible_f32", "spira_scene_gather_visible_f64", "spira_scene_gather_visible_device_f32", "spira_scene_gather_visible_device_f64",
+    "spira_sh9_basis_f32", "spira_sh9_basis_f64", "spira_probe_rays_f32", "spira_probe_rays_f64", "spira_probe_rays_device_f32", "spira_probe_rays_device_f64",
+    "spira_scene_probe_sh_f32", "spira_scene_probe_sh_f64", "spira_scene_probe_sh_device_f32", "spira_scene_probe_sh_device_f64",
     "spira_scene_closest_point_f32", "spira_scene_closest_point_f64", "spira_scene_closest_point_device_f32", "spira_scene_closest_point_device_f64",
     "spira_closest_point_triangle_f32", "spira_closest_point_triangle_f64",
     "spira_scene_cast_hits_f32", "spira_scene_cast_hits_f64", "spira_scene_cast_hits_device_f32", "spira_scene_cast_hits_device_f64",
@@ -304,7 +306,33 @@ def render_multi(spheres5, materials8, triangles10, camera12, params, n_devices,
     return hdr, img
 
 
-class Scene:
+class _SceneProbes:
+    """The light-probe entries of a scene handle (csrc/spira_probe.h): Scene inherits them.  They use the handle's `prec`, `_list` and `_query`."""
+
+    def probe_sh(self, points3, spp, max_depth, seed=0, sample0=0, key0=0, flags=0, sums=None, want_valid=False):
+        """spira_scene_probe_sh_*: path-traced radiance over the whole sphere of every point of points3 (n x [px py pz], host array; the library draws the
+        uniform directions itself, point k under pixel key key0 + k), projected onto the nine real spherical harmonics of bands 0 .. 2.  ADDS samples
+        sample0 .. sample0 + spp - 1, in order, to sums ([n, 9, 3], in place; None: a fresh zero array); the SH coefficients of the radiance are
+        4 pi * sums / spp.  Returns sums, or (sums, valid uint8 [n]) with want_valid."""
+        npdt, _ = _dt(self.prec)
+        p = self._list(points3, 3, "points3: n_points x [px py pz]")
+        n = len(p)
+        if sums is None:
+            sums = np.zeros((n, 9, 3), dtype=npdt)
+        if sums.dtype != npdt or not sums.flags["C_CONTIGUOUS"] or sums.shape != (n, 9, 3):
+            raise ValueError("sums: a contiguous [n_points, 9, 3] array of the handle's precision")
+        valid = np.empty(n, dtype=np.uint8) if want_valid else None
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        self._query("probe_sh", False, (p,), (n,), C.byref(rp), (sums, valid))
+        return (sums, valid) if want_valid else sums
+
+    def probe_sh_device(self, d_points_ptr, n_points, spp, max_depth, d_sums_ptr, seed=0, sample0=0, key0=0, flags=0, d_valid_ptr=0, stream_ptr=0):
+        """spira_scene_probe_sh_device_*: DEVICE addresses (d_valid_ptr 0 / None: not wanted), asynchronous on the stream; the sums are added to in place."""
+        rp = Radiance(spp, max_depth, flags, sample0, seed, key0, 0)
+        self._query("probe_sh", True, (d_points_ptr,), (n_points,), C.byref(rp), (d_sums_ptr, d_valid_ptr, stream_ptr))
+
+
+class Scene(_SceneProbes):
     """A scene resident on the current device (spira_scene_create_* / spira_scene_destroy): validated, its BVH built
     and everything uploaded once.  Use as a context manager or call destroy()."""
 
@@ -767,6 +795,42 @@ def gather_rays_device(d_points_ptr, n_points, d_rays_ptr, sample=0, seed=0, key
     fn = lib().spira_gather_rays_device_f32 if prec == "f32" else lib().spira_gather_rays_device_f64
     _check(fn(C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(sample), C.c_uint64(seed), C.c_uint32(key0), C.c_void_p(d_rays_ptr or None),
               C.c_void_p(stream_ptr or None)))
+
+
+def probe_rays(points3, sample=0, seed=0, key0=0, prec="f32"):
+    """spira_probe_rays_*: the sphere rays of one sample of every point of points3 (n x [px py pz]) as a host array [n, 6] = [p, qh], qh a uniform
+    direction on the unit sphere; six zeros for an invalid point.  Point k draws under pixel key key0 + k.  Host arithmetic; no device needed."""
+    npdt, _ = _dt(prec)
+    p = np.ascontiguousarray(points3, dtype=npdt)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("points3: n_points x [px py pz]")
+    out = np.empty((len(p), 6), dtype=npdt)
+    fn = lib().spira_probe_rays_f32 if prec == "f32" else lib().spira_probe_rays_f64
+    _check(fn(p.ctypes.data_as(C.c_void_p), C.c_uint32(len(p)), C.c_uint32(sample), C.c_uint64(seed), C.c_uint32(key0), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def probe_rays_device(d_points_ptr, n_points, d_rays_ptr, sample=0, seed=0, key0=0, stream_ptr=0, prec="f32"):
+    """spira_probe_rays_device_*: the same from a DEVICE array of n_points * 3 values into one of n_points * 6, asynchronous on the stream."""
+    _dt(prec)
+    fn = lib().spira_probe_rays_device_f32 if prec == "f32" else lib().spira_probe_rays_device_f64
+    _check(fn(C.c_void_p(d_points_ptr or None), C.c_uint32(n_points), C.c_uint32(sample), C.c_uint64(seed), C.c_uint32(key0), C.c_void_p(d_rays_ptr or None),
+              C.c_void_p(stream_ptr or None)))
+
+
+def sh9_basis(d, prec="f32"):
+    """spira_sh9_basis_*: the nine real spherical harmonics of bands 0 .. 2 at the unit directions d ([n, 3] or [3]), [n, 9] or [9] in `prec`."""
+    npdt, _ = _dt(prec)
+    dd = np.ascontiguousarray(d, dtype=npdt)
+    if dd.ndim not in (1, 2) or dd.shape[-1] != 3:
+        raise ValueError("d: [n, 3] or [3] unit directions")
+    rows = dd.reshape(-1, 3)
+    out = np.empty((len(rows), 9), dtype=npdt)
+    fn = lib().spira_sh9_basis_f32 if prec == "f32" else lib().spira_sh9_basis_f64
+    fn.restype = None
+    for k in range(len(rows)):
+        fn(rows[k].ctypes.data_as(C.c_void_p), out[k].ctypes.data_as(C.c_void_p))
+    return out.reshape(dd.shape[:-1] + (9,))
 
 
 def gather_plan(n_points, spp, num_cus):
