@@ -611,6 +611,40 @@ int spira_overlap_box_triangle_f64(const double v0[3], const double e1[3], const
 int spira_overlap_box_sphere_f32(const float centre[3], float radius, const float box10[10]);
 int spira_overlap_box_sphere_f64(const double centre[3], double radius, const double box10[10]);
 
+/* ---- triangle overlap queries on a scene handle: which objects does a triangle cut (mesh against mesh narrowphase, cloth or a skinned mesh against
+ *      the environment, selection by a cutting polygon, the pair list an intersection curve starts from) ----
+ * triangles10 is n x [q0 q1 q2 mat], the layout of a scene's triangles10: the array another handle was created from or updated with is a query list as it
+ * is, host or device.  The tenth value is never read (it may be NaN).
+ * Contract (csrc/spira_trioverlap.h states every formula in its written order and is the authority; all arithmetic in T, nothing fused): with
+ * g1 = q1 - q0, g2 = q2 - q0, g3 = g2 - g1, m = cross(g1, g2) and, for a scene triangle's record v0, e1, e2: u0 = v0 - q0, u1 = u0 + e1, u2 = u0 + e2,
+ * e3 = e2 - e1, n = cross(e1, e2), an axis L overlaps when min(dot(L, u_m)) <= max(0, dot(L, g1), dot(L, g2)) and min(0, dot(L, g1), dot(L, g2)) <=
+ * max(dot(L, u_m)) with no NaN among the six values — closed, touching counts.  A TRIANGLE is a candidate when all 20 axes overlap: the three world unit
+ * axes (the components themselves), n, m, the nine cross(g_i, e_j), the three cross(n, e_j) and the three cross(m, g_i) (which separate coplanar pairs),
+ * and n is not exactly (0, 0, 0).  A SPHERE is a shell: with dmin2 the squared distance of closest_point_triangle(q0, g1, g2, C) and dmax2 the largest
+ * squared distance from C to q0, q1, q2, it is a candidate when dmin2 <= R R && dmax2 >= R R.
+ * A query is INVALID — it never faults and never disturbs its neighbours — when any of its nine coordinates is NaN or infinite, m is not finite or is
+ * exactly (0, 0, 0) (a segment or a point is no triangle query), or — scenes with a tree only — the origin rule of the ray queries fails for one of its
+ * three vertices.  There is no extent rule.
+ * Outputs, max_list, flags, out_trips, the errors, the host and the device form and their ordering are spira_scene_overlap_box_*'s above, word for word,
+ * with "query triangle" for "box".  spira_overlap_tri_triangle_* / spira_overlap_tri_sphere_* are the leaf functions as host arithmetic (no device): 1, 0,
+ * or SPIRA_RAY_INVALID for a query that is invalid without a frame. */
+int spira_scene_overlap_tri_f32(const spira_scene *scene, const float *triangles10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                int *out_prim, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_overlap_tri_f64(const spira_scene *scene, const double *triangles10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                int *out_prim, uint32_t *out_count, uint32_t *out_trips);
+int spira_scene_overlap_tri_device_f32(const spira_scene *scene, const float *d_triangles10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                       int *d_out_prim, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+int spira_scene_overlap_tri_device_f64(const spira_scene *scene, const double *d_triangles10, uint32_t n, uint32_t max_list, uint32_t flags,
+                                       int *d_out_prim, uint32_t *d_out_count, uint32_t *d_out_trips, void *stream);
+int spira_scene_overlap_tri_any_f32(const spira_scene *scene, const float *triangles10, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_overlap_tri_any_f64(const spira_scene *scene, const double *triangles10, uint32_t n, uint32_t flags, uint8_t *out_hit);
+int spira_scene_overlap_tri_any_device_f32(const spira_scene *scene, const float *d_triangles10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+int spira_scene_overlap_tri_any_device_f64(const spira_scene *scene, const double *d_triangles10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream);
+int spira_overlap_tri_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float query10[10]);
+int spira_overlap_tri_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double query10[10]);
+int spira_overlap_tri_sphere_f32(const float centre[3], float radius, const float query10[10]);
+int spira_overlap_tri_sphere_f64(const double centre[3], double radius, const double query10[10]);
+
 /* ---- radiance along the CALLER'S rays on a scene handle: the integrator for any camera, light probe, irradiance point or lightmap texel ----
  * Replaces ray_color(ray, world, depth) of examples/julia-raytracer.jl:328-367 called once per ray and sample — the function the reference's render loop
  * calls with get_ray's ray (:398-402), here for a ray list the caller owns, with the estimator, RNG and sample order of every render entry.

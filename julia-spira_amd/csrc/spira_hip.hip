@@ -52,6 +52,7 @@
 #include "spira_knearest.h"
 #include "spira_sweep.h"
 #include "spira_overlap.h"
+#include "spira_trioverlap.h"
 #include "spira_sdf.h"
 
 // The library is built from this one file as THREE translation units (Makefile), because what the optimiser does to one family of kernels it undoes
@@ -116,6 +117,8 @@ template <class T> struct Impl {
                        T *out_hdr, T *out_img, bool on_device, void *user_stream);
     static int probe_sh(const spira_scene *h, const T *points3, uint32_t n_points, const spira_radiance *rp, T *sum_sh, uint8_t *out_valid, bool on_device, void *user_stream);
     static int probe_rays(const T *points3, uint32_t n_points, uint32_t sample, uint64_t seed, uint32_t key0, T *rays6, bool on_device, void *user_stream);
+    static int overlap_tri(const spira_scene *h, const T *triangles10, uint32_t n_tris, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                           uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream);
 };
 // defined in the SPIRA_TU_F64MESH unit: launch_path<double> of a mesh scene (PathArgs::mesh_mode 0 or 1) and launch_path_resume<double> (mode 2)
 int launch_path_mesh_f64(int R, dim3 grid, size_t lds, hipStream_t st, const spira::PathArgs<double> &a, int spec);
@@ -1803,6 +1806,33 @@ int spira_tu::Impl<T>::overlap(const spira_scene *h, const T *boxes10, uint32_t 
 }
 namespace {
 
+// ======================================================================= spira_scene_overlap_tri_* / spira_scene_overlap_tri_any_*: what a triangle cuts
+// Kernels, the contract and the margin argument: spira_trioverlap.h; the call is the box query's (its arguments, its check, its blocks) with these kernels.
+template <class T, bool ANY, int CAP>
+ListKernels<spira::TriOverlapArgs<T>> trioverlap_kernels() {
+    return {spira::k_trioverlap_session<T, ANY, CAP>, spira::k_trioverlap<T, true, false, ANY, CAP>, spira::k_trioverlap<T, false, true, ANY, CAP>,
+            spira::k_trioverlap<T, false, false, ANY, CAP>, false};
+}
+}  // namespace
+template <class T>
+int spira_tu::Impl<T>::overlap_tri(const spira_scene *h, const T *triangles10, uint32_t n_tris, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                                   uint8_t *out_hit, uint32_t *out_trips, bool any, bool on_device, void *user_stream) {
+    using A = spira::TriOverlapArgs<T>;
+    const char *msg = nullptr;
+    if (any) max_list = 0;
+    if (max_list == 0) out_prim = nullptr;      // (count only: the lists have no slots)
+    if (int rc = spira::overlap_tri_check(triangles10 != nullptr, n_tris, max_list, flags, any ? out_hit != nullptr : (out_prim || out_count), &msg)) return fail(rc, msg);
+    const ListKernels<A> kernels = any ? trioverlap_kernels<T, true, 1>()
+                                       : max_list <= 1 ? trioverlap_kernels<T, false, 1>() : max_list <= 4 ? trioverlap_kernels<T, false, 4>() : trioverlap_kernels<T, false, 16>();
+    A a{};
+    a.n = n_tris; a.max_list = max_list;
+    const size_t n = n_tris, slots = n * max_list;
+    StageBlock io[] = {{a.boxes, triangles10, 10 * n * sizeof(T), kStageIn}, {a.prim, out_prim, slots * sizeof(int), kStageOut}, {a.count, out_count, n * sizeof(uint32_t), kStageOut},
+                       {a.trips, out_trips, n * sizeof(uint32_t), kStageOut}, {a.hit, out_hit, n, kStageOut}};
+    return list_query_call<T>(h, n_tris, flags, on_device, user_stream, a, io, kernels);
+}
+namespace {
+
 // ======================================================================= spira_scene_signed_distance_*: the nearest surface of every point and which side of it
 // Kernels and the contract: spira_sdf.h; the call: list_query_call, with the kernels with or without the nearest walk (out_prim, out_dist and out_point
 // all NULL: the sign-only query).
@@ -3251,6 +3281,57 @@ int spira_overlap_box_sphere_f64(const double centre[3], double radius, const do
     spira::OverlapBox<double> B; double He[3];
     if (!spira::overlap_prepare<double>(box10, false, nullptr, B, He)) return SPIRA_RAY_INVALID;
     return spira::overlap_box_sphere<double>(B, centre, radius) ? 1 : 0;
+}
+
+// ---- triangle overlap queries on a scene handle (spira_trioverlap.h)
+int spira_scene_overlap_tri_f32(const spira_scene *scene, const float *triangles10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                                uint32_t *out_trips) {
+    return spira_tu::Impl<float>::overlap_tri(scene, triangles10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_overlap_tri_device_f32(const spira_scene *scene, const float *d_triangles10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim,
+                                       uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
+    return spira_tu::Impl<float>::overlap_tri(scene, d_triangles10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_overlap_tri_any_f32(const spira_scene *scene, const float *triangles10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return spira_tu::Impl<float>::overlap_tri(scene, triangles10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_overlap_tri_any_device_f32(const spira_scene *scene, const float *d_triangles10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return spira_tu::Impl<float>::overlap_tri(scene, d_triangles10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+int spira_scene_overlap_tri_f64(const spira_scene *scene, const double *triangles10, uint32_t n, uint32_t max_list, uint32_t flags, int *out_prim, uint32_t *out_count,
+                                uint32_t *out_trips) {
+    return spira_tu::Impl<double>::overlap_tri(scene, triangles10, n, max_list, flags, out_prim, out_count, nullptr, out_trips, false, false, nullptr);
+}
+int spira_scene_overlap_tri_device_f64(const spira_scene *scene, const double *d_triangles10, uint32_t n, uint32_t max_list, uint32_t flags, int *d_out_prim,
+                                       uint32_t *d_out_count, uint32_t *d_out_trips, void *stream) {
+    return spira_tu::Impl<double>::overlap_tri(scene, d_triangles10, n, max_list, flags, d_out_prim, d_out_count, nullptr, d_out_trips, false, true, stream);
+}
+int spira_scene_overlap_tri_any_f64(const spira_scene *scene, const double *triangles10, uint32_t n, uint32_t flags, uint8_t *out_hit) {
+    return spira_tu::Impl<double>::overlap_tri(scene, triangles10, n, 0u, flags, nullptr, nullptr, out_hit, nullptr, true, false, nullptr);
+}
+int spira_scene_overlap_tri_any_device_f64(const spira_scene *scene, const double *d_triangles10, uint32_t n, uint32_t flags, uint8_t *d_out_hit, void *stream) {
+    return spira_tu::Impl<double>::overlap_tri(scene, d_triangles10, n, 0u, flags, nullptr, nullptr, d_out_hit, nullptr, true, true, stream);
+}
+// the leaf functions as host arithmetic: the same inline functions the kernels call, compiled for the host
+int spira_overlap_tri_triangle_f32(const float v0[3], const float e1[3], const float e2[3], const float query10[10]) {
+    spira::TriQuery<float> Q;
+    if (!spira::trioverlap_prepare<float>(query10, false, nullptr, Q)) return SPIRA_RAY_INVALID;
+    return spira::overlap_tri_triangle<float>(Q, v0, e1, e2) ? 1 : 0;
+}
+int spira_overlap_tri_triangle_f64(const double v0[3], const double e1[3], const double e2[3], const double query10[10]) {
+    spira::TriQuery<double> Q;
+    if (!spira::trioverlap_prepare<double>(query10, false, nullptr, Q)) return SPIRA_RAY_INVALID;
+    return spira::overlap_tri_triangle<double>(Q, v0, e1, e2) ? 1 : 0;
+}
+int spira_overlap_tri_sphere_f32(const float centre[3], float radius, const float query10[10]) {
+    spira::TriQuery<float> Q;
+    if (!spira::trioverlap_prepare<float>(query10, false, nullptr, Q)) return SPIRA_RAY_INVALID;
+    return spira::overlap_tri_sphere<float>(Q, centre, radius) ? 1 : 0;
+}
+int spira_overlap_tri_sphere_f64(const double centre[3], double radius, const double query10[10]) {
+    spira::TriQuery<double> Q;
+    if (!spira::trioverlap_prepare<double>(query10, false, nullptr, Q)) return SPIRA_RAY_INVALID;
+    return spira::overlap_tri_sphere<double>(Q, centre, radius) ? 1 : 0;
 }
 
 // ---- signed distance queries on a scene handle (spira_sdf.h)

@@ -286,8 +286,9 @@ template <class T, int CAP> struct OverlapWalk {
     OverlapList<CAP> l;
 };
 
-template <class T, bool ANY, int CAP>
-__device__ __forceinline__ void overlap_store(const OverlapArgs<T> &a, uint32_t i, bool valid, const OverlapWalk<T, CAP> &w) {
+// (W: OverlapWalk<T, CAP>, or the walk of a query that shares the answer — spira_trioverlap.h.)
+template <class T, bool ANY, int CAP, class W>
+__device__ __forceinline__ void overlap_store(const OverlapArgs<T> &a, uint32_t i, bool valid, const W &w) {
     if (ANY) { a.hit[i] = valid ? (w.total ? (uint8_t)1 : (uint8_t)0) : (uint8_t)255; if (a.trips) a.trips[i] = w.trips; return; }
     const uint32_t K = a.max_list;
     if (a.prim) {
@@ -330,7 +331,7 @@ __device__ __forceinline__ bool overlap_load(const OverlapArgs<T> &a, const Scen
     return ok;
 }
 
-template <class T, int CAP> __device__ __forceinline__ void overlap_take(OverlapWalk<T, CAP> &w, uint32_t K, int p) {
+template <class T, int CAP, class W> __device__ __forceinline__ void overlap_take(W &w, uint32_t K, int p) {
     ++w.total;
     overlap_insert<CAP>(w.l, K, p);
 }
@@ -396,10 +397,11 @@ __device__ __forceinline__ uint32_t overlap_node(const uint4 w0, const uint4 w2,
     return surv;
 }
 
-// One trip of the box walk = ONE memory round trip (header comment, "The walk"), on the pieces of spira_device.h ("one TRIP") with the overlap's own
-// arms; no octant (the children are taken in slot order), the stack is private.  Returns false when the walk is over.
-template <class T, int CAP>
-__device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<T, CAP> &w, int base, uint32_t K, uint32_t *stack) {
+// One trip of an overlap walk = ONE memory round trip (header comment, "The walk"), on the pieces of spira_device.h ("one TRIP") with the overlap's own
+// node arm; no octant (the children are taken in slot order), the stack is private.  leaf(v0, e1, e2, id): the query's leaf arm on the record's own values
+// and the triangle's index within the mesh.  Returns false when the walk is over.
+template <class T, class W, class Leaf>
+__device__ __forceinline__ bool overlap_trip(const SceneLds<T> &sc, W &w, uint32_t *stack, Leaf &&leaf) {
     const bool is_tri = (w.tw >> 24) != 0;
     const uint4 *ptr;
     if (is_tri) ptr = reinterpret_cast<const uint4 *>(sc.bvh_tris + 3 * (size_t)walk_take_tri(w));
@@ -411,7 +413,7 @@ __device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<
         Pack4<T> a0, a1, a2;
         bvh8_tri_words(w0, w1, w2, w3, w4, w5, a0, a1, a2);
         const T v0[3] = {a0.x, a0.y, a0.z}, e1[3] = {a1.x, a1.y, a1.z}, e2[3] = {a2.x, a2.y, a2.z};
-        if (overlap_box_triangle<T>(w.B, v0, e1, e2)) overlap_take<T, CAP>(w, K, base + (int)Bits<T>::to_u32(a0.w));
+        leaf(v0, e1, e2, Bits<T>::to_u32(a0.w));
     } else {
         const uint32_t imask = w0.w >> 24;
         const uint32_t surv = overlap_node(w0, w2, w3, w4, w.qlo, w.qhi);
@@ -420,6 +422,14 @@ __device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<
         w.rank = w1.z;
     }
     return walk_pop(w, stack);
+}
+
+// One trip of the box walk: the leaf arm is the 13-axis SAT.
+template <class T, int CAP>
+__device__ __forceinline__ bool overlap_step(const SceneLds<T> &sc, OverlapWalk<T, CAP> &w, int base, uint32_t K, uint32_t *stack) {
+    return overlap_trip<T>(sc, w, stack, [&](const T v0[3], const T e1[3], const T e2[3], uint32_t id) {
+        if (overlap_box_triangle<T>(w.B, v0, e1, e2)) overlap_take<T, CAP>(w, K, base + (int)id);
+    });
 }
 
 // One lane per box.  Launches: <T, false, false, ..> spheres alone, <T, false, true, ..> with LDS triangles, <T, true, false, ..> a BVH mesh (SPIRA_CAST_INPLACE).

@@ -476,6 +476,14 @@ inline int overlap_check(bool boxes, uint32_t n, uint32_t max_list, uint32_t fla
     if ((uint64_t)n * max_list > SPIRA_MAX_RAYS) { *msg = "n * max_list is above SPIRA_MAX_RAYS (2^26) slots"; return SPIRA_E_LIMIT; }
     return 0;
 }
+// spira_scene_overlap_tri_* / spira_scene_overlap_tri_any_*: overlap_check's rules, case for case and in its order; only the two messages that name the
+// list speak of triangles.
+inline int overlap_tri_check(bool triangles, uint32_t n, uint32_t max_list, uint32_t flags, bool any_output, const char **msg) {
+    if (!triangles) { *msg = "the query triangle array is NULL"; return SPIRA_E_INVALID; }
+    const int rc = overlap_check(true, n, max_list, flags, any_output, msg);
+    if (rc == SPIRA_E_LIMIT && n > SPIRA_MAX_RAYS) *msg = "more than SPIRA_MAX_RAYS (2^26) query triangles";
+    return rc;
+}
 // spira_scene_signed_distance_*: closest point's rules; any_output: out_prim, out_dist, out_point, out_inside or out_crossings is given (out_trips alone is no
 // output).  With out_prim, out_dist and out_point all NULL the call is the sign-only query: the nearest walk is not run (signed_distance_wants_nearest).
 inline int signed_distance_check(bool points, uint32_t n_points, uint32_t flags, bool any_output, const char **msg) {

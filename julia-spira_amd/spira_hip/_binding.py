@@ -77,6 +77,9 @@ EXPORTS = [
     "spira_scene_overlap_box_f32", "spira_scene_overlap_box_f64", "spira_scene_overlap_box_device_f32", "spira_scene_overlap_box_device_f64",
     "spira_scene_overlap_any_f32", "spira_scene_overlap_any_f64", "spira_scene_overlap_any_device_f32", "spira_scene_overlap_any_device_f64",
     "spira_overlap_box_triangle_f32", "spira_overlap_box_triangle_f64", "spira_overlap_box_sphere_f32", "spira_overlap_box_sphere_f64",
+    "spira_scene_overlap_tri_f32", "spira_scene_overlap_tri_f64", "spira_scene_overlap_tri_device_f32", "spira_scene_overlap_tri_device_f64",
+    "spira_scene_overlap_tri_any_f32", "spira_scene_overlap_tri_any_f64", "spira_scene_overlap_tri_any_device_f32", "spira_scene_overlap_tri_any_device_f64",
+    "spira_overlap_tri_triangle_f32", "spira_overlap_tri_triangle_f64", "spira_overlap_tri_sphere_f32", "spira_overlap_tri_sphere_f64",
     "spira_scene_signed_distance_f32", "spira_scene_signed_distance_f64", "spira_scene_signed_distance_device_f32", "spira_scene_signed_distance_device_f64",
 ]
 
@@ -332,7 +335,42 @@ class _SceneProbes:
         self._query("probe_sh", True, (d_points_ptr,), (n_points,), C.byref(rp), (d_sums_ptr, d_valid_ptr, stream_ptr))
 
 
-class Scene(_SceneProbes):
+class _SceneTriOverlap:
+    """The triangle overlap entries of a scene handle (csrc/spira_trioverlap.h): Scene inherits them.  They use the handle's `_list`, `_flags` and `_query`."""
+
+    def _query_tris(self, triangles10):
+        return self._list(triangles10, 10, "triangles10: n x [q0 q1 q2 mat] (the tenth value is ignored)")
+
+    def overlap_tri(self, triangles10, max_list, inplace=False, want_prim=True, want_count=True, want_trips=False):
+        """spira_scene_overlap_tri_*: the objects that each triangle of triangles10 cuts (host array, n x [q0 q1 q2 mat], the layout of a scene's own
+        triangles10; the tenth value is ignored).  Returns (prim int32 [n, K], count uint32 [n], trips uint32 [n]) exactly as overlap_box does."""
+        t = self._query_tris(triangles10)
+        n, k = len(t), int(max_list)
+        room = k if 0 < k <= MAX_OVERLAP else 1      # (a refused max_list: the entry says so)
+        prim = np.empty((n, room), dtype=np.int32) if want_prim and k else None
+        count = np.empty(n, dtype=np.uint32) if want_count else None
+        trips = np.empty(n, dtype=np.uint32) if want_trips else None
+        self._query("overlap_tri", False, (t,), (n, k), self._flags(inplace), (prim, count, trips))
+        return prim, count, trips
+
+    def overlap_tri_any(self, triangles10, inplace=False):
+        """spira_scene_overlap_tri_any_*: uint8 [n] — 1 where the triangle cuts anything, 0 where nothing, 255 for an invalid query."""
+        t = self._query_tris(triangles10)
+        hit = np.empty(len(t), dtype=np.uint8)
+        self._query("overlap_tri_any", False, (t,), (len(t),), self._flags(inplace), (hit,))
+        return hit
+
+    def overlap_tri_device(self, d_triangles_ptr, n, max_list, d_prim_ptr, d_count_ptr, stream_ptr, inplace=False, d_trips_ptr=0):
+        """spira_scene_overlap_tri_device_*: DEVICE addresses (0 / None: output not wanted), asynchronous on the stream; nothing is synchronised or
+        allocated."""
+        self._query("overlap_tri", True, (d_triangles_ptr,), (n, max_list), self._flags(inplace), (d_prim_ptr, d_count_ptr, d_trips_ptr, stream_ptr))
+
+    def overlap_tri_any_device(self, d_triangles_ptr, n, d_hit_ptr, stream_ptr, inplace=False):
+        """spira_scene_overlap_tri_any_device_*: DEVICE addresses, asynchronous on the stream."""
+        self._query("overlap_tri_any", True, (d_triangles_ptr,), (n,), self._flags(inplace), (d_hit_ptr, stream_ptr))
+
+
+class Scene(_SceneProbes, _SceneTriOverlap):
     """A scene resident on the current device (spira_scene_create_* / spira_scene_destroy): validated, its BVH built
     and everything uploaded once.  Use as a context manager or call destroy()."""
 
@@ -1065,3 +1103,24 @@ def overlap_box_sphere(centre, radius, box10, prec):
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, ct, C.c_void_p]
     return int(fn(c.ctypes.data_as(C.c_void_p), ct(npdt(radius)), b.ctypes.data_as(C.c_void_p)))
+
+
+def overlap_tri_triangle(v0, e1, e2, query10, prec):
+    """spira_overlap_tri_triangle_*: the library's leaf function of the triangle overlap queries on one scene triangle (v0, e1 = v1 - v0, e2 = v2 - v0) and
+    one query [q0 q1 q2 mat], as host arithmetic (no device needed).  Returns 1, 0, or RAY_INVALID for a query that is invalid without a frame."""
+    npdt, _ = _dt(prec)
+    a = [np.ascontiguousarray(x, dtype=npdt).reshape(3) for x in (v0, e1, e2)] + [np.ascontiguousarray(query10, dtype=npdt).reshape(10)]
+    fn = lib().spira_overlap_tri_triangle_f32 if prec == "f32" else lib().spira_overlap_tri_triangle_f64
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 4
+    return int(fn(*[x.ctypes.data_as(C.c_void_p) for x in a]))
+
+
+def overlap_tri_sphere(centre, radius, query10, prec):
+    """spira_overlap_tri_sphere_*: the leaf function on one sphere (a shell) and one query, as host arithmetic.  Returns 1, 0 or RAY_INVALID."""
+    npdt, ct = _dt(prec)
+    c, q = np.ascontiguousarray(centre, dtype=npdt).reshape(3), np.ascontiguousarray(query10, dtype=npdt).reshape(10)
+    fn = lib().spira_overlap_tri_sphere_f32 if prec == "f32" else lib().spira_overlap_tri_sphere_f64
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, ct, C.c_void_p]
+    return int(fn(c.ctypes.data_as(C.c_void_p), ct(npdt(radius)), q.ctypes.data_as(C.c_void_p)))

@@ -1,7 +1,8 @@
 """Ray queries on a scene handle: the numpy restatement of the library's ray preparation (include/spira_hip.h, "ray queries") and the torch form of
 spira_scene_cast_device_* / spira_scene_occluded_device_*; the multi-hit queries (cast_all, count_hits, inside_mesh); the closest-point queries and the
 K-nearest ones (k_nearest, count_within); the sphere sweeps (sweep_spheres, sweep_segments) with the numpy twins of csrc/spira_sweep.h; the box overlap
-queries (overlap_boxes, voxelize) with the numpy twins of csrc/spira_overlap.h; the signed distance queries (signed_distance, inside_points,
+queries (overlap_boxes, voxelize) with the numpy twins of csrc/spira_overlap.h; the triangle overlap queries (overlap_triangles, mesh_pairs,
+meshes_intersect: spira_hip/trioverlap.py, named here) with the numpy twins of csrc/spira_trioverlap.h; the signed distance queries (signed_distance, inside_points,
 distance_field) with the numpy restatement of their sign rule.
 
 A ray is eight values [ox oy oz t_min dx dy dz t_max].  The library normalises the direction in the call's precision T, nothing fused:
@@ -722,3 +723,8 @@ def distance_field(scene, lo, hi, dims, band=None, stream=None):
         pts.record_stream(st)
         field = torch.where(inside == 255, torch.full_like(dist, float("nan")), dist)
         return field.reshape(dims[0], dims[1], dims[2])
+
+
+# ------------------------------------------------------------------ triangle overlap queries (spira_scene_overlap_tri_* / _tri_any_*; csrc/spira_trioverlap.h)
+from .trioverlap import (meshes_intersect, mesh_pairs, overlap_tri_sphere, overlap_tri_triangle, overlap_triangles,      # noqa: E402,F401
+                         prepare_triangles)
